@@ -10,12 +10,17 @@ A "step" is one wrapper-level env.step(): task action scaling -> locomotion poli
 fresh U(-1,1) actions every step (generator seed 1234).  Environments shard across ranks (weak scaling: 4096 envs
 per GPU); the only collective is the RCCL all-gather of the returned (obs, reward, done) batch.
 
-Prints ONE JSON line (rank 0).  value = agents x envs(all ranks) x steps / max-over-ranks wall time.
+Prints ONE JSON line (rank 0).  value = agents x envs(all ranks) x steps / max-over-ranks wall time; ms_per_step = that wall
+time / steps.  A plain run does only that: set up, warm up, time --steps steps, print.  --dump-outputs DIR also writes what the
+last timed step returned (obs, reward, done) as DIR/<name>.npy.  Everything below is --full only, measured after the clock stopped:
+the all-gather checks (N > 1), `value_long` (a timed region under 50 ms continued to >= 100 ms), the gather-schedule sweep
+(MQE_BENCH_SWEEP_GATHER=1), contact overflow counts, and
 `roofline`: dominant kernel (largest share of GPU time, HIP events on the launch stream over the timed region) charged with the
 whole step's algorithmic bytes (SURVEY 8d); `roofline_per_kernel`: every kernel class against ITS OWN bytes / flops;
 `strict_f32`: the same workload with every policy GEMM on the exact-f32 kernels (the companion of `dtype: f32`);
 `cpu_baseline` / `cpu_baseline_n4`: the build's CPU restatement (oracle/, kind "port") timed on this box's host cores at the
-GPU run's batch size (8 steps) and at N = 4 (BASELINE config 1).
+GPU run's batch size (8 steps) and at N = 4 (BASELINE config 1); `configs`: the other BASELINE configs that fit one GPU
+(go1gate at 4096 envs only).  MQE_BENCH_FULL=1 in the environment makes --full the default (the profiling scripts under tools/).
 NOTE: body_latest.jit is missing from the reference snapshot, so the locomotion-policy body is the deterministic
 synthetic 2102-512-256-128-12 ELU MLP (mqe/utils/policy_weights.py); the adaptation module and actuator net are real.
 """
@@ -39,6 +44,7 @@ PROF_KERNEL = ["k_gemm_h2", "k_gemm_f32", "k_compute_torques_mfma", "k_substeps"
 PEAK_F32_MFMA_TFLOPS = 157.3    # MI355X_MICROARCH.md: f32-input MFMA = f32 vector peak
 PEAK_F16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense f16 / bf16 MFMA peak
 PEAK_HBM_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E spec peak
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: all arrays together
 K_SPLIT = 30 * 48               # K of k_gemm_h2 over the history: MQE_HIST frames x MQE_H2_FRAME compact columns (csrc/mqe_common.hpp; tests/test_abi.py keeps the two in step)
 
 
@@ -263,6 +269,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--task", type=str, default="go1gate")
     ap.add_argument("--num_envs", type=int, default=4096, help="envs PER GPU (weak scaling)")
+    ap.add_argument("--full", action="store_true", default=bool(os.environ.get("MQE_BENCH_FULL")),
+                    help="everything beyond the headline (module docstring); off by default: a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (obs, reward, done) as DIR/<name>.npy, float32")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_strict_f32", action="store_true", help="skip the exact-f32 companion run")
     ap.add_argument("--no_configs", action="store_true", help="skip the other single-GPU BASELINE configs (`configs` on the line)")
@@ -360,6 +370,8 @@ def main():
         env.env.between_policy_and_physics = issue_gather if name == "between" else (wait_gathers if name == "tail" else None)
     set_schedule(sched[0])
 
+    returned = [None]             # (obs, reward, done) of the latest step: fresh tensors per step, what a caller of the path receives
+
     def one_step():
         t = step_no[0]
         a = actions[t % len(actions)]
@@ -373,6 +385,7 @@ def main():
                     pending[b].wait()
                     pending[b] = None
         o, r, d, info = env.step(a)
+        returned[0] = (o, r, d)
         if use_gather:
             ready[0] = (t & 1, env.returned_batch)
             if sched[0] == "after":
@@ -390,8 +403,7 @@ def main():
     for _ in range(args.warmup):
         one_step()
     drain()
-    # (no HIP-event brackets inside any timed region: profile_pass() below runs after the clocks have stopped)
-    prof_on = not os.environ.get("MQE_BENCH_NOPROF")
+    # (no HIP-event brackets inside any timed region: --full's profile_pass() runs after the clocks have stopped)
 
     def timed(n):
         """n steps bracketed by barrier + synchronize on both sides; seconds, MAX over ranks"""
@@ -414,6 +426,67 @@ def main():
             el = float(tt.item())
         return el
     elapsed = timed(args.steps)
+    last_step = returned[0]                      # the K-th timed step's outputs (later steps of --full return fresh tensors of their own)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step)
+    value = A * N * world * args.steps / elapsed
+    if rank == 0:
+        split = os.environ.get("MQE_GEMM_SPLIT", "1") != "0"
+        d = eng.desc
+        out = {
+            "metric": f"env-steps/sec (agents x envs x steps/s), {args.task} {N} envs x {A} agents per GPU",
+            "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32 (policy GEMMs and the actuator network's 32 x 32 layer: 2-plane split-f16, 22-bit)" if split else "f32", "data": "synthetic (U(-1,1) actions seed 1234; synthetic body MLP: body_latest.jit missing upstream)",
+            "config": {"workload": f"{args.task}, {A} agents, num_envs={N} per GPU ({N * world} total), 4 substeps x 5 ms per step",
+                       "parallelism": (f"env-sharded x{world}, " + ("no collective (per-GPU learners)" if args.no_gather else
+                                       f"all-gather of the returned batch issued {dict(between='between policy and physics of the next step', after='after the step, next step waits', tail='after layer 0 of the next step (beside the policy tail), physics waits')[args.gather]}"))
+                                      if world > 1 else "single GPU"},
+            "collective": None if (world == 1 and not solo_group) else ("none" if args.no_gather else {"op": "all_gather_into_tensor", "schedule": args.gather, "bytes_per_rank": int(4 * env.returned_batch.numel()),
+                                                                                  "gathers": n_gathers[0]}),
+            "target_env_steps_per_s": 1.0e6,
+            "contact_solver": {0: "pgs: velocity-level projected Gauss-Seidel, erp %.2f" % d.erp, 1: "tgs: temporal Gauss-Seidel, %d sub-steps of dt / %d (sim.physx.solver_type = 1)" % (d.solver_iterations, d.solver_iterations)}[int(d.solver_type)],
+            "binary": binary_info(),
+            "physical_robot_steps_per_s": round(value * env.env.num_agents / A, 1),
+            "dtype_note": "state and physics: f32.  Policy layer 0 + tail and (round 5) layer 2 of the actuator network: f32 operands carried as two f16 planes "
+                          "(22 significand bits, 3 MFMA terms), held to the same 5e-5 bound as exact f32; strict_f32 = the same run on the exact-f32 kernels",
+        }
+        if args.dump_outputs:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": ["obs", "reward", "done"], "step": args.warmup + args.steps}
+    if args.full:
+        full_report(args, env, eng, one_step, drain, timed, set_schedule, sched, gather, n_gathers, obs, elapsed,
+                    world, rank, dev, N, A, sharded, out if rank == 0 else None)
+    if rank == 0:
+        print(json.dumps(out))
+    env.close()
+    if world > 1 or solo_group:
+        dist.destroy_process_group()
+
+
+def dump_outputs(dirname, last_step):
+    """--dump-outputs: what the K-th timed step returned to its caller -- obs (N, A, D), reward (N, A, 1), done (N,) as 0 / 1 --
+    as float32 .npy files (4096 x 2 envs: 0.6 MB in all; a batch whose arrays exceed DUMP_MAX_BYTES is written as a fixed, seeded
+    sample of its envs, the same rows of every array, their indices in env_index.npy).  Inputs are seeded, so two builds given the
+    same arguments can be compared array for array."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = [t.detach().to(torch.float32).cpu().numpy() for t in last_step]
+    n = arrays[0].shape[0]
+    row_bytes = sum(a[:1].nbytes for a in arrays)
+    if n * row_bytes > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // (row_bytes + 8), replace=False))   # + 8 B: its index
+        arrays = [a[keep] for a in arrays]
+        np.save(os.path.join(dirname, "env_index.npy"), keep.astype(np.float64))
+    for name, a in zip(("obs", "reward", "done"), arrays):
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def full_report(args, env, eng, one_step, drain, timed, set_schedule, sched, gather, n_gathers, obs, elapsed,
+                world, rank, dev, N, A, sharded, out):
+    """--full: everything the line carries beyond the headline, measured after its clock has stopped -- the all-gather checks, the
+    long run, per-kernel HIP-event times and rooflines, the gather-schedule sweep, the strict-f32 / pgs companions, the other
+    BASELINE configs and the CPU baselines.  Adds its keys to `out` (rank 0; None on the other ranks)."""
+    prof_on = not os.environ.get("MQE_BENCH_NOPROF")
     use_gather = sched[0] != "none"
     if use_gather:   # every step's batch was gathered, and the last one arrived whole: this rank's slice is its own snapshot
         b = (args.warmup + args.steps - 1) & 1
@@ -424,7 +497,6 @@ def main():
     gathers_contract = n_gathers[0]              # collectives of the warm-up + the K timed steps (the long run below adds its own)
     overflow_substeps = int(env.env.contact_overflow.sum().item())      # truncated contact lists over the whole run (after the clock stopped)
     reduced_substeps = int(eng.tensor(abi_mod().T_CONTACT_REDUCED).sum().item())   # env-substeps with a robot's contacts reduced to its deepest eight
-    value = A * N * world * args.steps / elapsed
     # A timed region shorter than 50 ms (the driver's --steps 20 is 4.6 ms) is below the resolution of everything that watches the
     # box from outside (rocm-smi samples, the driver's own clock): the same loop is continued until >= 100 ms of GPU time have been
     # timed and reported beside the contract's number as value_long (value itself stays the K steps the caller asked for).
@@ -565,23 +637,11 @@ def main():
             else:
                 row.update({"bound": "latency / hbm"})
             table.append(row)
-        out = {
-            "metric": f"env-steps/sec (agents x envs x steps/s), {args.task} {N} envs x {A} agents per GPU",
-            "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32 (policy GEMMs and the actuator network's 32 x 32 layer: 2-plane split-f16, 22-bit)" if split else "f32", "data": "synthetic (U(-1,1) actions seed 1234; synthetic body MLP: body_latest.jit missing upstream)",
-            "config": {"workload": f"{args.task}, {A} agents, num_envs={N} per GPU ({N * world} total), 4 substeps x 5 ms per step",
-                       "parallelism": (f"env-sharded x{world}, " + ("no collective (per-GPU learners)" if args.no_gather else
-                                       f"all-gather of the returned batch issued {dict(between='between policy and physics of the next step', after='after the step, next step waits', tail='after layer 0 of the next step (beside the policy tail), physics waits')[args.gather]}"))
-                                      if world > 1 else "single GPU"},
-            "collective": None if (world == 1 and not solo_group) else ("none" if args.no_gather else {"op": "all_gather_into_tensor", "schedule": args.gather, "bytes_per_rank": int(4 * env.returned_batch.numel()),
-                                                                                  "gathers": gathers_contract, "gathers_incl_long_run_and_sweep": n_gathers[0]}),
-            "target_env_steps_per_s": 1.0e6,
-            "contact_solver": {0: "pgs: velocity-level projected Gauss-Seidel, erp %.2f" % d.erp, 1: "tgs: temporal Gauss-Seidel, %d sub-steps of dt / %d (sim.physx.solver_type = 1)" % (d.solver_iterations, d.solver_iterations)}[int(d.solver_type)],
+        if out["collective"] not in (None, "none"):
+            out["collective"].update({"gathers": gathers_contract, "gathers_incl_long_run_and_sweep": n_gathers[0]})
+        out.update({
             "value_long": long_run["value"] if long_run else None, "ms_per_step_long": long_run["ms_per_step"] if long_run else None, "long_run": long_run,
             "gather_schedule_sweep": sweep,
-            "binary": binary_info(),
-            "physical_robot_steps_per_s": round(value * env.env.num_agents / A, 1),
             "roofline": roof,
             "roofline_policy_layer0": l0,
             "roofline_per_kernel": table,
@@ -596,9 +656,7 @@ def main():
             "contact_reduced_substeps": reduced_substeps,        # env-substeps in which a robot's one-sided contacts were reduced to its deepest eight
             "hip_event_sampling": (f"{sampled} steps bracketed (one per period of 4) AFTER the timed regions; an empty event pair reads {pair_ms:.4f} ms on this stream, "
                                    "subtracted per launch (raw sums beside)") if prof_on else "off",
-            "dtype_note": "state and physics: f32.  Policy layer 0 + tail and (round 5) layer 2 of the actuator network: f32 operands carried as two f16 planes "
-                          "(22 significand bits, 3 MFMA terms), held to the same 5e-5 bound as exact f32; strict_f32 = the same run on the exact-f32 kernels",
-        }
+        })
         if world == 1 and not args.no_strict_f32 and not os.environ.get("MQE_BENCH_NOPROF"):
             # the dtype claim's companion: identical workload with every policy GEMM on the exact-f32 kernels
             sms, _ = time_variant(args.task, N, dev, min(args.steps, 100), min(args.warmup, 10), {"MQE_GEMM_SPLIT": "0", "MQE_NO_FUSED_TAIL": "1", "MQE_ACT_F32": "1"})
@@ -623,10 +681,6 @@ def main():
             v4, secs4, nthr4 = cpu_baseline(args.task, 4, 2000, threads=4)
             out["cpu_baseline_n4"] = {"value": round(v4, 1), "unit": "env-steps/s", "cores": nthr4, "kind": "port",
                                       "sample": f"{args.task} 4 envs x 2000 steps (BASELINE config 1 size), {secs4:.1f} s"}
-        print(json.dumps(out))
-    env.close()
-    if world > 1 or solo_group:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

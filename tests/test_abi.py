@@ -82,7 +82,7 @@ def test_bench_flop_basis_matches_the_kernel_constants():
 
 
 def test_bench_times_every_single_gpu_baseline_config():
-    """BASELINE.json names five configs; the default bench.py run carries the headline (configs[1]) as `value` and the other ones that fit one
+    """BASELINE.json names five configs; a bench.py --full run carries the headline (configs[1]) as `value` and the other ones that fit one
     GPU -- go1sheep-hard 2048, go1seesaw 4096, go1football-defender's 4096-env shard -- as `configs[]` (VERDICT r4 "Next" 2), at the sizes named."""
     import importlib.util
     import json

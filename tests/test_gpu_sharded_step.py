@@ -102,7 +102,7 @@ def test_step_end_without_begin_is_an_error():
     ("go1gate", "29651", 8, ["--no_gather"]), ("go1gate", "29653", 8, ["--gather", "tail"]), ("go1football-defender", "29655", 2, ["--gather", "tail"])])
 def test_bench_sharded_schedules_over_gloo(task, port, world, extra):
     """bench.py --gpus N as the driver launches it, all ranks on cuda:0 over gloo (world sizes 2 and 8 = the node the driver
-    measures on): every step's batch is gathered and arrives whole -- bench.py asserts both -- under both schedules of the
+    measures on): every step's batch is gathered and arrives whole -- bench.py --full asserts both -- under both schedules of the
     collective (issued between policy and physics of the next step | issued after the step, next step waits) and without a
     collective (per-GPU learners).  go1football-defender = BASELINE config 5's sharded path: 3 robots per env, the scripted
     defender and the reset draws keyed by the global env id."""
@@ -110,7 +110,7 @@ def test_bench_sharded_schedules_over_gloo(task, port, world, extra):
     n = 128 if world == 2 else 32
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "12", "--warmup", "3",
-           "--num_envs", str(n), "--no_cpu_baseline", "--task", task] + extra
+           "--num_envs", str(n), "--no_cpu_baseline", "--full", "--task", task] + extra
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

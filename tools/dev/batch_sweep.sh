@@ -7,7 +7,7 @@ python - <<PY > gpurun_out/${T}_batch_sweep.json
 import json, subprocess, sys
 rows = []
 for n in (1, 256, 1000, 2048, 3072, 4096, 4097, 4352, 4608, 5120, 6144, 8192, 8193, 10240, 12288):
-    out = subprocess.run([sys.executable, "bench.py", "--num_envs", str(n), "--steps", "100", "--warmup", "20", "--no_cpu_baseline", "--no_strict_f32"],
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--num_envs", str(n), "--steps", "100", "--warmup", "20", "--no_cpu_baseline", "--no_strict_f32"],
                          capture_output=True, text=True).stdout
     line = [l for l in out.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)

@@ -1,3 +1,4 @@
+export MQE_BENCH_FULL=1     # every bench.py line below (and in the scripts called) is a --full run
 for pad in 0 1400 3000 5400; do
   MQE_PHYS_LDS_PAD=$pad MQE_VERBOSE=1 python bench.py --task go1football-defender --num_envs 4096 --steps 150 --warmup 20 --no_cpu_baseline --no_strict_f32 2> gpurun_out/r05f/err_$pad.txt | grep "^{" | python -c "
 import sys, json

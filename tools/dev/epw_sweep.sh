@@ -9,7 +9,7 @@ rows = []
 for n in (4096, 4608, 5120, 6144, 8192, 12288, 16384):
     for epw in (1, 2):
         env = dict(os.environ, MQE_ENVS_PER_WAVE=str(epw))
-        out = subprocess.run([sys.executable, "bench.py", "--num_envs", str(n), "--steps", "100", "--warmup", "20", "--no_cpu_baseline", "--no_strict_f32"],
+        out = subprocess.run([sys.executable, "bench.py", "--full", "--num_envs", str(n), "--steps", "100", "--warmup", "20", "--no_cpu_baseline", "--no_strict_f32"],
                              capture_output=True, text=True, env=env).stdout
         d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
         rows.append({"num_envs": n, "envs_per_wavefront": epw, "env_steps_per_s": d["value"], "ms_per_step": d["ms_per_step"],

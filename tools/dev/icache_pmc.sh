@@ -2,7 +2,7 @@
 # instruction-cache counters of the step's kernels (run from the repo root on the GPU box): gpurun_out/r06_icache/summary.txt
 R=$PWD; O=$R/gpurun_out/r06_icache; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVE_CYCLES SQ_WAVES --kernel-trace --output-format csv -d $O/pmc -- python $R/bench.py --steps 30 --warmup 5 --no_cpu_baseline --no_strict_f32 > $O/pmc.log 2>&1
+rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVE_CYCLES SQ_WAVES --kernel-trace --output-format csv -d $O/pmc -- python $R/bench.py --full --steps 30 --warmup 5 --no_cpu_baseline --no_strict_f32 > $O/pmc.log 2>&1
 cd $R
 python - > $O/summary.txt <<PY
 import csv, glob, collections

@@ -3,6 +3,7 @@
 #   usage: tools/dev/refresh_profiles.sh r04
 # then, back in the container: python tools/summarize_pmc.py <tag>, and copy the gpurun_out/<tag>_* summaries into profiles/.
 set -u
+export MQE_BENCH_FULL=1     # every bench.py line below (and in the scripts called) is a --full run
 T=${1:-r04}
 R=$PWD; mkdir -p gpurun_out
 tools/profile_round.sh $T > gpurun_out/${T}_round.log 2>&1

@@ -3,6 +3,7 @@
 # times): what a round's last commits change when they leave the arithmetic alone.  Run from the repo root on the GPU box:
 #   usage: tools/dev/refresh_profiles_short.sh r06f
 set -u
+export MQE_BENCH_FULL=1     # every bench.py line below (and in the scripts called) is a --full run
 T=${1:-r06f}
 R=$PWD; mkdir -p gpurun_out
 tools/profile_round.sh $T > gpurun_out/${T}_round.log 2>&1
