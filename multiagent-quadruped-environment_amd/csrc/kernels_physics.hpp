@@ -2543,7 +2543,7 @@ struct PostArgs { int on, wrapper_level, push_count, step_no; };
 // TIMED (MQE_PHASE_TIMES=1, tools/dev/phase_walltimes.py): the same kernel with the phase taps of phys_substep live -- every wavefront
 // writes the wall clock at the 15 taps of each of its substeps (+ [15]: the substep's end) behind the entry / exit stamps of
 // st.wave_times: where the time of a FULL launch goes, phase by phase, as opposed to the lone wavefront of tools/phase_times.py.
-// ACT32: the actuator network's layer 2 as the exact f32 MFMA chain (MQE_ACT_F32=1: torques bit for bit the oracle's fmaf chain); default:
+// ACT32: the actuator network's layer 2 as the f32 MFMA chain (MQE_ACT_F32=1; f32 operands, not the oracle's fmaf order bit for bit); default:
 // two-plane split-f16 operands on v_mfma_f32_32x32x16_f16 (f32-class accuracy, 22 significand bits per operand).  A compile-time choice: with
 // both forms behind a run-time branch the 128-register kernels spilled 20-50 registers.
 template <int TA, int TP, int EPW = 1, bool TIMED = false, bool ACT32 = false>

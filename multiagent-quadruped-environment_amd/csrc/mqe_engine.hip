@@ -456,6 +456,8 @@ extern "C" int mqe_sim_create(const mqe_sim_desc* d, mqe_sim** out) {
   if (getenv("MQE_VERBOSE")) {
     const char* names[] = {"MQE_LANE_SWEEP", "MQE_PHYS_LDS_PAD", "MQE_NO_FUSE_SUBSTEPS", "MQE_GEMM_SPLIT", "MQE_NO_FUSED_TAIL", "MQE_DEBUG_STOP_PHASE", "MQE_ENVS_PER_WAVE", "MQE_ACT_F32"};
     fprintf(stderr, "mqe: k_substeps runs %d env(s) per wavefront\n", s->substeps_epw);
+    static const char* shape_names[] = {"SH_A2", "SH_A1", "SH_A2_NOPAD", "SH_A2_LINK", "SH_A2_NPC_FEW", "SH_A2_BOX_FEW", "SH_A2_STATIC_FEW", "SH_A3_NPC_ROW", "SH_A2_NPC", "SH_A4_NPC", "SH_A2_GEN", "SH_GEN"};
+    fprintf(stderr, "mqe: variant shape=%s epw=%d actuator=%s post=%s\n", shape_names[shape], s->substeps_epw, act32 ? "f32" : "f16", s->fuse_post ? "fused" : "separate");
     for (const char* n : names)
       if (const char* v = getenv(n)) fprintf(stderr, "mqe: override in effect: %s=%s\n", n, v);
   }

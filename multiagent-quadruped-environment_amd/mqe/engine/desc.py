@@ -116,8 +116,9 @@ def task_kind(cfg):
 
 def build_desc(cfg, num_envs, terrain, env_origins, agent_origins, gate_pos=None, env_id_offset=0, seed=0,
                task=None, body=None, resources_root=None, solver_iterations=None, erp=0.2, noise_mode=0, solver_type=None, velocity_iterations=None,
-               terrain_levels=None, terrain_types=None, collision_model=None, edge_contacts=None):
-    """Returns (SimDesc, keepalive) -- keepalive holds the numpy arrays the struct points into."""
+               terrain_levels=None, terrain_types=None, collision_model=None, edge_contacts=None, actuator=None):
+    """Returns (SimDesc, keepalive) -- keepalive holds the numpy arrays the struct points into.
+    body / actuator: (Ws, bs) in place of the shipped policy body / actuator network (unitree_go1.pt)."""
     keep = []
     d = abi.SimDesc()
     A = getattr(cfg.env, "num_agents", 1)
@@ -446,7 +447,7 @@ def build_desc(cfg, num_envs, terrain, env_origins, agent_origins, gate_pos=None
         d.wrapper_param[0] = kw["init"]["block_length"] + kw["gate"]["block_length"] + kw["plane"]["block_length"] / 2
         d.wrapper_param[1] = kw["track_width"] / 4
     # networks
-    aW, ab = policy_weights.load_actuator_net()
+    aW, ab = policy_weights.load_actuator_net() if actuator is None else actuator
     dW, db = policy_weights.load_adaptation_module()
     if body is None:
         bW, bb, synthetic = policy_weights.load_body(getattr(ctl, "locomotion_policy_dir", None), seed=0)
