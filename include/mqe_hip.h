@@ -12,6 +12,7 @@
  *   ROOT_STATE     [N, A+P, 13]  pos3, quat4 (xyzw), linvel3, angvel3 in world frame; agents first   (:567-574)
  *   DOF_STATE      [N, 12A+Dn, 2] (pos, vel); agent dofs first, NPC dofs after                        (:577-585)
  *   CONTACT_FORCE  [N, 17A+Bn, 3] net contact force per reported rigid body, agents first             (:595)
+ *   RIGID_BODY_STATE [N, 17A+Bn, 13] the same rows: link-frame origin, quat, linvel, angvel (legged_robot_field.py:196-197)
  *   TORQUES        [N, 12A]                                                                            (:605)
  * Leg/DOF order inside one robot: FL, FR, RL, RR x (hip, thigh, calf); bodies: base, then per leg hip, thigh,
  * calf, foot.
@@ -31,8 +32,9 @@ extern "C" {
  * list holds the sum of its per-actor caps (+ 8 two-actor slots in scenes of more than four actors, at most 64) instead of min(40, .), and
  * mqe_sim_create refuses a scene whose caps exceed 64; edge_contacts bit 8 + MQE_T_CONTACT_REDUCED (new tensor): optional manifold reduction of a
  * robot's one-sided contacts to its DEEPEST eight instead of the first eight in feature order.  v16 (round 6) over v15: mqe_debug_epilogue_times
- * (new export). */
-#define MQE_ABI_VERSION 16
+ * (new export).  v17 over v16: MQE_T_RIGID_BODY_STATE (new tensor kind before MQE_T_COUNT), mqe_refresh_rigid_body_state and
+ * mqe_set_rigid_body_refresh (new exports). */
+#define MQE_ABI_VERSION 17
 #define MQE_MAX_SPHERES 64    /* feature points of one robot (the capsule model has 32, the exact one 60) */
 #define MQE_MAX_PRIMS 20      /* collision primitives of one robot (Go1: 18) */
 #define MQE_MAX_SELF_PAIRS 384
@@ -303,6 +305,12 @@ enum {
                             * points than its eight one-sided slots and the set was reduced (penetrations of more than 1 mm first, deepest 2 mm class first, then feature
                             * order: feet first); MQE_T_CONTACT_OVERFLOW then counts only what is dropped in list order (NPC caps, the two-actor
                             * share, the end of the list).  Without the bit (default): always zero, robots' extra contacts count as overflow */
+  MQE_T_RIGID_BODY_STATE,  /* [N, NBR, 13] (v17) Isaac Gym's rigid-body state tensor: the rows of MQE_T_CONTACT_FORCE in their order; origin of the
+                              link frame, quaternion xyzw, linear velocity of that origin, angular velocity, all world frame.  Robot rows: base =
+                              the root row (bit-equal), hip / thigh / calf by the kinematic chain, foot = its calf moved by the foot joint's origin.
+                              NPC rows: a free NPC's root row; a 1-dof link scene's fixed base, then its link from the NPC dof; a static scenery
+                              actor's root pose with zero velocity in each of its rows.  Written only by mqe_refresh_rigid_body_state and, while
+                              mqe_set_rigid_body_refresh is on, by every post-physics step; derived data, not part of mqe_state_save's blob */
   MQE_T_COUNT
 };
 
@@ -417,6 +425,16 @@ int mqe_step_joint(mqe_sim* s, const float* actions12, void* stream);
  * (tests/test_camera_oracle.py); the kernel is held to it per pixel on 8 scenes (tests/test_camera_gpu.py: <= 0.2 % of the pixels -- silhouettes -- may differ in hit / miss or depth, the rest agree to 1e-4 m + 1e-5 relative).  Colour images (IMAGE_COLOR) are not offered. */
 int mqe_render_depth(mqe_sim* s, float* out_dev, int height, int width, float horizontal_fov_deg, const float* cam_pos3, const float* cam_rpy3,
                      float far_m, void* stream);
+
+/* gym.refresh_rigid_body_state_tensor (legged_robot_field.py:117-119): MQE_T_RIGID_BODY_STATE from the CURRENT root and dof state.
+ * Enqueued on `stream`. */
+int mqe_refresh_rigid_body_state(mqe_sim* s, void* stream);
+/* on != 0: every post-physics step refreshes MQE_T_RIGID_BODY_STATE first -- after the last substep, before termination, the NPC script
+ * and the resets (an env reset in that step shows its terminal pose, as upstream) -- in mqe_step, mqe_step_end, mqe_step_command,
+ * mqe_step_joint, mqe_post_physics_step and mqe_post_physics_stage calls that include MQE_POST_FRAME.  A fused step then runs its
+ * post-physics step as a launch of its own instead of the physics kernel's epilogue (the same arithmetic).  0 (the default): no step
+ * launches it.  mqe_reset_all and mqe_state_load never refresh it.  Host-side switch; not inside an open step. */
+int mqe_set_rigid_body_refresh(mqe_sim* s, int on);
 
 /* After host writes into MQE_T_HISTORY (obs_history of the reference, go1.py:102,145): rebuilds what the engine derives from the ring --
  * the compact split-f16 operand of layer 0, the presence flags (a frame of 70 zeros is absent), the carrier columns, the continuity

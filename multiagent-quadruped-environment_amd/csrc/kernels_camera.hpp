@@ -44,6 +44,34 @@ __device__ __forceinline__ void caxis(CV3 a, float q, float* R) {    // rotation
   R[3] = t * a.x * a.y + s * a.z; R[4] = t * a.y * a.y + c; R[5] = t * a.y * a.z - s * a.x;
   R[6] = t * a.x * a.z - s * a.y; R[7] = t * a.y * a.z + s * a.x; R[8] = t * a.z * a.z + c;
 }
+__device__ __forceinline__ CV3 ccross(CV3 a, CV3 b) { return cv(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+// World frame of body bb of one robot (0 = base, 1 + 3 leg + {0, 1, 2} = hip, thigh, calf) by walking its chain from the base (<= 3
+// joints): rotation R (row-major) and origin p, from the robot's root row (pos, quat xyzw, ...) and its 12 (angle, speed) dof pairs:
+// p_b = p_parent + R_parent offset_b, R_b = R_parent Rot(axis_b, q_b).  VEL: also the world angular velocity w and the world velocity v
+// of the frame's origin, w_b = w_parent + (R_b axis_b) qd_b, v_b = v_parent + w_parent x (p_b - p_parent), from the root row's linvel /
+// angvel.  Shared by k_depth_camera (poses) and k_rigid_body_state (kernels_bodies.hpp).
+template <bool VEL>
+__device__ __forceinline__ void robot_link_walk(const mqe_robot_model& rm, const float* root13, const float* dof24, int bb, float* R, CV3& p,
+                                                CV3& w, CV3& v) {
+  cquat(root13 + 3, R);
+  p = cv(root13[0], root13[1], root13[2]);
+  if (VEL) { v = cv(root13[7], root13[8], root13[9]); w = cv(root13[10], root13[11], root13[12]); }
+  if (bb > 0) {
+    const int leg = (bb - 1) / 3, t = (bb - 1) - leg * 3;
+    for (int k = 0; k <= t; k++) {
+      const int b = 1 + leg * 3 + k;
+      const CV3 d = cmul(R, cv(rm.joint_offset[b][0], rm.joint_offset[b][1], rm.joint_offset[b][2]));
+      p = p + d;
+      if (VEL) v = v + ccross(w, d);
+      const CV3 ax = cv(rm.joint_axis[b][0], rm.joint_axis[b][1], rm.joint_axis[b][2]);
+      float Rj[9], Rn[9];
+      caxis(ax, dof24[(b - 1) * 2], Rj);
+      cmat(R, Rj, Rn);
+      for (int i = 0; i < 9; i++) R[i] = Rn[i];
+      if (VEL) w = w + dof24[(b - 1) * 2 + 1] * cmul(R, ax);
+    }
+  }
+}
 // ray o + t d (d NOT normalised: t is the depth along the optical axis), nearest t in (tmin, best) or best
 __device__ __forceinline__ float ray_sphere(CV3 o, CV3 d, CV3 c, float r, float best) {
   const CV3 oc = o - c;
@@ -97,19 +125,8 @@ __global__ void __launch_bounds__(256) k_depth_camera(const DevModel* __restrict
   if (tid < A * MQE_NBODY) {
     const int r = tid / MQE_NBODY, bb = tid - r * MQE_NBODY;
     float R[9];
-    cquat(root + r * 13 + 3, R);
-    CV3 p = cv(root[r * 13], root[r * 13 + 1], root[r * 13 + 2]);
-    if (bb > 0) {
-      const int leg = (bb - 1) / 3, t = (bb - 1) - leg * 3;
-      for (int k = 0; k <= t; k++) {
-        const int b = 1 + leg * 3 + k;
-        p = p + cmul(R, cv(rm.joint_offset[b][0], rm.joint_offset[b][1], rm.joint_offset[b][2]));
-        float Rj[9], Rn[9];
-        caxis(cv(rm.joint_axis[b][0], rm.joint_axis[b][1], rm.joint_axis[b][2]), dof[(r * 12 + b - 1) * 2], Rj);
-        cmat(R, Rj, Rn);
-        for (int i = 0; i < 9; i++) R[i] = Rn[i];
-      }
-    }
+    CV3 p, w_, v_;
+    robot_link_walk<false>(rm, root + r * 13, dof + r * 24, bb, R, p, w_, v_);
     float* L = s_link + tid * CAM_LINK;
     for (int i = 0; i < 9; i++) L[i] = R[i];
     L[9] = p.x; L[10] = p.y; L[11] = p.z;

@@ -16,6 +16,7 @@
 #include "kernels_gemm.hpp"
 #include "kernels_physics.hpp"
 #include "kernels_camera.hpp"
+#include "kernels_bodies.hpp"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, const char* a = "") {
@@ -75,6 +76,10 @@ struct mqe_sim {
   bool fuse_substeps = true;
   bool fuse_post = true;              // the post-physics step as the epilogue of k_substeps (mqe_step & co; MQE_NO_FUSE_POST=1: its own launch)
   int dbg_stop_phase = -1;            // MQE_DEBUG_STOP_PHASE, read once at creation (tools/phase_counters.py)
+  // rigid-body state tensor (kernels_bodies.hpp): derived data, not state -- allocated when first asked for, never in state_bufs
+  float* rbs = nullptr;
+  bool rbs_refresh = false;           // mqe_set_rigid_body_refresh: every post-physics step refreshes it first
+  RbsArgs rbs_args;
   // profiling
   bool prof = false, prof_now = false;   // prof_now: this call is one of the sampled ones
   int step_open = 0;                     // 0: no step in flight; 1: after mqe_step_head; 2: after mqe_step_tail / mqe_step_begin (mqe_step_end closes)
@@ -715,9 +720,32 @@ extern "C" int mqe_sim_destroy(mqe_sim* s) {
   return 0;
 }
 
+// the rigid-body state tensor's buffer and launch constants, made when the tensor, a refresh or the per-step refresh is first asked for:
+// a handle that never uses it allocates nothing and launches nothing
+static int rbs_alloc(mqe_sim* s) {
+  if (s->rbs) return 0;
+  if (s->NBR > RBS_THREADS) return fail(-4, "the rigid-body state kernel holds one env's rows in a workgroup: more than 256 reported bodies per env");
+  RbsArgs& ra = s->rbs_args;
+  memset(&ra, 0, sizeof ra);
+  ra.epg = RBS_THREADS / s->NBR;
+  const mqe_robot_model& rm = s->d.robot;
+  for (int leg = 0; leg < 4; leg++)          // foot origin = the centre of the foot's collision sphere, on the calf (go1.urdf *_foot_fixed)
+    for (int q = 0; q < rm.n_prims && q < MQE_MAX_PRIMS; q++)
+      if (rm.prim_reported[q] == 4 + 4 * leg && rm.prim_type[q] == MQE_PRIM_SPHERE && rm.prim_body[q] == 3 + 3 * leg)
+        for (int k = 0; k < 3; k++) ra.foot[leg][k] = rm.prim_center[q][k];
+  if (dalloc(s, &s->rbs, (size_t)s->N * s->NBR * 13)) return fail(-5, "device alloc failed (rigid-body state tensor)");
+  ra.out = s->rbs;
+  s->tens[MQE_T_RIGID_BODY_STATE] = s->rbs;
+  return 0;
+}
+static void launch_rbs(mqe_sim* s, hipStream_t q) {
+  hipLaunchKernelGGL(k_rigid_body_state, dim3((s->N + s->rbs_args.epg - 1) / s->rbs_args.epg), dim3(RBS_THREADS), 0, q, s->dm, s->st, s->rbs_args);
+}
+
 extern "C" int mqe_sim_tensor(mqe_sim* s, int kind, mqe_tensor_view* v) {
   if (!s || !v || kind < 0 || kind >= MQE_T_COUNT) return fail(-1, "bad tensor kind");
   memset(v, 0, sizeof *v);
+  if (kind == MQE_T_RIGID_BODY_STATE) { if (int rc = rbs_alloc(s)) return rc; }
   v->ptr = s->tens[kind];
   const int N = s->N, A = s->A, P = s->P, R = s->R;
 #define SH(nd, a, b, c, e, dt_) do { v->ndim = nd; v->shape[0] = a; v->shape[1] = b; v->shape[2] = c; v->shape[3] = e; v->dtype = dt_; } while (0)
@@ -749,6 +777,7 @@ extern "C" int mqe_sim_tensor(mqe_sim* s, int kind, mqe_tensor_view* v) {
     case MQE_T_NPC_NOISE: SH(3, N, P, 3, 0, 0); break;
     case MQE_T_WRAPPER_PACKED: SH(1, N * s->Aw * s->D + N * s->Aw + (N + 3) / 4, 0, 0, 0, 0); break;
     case MQE_T_DOMAIN_PARAMS: SH(2, s->R, 8, 0, 0, 0); break;
+    case MQE_T_RIGID_BODY_STATE: SH(3, N, s->NBR, 13, 0, 0); break;
   }
   return 0;
 }
@@ -979,6 +1008,19 @@ extern "C" int mqe_render_depth(mqe_sim* s, float* out_dev, int height, int widt
   hipLaunchKernelGGL(k_depth_camera, dim3(s->N), dim3(256), 0, (hipStream_t)stream, s->dm, s->st, ca);
   return hipGetLastError() == hipSuccess ? 0 : fail(-4, "k_depth_camera launch failed");
 }
+extern "C" int mqe_refresh_rigid_body_state(mqe_sim* s, void* stream) {
+  if (!s) return fail(-1, "null engine handle");
+  if (int rc = rbs_alloc(s)) return rc;
+  launch_rbs(s, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? 0 : fail(-4, "k_rigid_body_state launch failed");
+}
+extern "C" int mqe_set_rigid_body_refresh(mqe_sim* s, int on) {
+  if (!s) return fail(-1, "null engine handle");
+  if (s->step_open) return fail(-8, "mqe_set_rigid_body_refresh inside an open step");
+  if (on) { if (int rc = rbs_alloc(s)) return rc; }
+  s->rbs_refresh = on != 0;
+  return 0;
+}
 extern "C" int mqe_history_sync(mqe_sim* s, void* stream) {
   if (!s) return fail(-1, "null engine handle");
   if (!s->st.hist2) return 0;                    // the exact-f32 layer 0 reads the ring itself
@@ -1070,6 +1112,7 @@ extern "C" int mqe_post_decimation_step(mqe_sim* s, int dec_i, void* stream) {
 }
 extern "C" int mqe_post_physics_step(mqe_sim* s, void* stream) {
   if (!s) return fail(-1, "null engine handle");
+  if (s->rbs_refresh) launch_rbs(s, (hipStream_t)stream);
   launch_post(s, (hipStream_t)stream, 0);
   HIPCHK(hipGetLastError());
   return 0;
@@ -1080,6 +1123,7 @@ extern "C" int mqe_post_physics_stage(mqe_sim* s, int stages, void* stream) {
   hipStream_t q = (hipStream_t)stream;
   const int step_no = s->n_post_steps + 1;           // = common_step_counter after its increment (legged_robot.py:127), the same for every stage of the step
   const int push = (s->d.push_interval > 0 && step_no % s->d.push_interval == 0) ? (int)(step_no / s->d.push_interval) : 0;
+  if ((stages & MQE_POST_FRAME) && s->rbs_refresh) launch_rbs(s, q);      // after the last substep, before termination and reset
   if ((stages & MQE_POST_RESET) && s->hm.curriculum) hipLaunchKernelGGL(k_curriculum_snapshot, dim3((s->N + 255) / 256), dim3(256), 0, q, s->dm, s->st);
   hipLaunchKernelGGL(k_post_staged, dim3((s->N + 63) / 64), dim3(64), 0, q, s->dm, s->st, stages & MQE_POST_ALL, (stages & MQE_POST_WRAPPER_LEVEL) ? 1 : 0, push, step_no);
   if (stages & MQE_POST_WRAPPER) s->n_post_steps++;
@@ -1203,14 +1247,17 @@ static int run_substeps_and_post(mqe_sim* s, hipStream_t q, int wrapper_level) {
     // decimation loop in one launch: state stays in LDS; actuator net on MFMA (C) or the PD / torque law (P, V, T) inside the wavefront
     ProfScope ps(s, PROF_SIMULATE, q);
     PostArgs pa = {0, 0, 0, 0};
-    if (s->fuse_post) {                        // the post-physics step rides along as the kernel's epilogue (launch_post's bookkeeping here)
+    // with the per-step rigid-body refresh on, the refresh sits between the physics and the post-physics step: the separate
+    // post-physics launch then (the one MQE_NO_FUSE_POST selects), never the epilogue
+    const bool fuse_post = s->fuse_post && !s->rbs_refresh;
+    if (fuse_post) {                           // the post-physics step rides along as the kernel's epilogue (launch_post's bookkeeping here)
       s->n_post_steps++;
       pa.on = 1; pa.wrapper_level = wrapper_level; pa.step_no = s->n_post_steps;
       pa.push_count = (s->d.push_interval > 0 && s->n_post_steps % s->d.push_interval == 0) ? (int)(s->n_post_steps / s->d.push_interval) : 0;
     }
     hipLaunchKernelGGL(s->substeps_fn, dim3((s->N + s->substeps_epw - 1) / s->substeps_epw), dim3(64), s->phys_lds_bytes * s->substeps_epw, q, s->dm, s->st, s->d.decimation, s->lag_pos, pa);
     advance_lag(s, s->d.decimation);
-    if (s->fuse_post) {
+    if (fuse_post) {
       s->prof_now = s->prof;
       HIPCHK(hipGetLastError());
       return 0;
@@ -1223,6 +1270,7 @@ static int run_substeps_and_post(mqe_sim* s, hipStream_t q, int wrapper_level) {
       hipLaunchKernelGGL(k_post_decimation, dim3((n + 255) / 256), dim3(256), 0, q, s->dm, s->st, k < 4 ? k : 3);
     }
   }
+  if (s->rbs_refresh) launch_rbs(s, q);       // rigid-body state after the last substep, before termination and reset (legged_robot_field.py:117-119)
   launch_post(s, q, wrapper_level);
   s->prof_now = s->prof;                      // the unfused entry points are always bracketed when profiling is on
   HIPCHK(hipGetLastError());

@@ -48,7 +48,7 @@ class HipEngine(EngineBase):
                            ("debug_stop_phase", [vp, C.c_int]),
                            ("debug_wave_times", [vp, vp]), ("debug_tail_times", [vp, vp]),
                            ("debug_phase_times", [vp, vp]), ("debug_epilogue_times", [vp, vp]),
-                           ("history_sync", [vp, vp]),
+                           ("history_sync", [vp, vp]), ("refresh_rigid_body_state", [vp, vp]), ("set_rigid_body_refresh", [vp, C.c_int]),
                            ("state_save", [vp, vp, vp]), ("state_load", [vp, vp, vp]),
                            ("profile_enable", [vp, C.c_int]),
                            ("profile_read", [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)])):
@@ -168,6 +168,15 @@ class HipEngine(EngineBase):
         if rc != 0:
             raise RuntimeError(f"mqe_render_depth failed ({rc}): {self.lib.mqe_last_error().decode()}")
         return out
+
+    def refresh_rigid_body_state(self):
+        """gym.refresh_rigid_body_state_tensor: tensor(T_RIGID_BODY_STATE) from the current root and dof state (mqe_refresh_rigid_body_state)"""
+        self._call("refresh_rigid_body_state", self._stream())
+
+    def set_rigid_body_refresh(self, on):
+        """on: every post-physics step refreshes tensor(T_RIGID_BODY_STATE) first, after the physics and before termination and resets
+        (mqe_set_rigid_body_refresh); off (the default): no step touches it"""
+        self._call("set_rigid_body_refresh", int(bool(on)))
 
     def history_sync(self):
         """after writing tensor(T_HISTORY): the compact layer-0 operand is rebuilt from the ring (mqe_history_sync)"""

@@ -14,6 +14,7 @@ import torch
 
 from mqe.engine import abi
 from mqe.engine.desc import build_desc, task_kind, REWARD_TERMS
+from mqe.utils import urdf_model
 from mqe.utils.helpers import class_to_dict, engine_seed
 from mqe.utils.terrain import get_terrain_cls
 
@@ -151,6 +152,16 @@ class Go1:
             self.dof_pos_npc = self.dof_state_npc[:, :, 0]
             self.dof_vel_npc = self.dof_state_npc[:, :, 1]
         self.contact_forces = T(abi.T_CONTACT_FORCE)
+        # body index lists over one robot's reported bodies (legged_robot.py:804-813,897-907: upstream's substring rule over the asset's
+        # body names); they index the rows of contact_forces and all_rigid_body_states alike
+        body_names = urdf_model.load_model("go1")["reported_body_names"]
+        asset = self.cfg.asset
+
+        def body_indices(patterns):
+            return torch.tensor([i for p in patterns for i, b in enumerate(body_names) if p in b], dtype=torch.long, device=dev)
+        self.feet_indices = body_indices([asset.foot_name])
+        self.penalised_contact_indices = body_indices(asset.penalize_contacts_on)
+        self.termination_contact_indices = body_indices(asset.terminate_after_contacts_on)
         self.torques = T(abi.T_TORQUES)
         self.actions = T(abi.T_ACTIONS)
         self.last_actions = T(abi.T_LAST_ACTIONS)
@@ -233,6 +244,25 @@ class Go1:
         """(N*A, 13): agents' rows of the actor root-state tensor (legged_robot.py:130)."""
         r = self._root3[:, :self.num_agents, :]
         return r.reshape(-1, 13)
+
+    @property
+    def all_rigid_body_states(self):
+        """(N*NBR, 13) rigid-body state tensor (legged_robot_field.py:196-197): the rows of contact_forces in their order (robot a of an env
+        owns its rows 17a .. 17a+16: base, then FL/FR/RL/RR x hip, thigh, calf, foot; the NPC rows follow), columns as root_states (link-frame
+        origin, quaternion xyzw, linear and angular velocity, world frame).  A live view of the engine's tensor, the same object on every
+        access.  The first access switches the engine's per-step refresh on and refreshes once, as upstream refreshes in _init_buffers;
+        from then on every step refreshes it after the physics, before termination and resets (mqe_set_rigid_body_refresh)."""
+        t = getattr(self, "_rigid_body_states", None)
+        if t is None:
+            e = self.engine
+            if not hasattr(e, "refresh_rigid_body_state"):
+                raise NotImplementedError(f"all_rigid_body_states is computed by the HIP engine (mqe.engine.hip_engine.HipEngine, "
+                                          f"mqe_refresh_rigid_body_state); {type(e).__name__} has no rigid-body state tensor")
+            t = e.tensor(abi.T_RIGID_BODY_STATE).view(-1, 13)
+            e.set_rigid_body_refresh(True)
+            e.refresh_rigid_body_state()
+            self._rigid_body_states = t
+        return t
 
     @property
     def root_states_npc(self):
