@@ -81,6 +81,21 @@ def test_bench_flop_basis_matches_the_kernel_constants():
     assert (int(k.group(1)), int(k.group(2))) == (hist, frame)
 
 
+def test_engine_switches_are_one_list_and_the_documented_ones():
+    """mqe_engine.hip reads the environment in one place, from one list (SWITCH_LIST), and INTEGRATION.md's switch table names exactly
+    the switches of that list: a switch added on the side, or one that is not documented, fails here."""
+    src = open(os.path.join(ROOT, "multiagent-quadruped-environment_amd", "csrc", "mqe_engine.hip")).read()
+    assert src.count("getenv(") == 1
+    listed = re.search(r"SWITCH_LIST\[SW_COUNT\] = \{(.*?)\n\};", src, re.S).group(1)
+    in_engine = set(re.findall(r'"(MQE_[A-Z0-9_]+)"', listed))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = doc[doc.index("Environment switches read by `libmqe_hip.so`"):]
+    table = table[table.index("| variable | effect |"):].split("\n\n")[0]
+    rows = re.findall(r"^\| (`MQE_[^|]*)\|", table, re.M)                # first cell of every row; a cell may name several switches
+    in_doc = {n for cell in rows for n in re.findall(r"`(MQE_[A-Z0-9_]+)", cell)}
+    assert len(in_engine) >= 10 and in_engine == in_doc, (sorted(in_engine - in_doc), sorted(in_doc - in_engine))
+
+
 def test_bench_times_every_single_gpu_baseline_config():
     """BASELINE.json names five configs; a bench.py --full run carries the headline (configs[1]) as `value` and the other ones that fit one
     GPU -- go1sheep-hard 2048, go1seesaw 4096, go1football-defender's 4096-env shard -- as `configs[]` (VERDICT r4 "Next" 2), at the sizes named."""

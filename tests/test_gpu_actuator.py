@@ -124,7 +124,7 @@ def test_staged_kernel_against_float64(monkeypatch, capfd, task, N):
     assert not np.array_equal(taus[False], taus[True]), "MQE_ACT_F32 did not reach the engine: both forms gave the same torques"
 
 
-# the compiled k_substeps variants (mqe_engine.hip pick_shape / shape_fn): (id, task, N, switches, shape, envs per wavefront, desc tweak)
+# the compiled k_substeps variants (mqe_engine.hip pick_shape / the shape table): (id, task, N, switches, shape, envs per wavefront, desc tweak)
 def _lag(d):
     d.lag_timesteps = 6                   # the action lag of test_gpu_parity.py::test_domain_randomisation_matches_oracle
 
