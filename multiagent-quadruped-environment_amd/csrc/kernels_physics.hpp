@@ -415,9 +415,13 @@ struct PhysShape {
 // Everything below is written for "the env's lanes": `lane` is the lane WITHIN the group, `lds` the group's own state, ballots are
 // the group's bits; the few places where a wave-wide decision is needed (barriers inside loops whose trip count depends on the
 // env) say so.  The arithmetic per env is the same either way: both forms produce bit-identical states (tests/test_gpu_parity.py).
-template <int TA, int TP, int EPW = 1>
+// LATE (k_substeps): the state pointers this body uses once per launch or less -- the write-back of root / dof, the contact forces, the
+// overflow counters -- are read from the kernel arguments where they are used (mqe_common.hpp ST_LATE) instead of riding through the
+// substep loop in scalar registers; `st` is not read at all.
+template <int TA, int TP, int EPW = 1, bool LATE = false>
 __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, const DevState& st, float* lds_wave, const int e_first, const int lane_wave,
-                                             const int flags, const int no_write, const PhysDebug& dbg, const int hotv) {
+                                             const int flags, const int no_write, const PhysDebug& dbg, const int hotv,
+                                             const DevModel* mtab = nullptr) {
   static_assert(EPW == 1 || (EPW == 2 && TP == 0 && (TA == 1 || TA == 2)), "two envs per wavefront: robot-only scenes of at most two robots");
   // the model's wave-uniform constants from the table k_substeps loaded once per launch (DevModel::hot: lane i of `hotv` = entry i)
   auto HI = [&](int i) -> int { return __builtin_amdgcn_readlane(hotv, i); };
@@ -442,14 +446,21 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
   };
   const PhysShape<TA, TP> shp(m);
   const int A = shp.A, P = shp.P, PD = shp.PD, npcdof = shp.npcdof;
-  const int nbody = shp.nbody, ndof = shp.ndof, nsph = HI(HOT_NSPH_ENV), maxc = shp.maxc;
+  const int nbody = shp.nbody, ndof = shp.ndof, maxc = shp.maxc;
+  int nsph = HI(HOT_NSPH_ENV);
+  if (LATE) asm volatile("" : "+s"(nsph));          // (read here every substep: what the layout derives from it crossed the loop in a spill lane)
   constexpr int BODY_STRIDE = BODY_STRIDE_OF(PhysPad<TP>::on), CON_STRIDE = CON_STRIDE_OF(PhysPad<TP>::on);
   const PhysLds L = phys_lds_layout(A, P, shp.ND, nbody, ndof, nsph, HI(HOT_NPRIM_ENV), maxc, shp.rowgs, PhysPad<TP>::on);
   float* lds = lds_wave + grp * L.total;
   const float dt = HF(HOT_DT);
-  const mqe_robot_model& rm = m->robot;
-  float* g_root = st.root + (size_t)e * (A + P) * 13;
-  float* g_dof = st.dof + (size_t)e * shp.ND * 2;
+  // LATE: the robot model's tables through the pointer laundered once per substep (mtab) -- their bases (m + a constant beyond an instruction's
+  // immediate) are then formed where a table is read instead of crossing the substep loop in a scalar register pair each
+  // (a pointer to CONSTANT memory, which the model is for every kernel: what comes out of the asm has lost `m`'s no-alias promise, and a
+  // wave-uniform read through a plain pointer would be a vector load + v_readfirstlane instead of an s_load)
+  const DevModel* mt = LATE ? mtab : m;       // (k_substeps passes the copy it laundered at the head of this substep)
+  const mqe_robot_model& rm = mt->robot;
+  float* g_root0 = LATE ? nullptr : st.root + (size_t)e * (A + P) * 13;        // (LATE: formed where the state is loaded / stored)
+  float* g_dof0 = LATE ? nullptr : st.dof + (size_t)e * shp.ND * 2;
 
   // this lane's self-collision candidates, one per pass of 64 (requested here, consumed after the terrain contacts: the
   // table sits in global memory and a load inside the pass loop put its full latency on every pass)
@@ -465,11 +476,13 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
   TSTAMP(0);
   // ---- coalesced state load (first substep of a launch only; afterwards the state stays in LDS) -----------------
   if (flags & PS_LOAD_STATE) {
+    const float* g_root = LATE ? ST_LATE(true, st, root) + (size_t)e * (A + P) * 13 : g_root0;
+    const float* g_dof = LATE ? ST_LATE(true, st, dof) + (size_t)e * shp.ND * 2 : g_dof0;
     for (int i = lane; i < (A + P) * 13; i += LW) lds[L.root + i] = g_root[i];
     for (int i = lane; i < shp.ND * 2; i += LW) lds[L.dof + i] = g_dof[i];
   }
   if (flags & PS_LOAD_TAU)
-    for (int i = lane; i < 12 * A; i += LW) lds[L.tau + i] = st.torques[(size_t)e * 12 * A + i];
+    for (int i = lane; i < 12 * A; i += LW) lds[L.tau + i] = ST_LATE(LATE, st, torques)[(size_t)e * 12 * A + i];
   __syncthreads();
 
   TSTAMP(1);
@@ -483,10 +496,10 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
   // contact solver, so that their latency is off the critical path: added base mass and base CoM shift of this lane's robot --
   // body 0 only, inertia about the CoM unchanged (legged_robot.py:332-334, legged_robot_field.py:324-334 edit mass and com of
   // props[0] only) -- and the env's shape friction
-  const float* dp = st.dparams + ((size_t)e * A + br) * 8;
+  const float* dp = ST_LATE(LATE, st, dparams) + ((size_t)e * A + br) * 8;
   const bool dbase = is_rbody && bb == 0;
   const float dp_mass = dbase ? dp[1] : 0.0f, dp_cx = dbase ? dp[2] : 0.0f, dp_cy = dbase ? dp[3] : 0.0f, dp_cz = dbase ? dp[4] : 0.0f;
-  const float mu_env = st.dparams[(size_t)e * A * 8];
+  const float mu_env = ST_LATE(LATE, st, dparams)[(size_t)e * A * 8];
   // (no initial values for what is only read where it has been written -- Rm, bp, bw, bvp of a body lane; the joint frame of a joint lane: a
   // constant costs one v_mov per register and substep for the whole wavefront.  The base lanes do read bax / bal / bap = 0.)
   // (ADVICE r5 asked for defined values here.  Both ways of giving them one were built in round 6 and cost what the zeros cost: a frozen value
@@ -2433,14 +2446,14 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
     }
   }
   if (no_write) return;
-  if (ovf && lane == 0 && evalid) st.overflow[e] += 1;          // MQE_T_CONTACT_OVERFLOW: this substep's list was truncated
+  if (ovf && lane == 0 && evalid) ST_LATE(LATE, st, overflow)[e] += 1;          // MQE_T_CONTACT_OVERFLOW: this substep's list was truncated
   if (__ballot(red != 0 && evalid) != 0ull) {                   // MQE_T_CONTACT_REDUCED (second half of the same buffer): per env of the wavefront
-    if (gballot(red != 0) != 0ull && lane == 0 && evalid) st.overflow[HI(HOT_N) + e] += 1;
+    if (gballot(red != 0) != 0ull && lane == 0 && evalid) ST_LATE(LATE, st, overflow)[HI(HOT_N) + e] += 1;
   }
 
   // ---- net contact force per reported body (deterministic: contact order) ---------------------------------------------------
   if ((flags & PS_WRITE_CF) && evalid) {
-    float* g_cf = st.cf + (size_t)e * HI(HOT_NBR) * 3;
+    float* g_cf = ST_LATE(LATE, st, cf) + (size_t)e * HI(HOT_NBR) * 3;
     for (int rb = lane; rb < HI(HOT_NBR); rb += LW) {
       V3 F = v3(0, 0, 0);
       for (int c = 0; c < nc; c++) {
@@ -2492,6 +2505,8 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
   }
   __syncthreads();
   if ((flags & PS_STORE_STATE) && evalid) {       // coalesced write-back
+    float* g_root = LATE ? ST_LATE(true, st, root) + (size_t)e * (A + P) * 13 : g_root0;
+    float* g_dof = LATE ? ST_LATE(true, st, dof) + (size_t)e * shp.ND * 2 : g_dof0;
     for (int i = lane; i < (A + P) * 13; i += LW) g_root[i] = lds[L.root + i];
     for (int i = lane; i < shp.ND * 2; i += LW) g_dof[i] = lds[L.dof + i];
   }
@@ -2537,6 +2552,12 @@ template <int TP> struct SubstepsClass {
   static constexpr int launder = 2;       // bit 0: the model pointer, bit 1: the lane id.  (The larger scenes at 2 waves per SIMD spilled
                                           // 12-44 registers with everything hoisted; laundered they need 136-154 and none: -4 % kernel time)
 #endif
+  // How the kernel holds what is wave-uniform and invariant over the substeps (k_substeps, "No state pointer crosses ..."):
+  // late: the DevState pointers are read from the kernel arguments where they are used, and the model pointer and the env index are
+  // laundered once per substep, instead of all 52 pointers owned at entry and every address hoisted.
+  // The robot-only shapes.  (The others were built both ways: at their 128 registers the late form moved 6 to 30 vector registers to
+  // scratch -- profiles/ab_substeps_scalar_pressure.txt -- so they keep the owned pointers.)
+  static constexpr bool late = TP == 0;
 };
 // the post-physics step as this kernel's epilogue (kernels_step.hpp post_body): on = 0 leaves it to its own launch
 struct PostArgs { int on, wrapper_level, push_count, step_no; };
@@ -2547,7 +2568,7 @@ struct PostArgs { int on, wrapper_level, push_count, step_no; };
 // two-plane split-f16 operands on v_mfma_f32_32x32x16_f16 (f32-class accuracy, 22 significand bits per operand).  A compile-time choice: with
 // both forms behind a run-time branch the 128-register kernels spilled 20-50 registers.
 template <int TA, int TP, int EPW = 1, bool TIMED = false, bool ACT32 = false>
-__global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k_substeps(const DevModel* __restrict__ m, DevState st, int nsub, int lag_pos, PostArgs pa) {
+__global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k_substeps(const DevModel* __restrict__ m, DevState st_arg, int nsub, int lag_pos, PostArgs pa) {
   extern __shared__ float lds_wave[];
   // EPW = 2 (phys_substep): the two halves of the wavefront run envs 2 b and 2 b + 1; `lane` / `lds` / `e` below are the group's.
   // 2048 wavefronts for 4096 envs = 2 per SIMD with the whole register file each: nothing is laundered, everything invariant
@@ -2559,12 +2580,17 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
   constexpr int launder = EPW == 2 ? 2 : SubstepsClass<TP>::launder;     // hoisting everything overflows even 256 VGPRs (43 spilled)
 #endif
   const int lane_wave = threadIdx.x, e_first = blockIdx.x * EPW;
-  own_state(st);                                  // every pointer in a register pair of its own (mqe_common.hpp)
+  // late (SubstepsClass): no state pointer crosses the substep loop in a register -- each is read from the kernel arguments where it is
+  // used (mqe_common.hpp ST_LATE; the epilogue: late_state).  `st` is empty until then: a use of a field inside the loop would read a
+  // null pointer, not quietly bring the spills back.  k_substeps<2, 0>: 145 -> 35 spilled SGPRs, 81 -> 0 reloads inside the loop.
+  constexpr bool late = SubstepsClass<TP>::late;
+  DevState st = {};
+  if constexpr (!late) { st = st_arg; own_state(st); }      // every pointer in a register pair of its own (mqe_common.hpp)
   const int hotv = (int)m->hot[lane_wave];        // DevModel::hot: the physics' wave-uniform constants, one entry per lane, read by v_readlane
-  if (st.wave_times && lane_wave == 0) {      // MQE_WAVE_TIMES (tools/dev/wave_times.py): entry / exit time, HW_ID and XCC_ID of the wavefront
-    st.wave_times[4 * blockIdx.x] = (long long)wall_clock64();
-    st.wave_times[4 * blockIdx.x + 2] = (long long)__builtin_amdgcn_s_getreg(0xF804);
-    st.wave_times[4 * blockIdx.x + 3] = (long long)__builtin_amdgcn_s_getreg(0xF814);
+  if ((late ? st_arg.wave_times : st.wave_times) && lane_wave == 0) {      // MQE_WAVE_TIMES (tools/dev/wave_times.py): entry / exit time, HW_ID and XCC_ID of the wavefront
+    (late ? st_arg.wave_times : st.wave_times)[4 * blockIdx.x] = (long long)wall_clock64();
+    (late ? st_arg.wave_times : st.wave_times)[4 * blockIdx.x + 2] = (long long)__builtin_amdgcn_s_getreg(0xF804);
+    (late ? st_arg.wave_times : st.wave_times)[4 * blockIdx.x + 3] = (long long)__builtin_amdgcn_s_getreg(0xF814);
   }
   const int grp = EPW == 1 ? 0 : lane_wave / LW, lane = EPW == 1 ? lane_wave : lane_wave - grp * LW;
   const bool evalid = EPW == 1 || e_first + grp < m->N;
@@ -2574,7 +2600,7 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
   const PhysLds L = phys_lds_layout(A, P, shp.ND, shp.nbody, shp.ndof, m->nsph_env, m->nprim_env, shp.maxc, shp.rowgs, PhysPad<TP>::on);
   float* lds = lds_wave + grp * L.total;
   const int nj = 12 * A;
-  const int ctrl = m->control_type;
+  const int ctrl0 = m->control_type;
   const size_t R12 = (size_t)m->R * 12;
   // Nothing of the controller stays in registers across the physics body (it needs every one of the 168 a wave may hold at 3
   // waves per SIMD): the actuator history of each joint lives in LDS, the per-joint constants and the action are re-read (L1 / L2)
@@ -2582,17 +2608,20 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
   float* acth = lds + L.acth;                                    // [4][nj]: e1, e2, v1, v2
   for (int i = lane; i < 4 * nj; i += LW) {
     const int w = i / nj, jt = i - w * nj;
-    acth[i] = st.act_hist[(size_t)w * R12 + (size_t)e * nj + jt];
+    acth[i] = (late ? as_global(st_arg.act_hist) : st.act_hist)[(size_t)w * R12 + (size_t)e * nj + jt];
   }
-  float* g_root = st.root + (size_t)e * (A + P) * 13;
-  float* g_dof = st.dof + (size_t)e * shp.ND * 2;
+  const float* g_root = (late ? as_global(st_arg.root) : st.root) + (size_t)e * (A + P) * 13;
+  const float* g_dof = (late ? as_global(st_arg.dof) : st.dof) + (size_t)e * shp.ND * 2;
   for (int i = lane; i < (A + P) * 13; i += LW) lds[L.root + i] = g_root[i];
   for (int i = lane; i < shp.ND * 2; i += LW) lds[L.dof + i] = g_dof[i];
   __syncthreads();
   const PhysDebug nodbg = {nullptr, nullptr, nullptr, 0, nullptr, -1};
+  const DevModel* ma = m;                  // the loop's own copies of the model pointer and the env index, laundered once per substep (below)
+  int e_first_k = e_first;
+  int lane_run = lane_wave;
 #pragma clang loop unroll(disable)
-  for (int k = 0; k < nsub; k++) {
-    const bool last = k + 1 == nsub;
+  for (int k = 0; k < LATE_ARG(late, nsub, 0); k++) {             // (the two integer arguments too: read where they are used)
+    const bool last = k + 1 == LATE_ARG(late, nsub, 0);
     // Wave priority by progress.  At equal priority the SIMD's arbiter prefers its oldest wave: the four waves of a SIMD then finish
     // one after the other (lifetimes 81 .. 131 us measured) and the last one runs alone, with nobody to hide its latencies.  A wave
     // that is a substep behind goes first instead, so the four stay abreast and finish together: go1gate 136.6 -> 120.5 us.
@@ -2613,42 +2642,59 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
     }
 #endif
     const DevModel* mk = m;
-    int lane_k = lane_wave;
     if (launder & 1) asm volatile("" : "+s"(mk));
+    // The lane id is laundered IN PLACE where the kernel owns its pointers (!late): one copy of it lives across the substep, not the
+    // original for the next substep and the epilogue beside this substep's copy.  That register is what k_substeps<2, PS_F_LINK> and
+    // <2, PS_F_STATIC | PS_F_FEW> lacked (2 VGPRs in scratch before).  The late kernels have it to spare and keep the fresh copy per
+    // substep: in place, their epilogue spilled 19 more SGPRs and one reload came back into the loop.
+    if (late) lane_run = lane_wave;
     if (launder & 2) {
-      asm volatile("" : "+v"(lane_k));
-      lane_k &= 63;                                  // gives the value range of threadIdx.x back to the optimiser
+      asm volatile("" : "+v"(lane_run));
+      lane_run &= 63;                                // gives the value range of threadIdx.x back to the optimiser
     }
+    const int lane_k = lane_run;
+    // What the loop body forms from the model pointer and the env index alone -- table bases m + constant beyond the 4 KiB an instruction's
+    // immediate reaches, pointers loaded from the model plus an offset, the env's rows pointer + e * stride -- is wave-uniform and invariant,
+    // so the optimiser forms each of them once, in front of the loop, as a 64-bit scalar sum: more register pairs than a wavefront has,
+    // and the ones that did not fit came back as a v_readlane per use.  Laundered copies of the two roots keep those sums where they are
+    // used (two scalar instructions each, no vector one).  `ma` serves the controller and the logs only: the physics body keeps its
+    // hoisted constants (mk).  It points to CONSTANT memory, which the model is: reads through it stay scalar loads (phys_substep, `mt`).
+    if constexpr (late) {
+      ma = launder_const(ma);
+      asm volatile("" : "+s"(e_first_k));
+    }
+    const int e_k = EPW == 1 ? e_first_k : e;
     const int glane_k = EPW == 1 ? lane_k : lane_k - (lane_k / LW) * LW;        // lane within the env's group
     const int j32 = lane_k & 31, h = lane_k >> 5;
+    const int ctrl = late ? ma->control_type : ctrl0;
     if (ctrl != MQE_CTRL_C) {          // P / V / T (legged_robot.py:384-390): a few FMAs per joint lane instead of the actuator network
       for (int jt = glane_k; jt < nj; jt += LW) {
-        const size_t gi = (size_t)e * nj + jt;
+        const size_t gi = (size_t)e_k * nj + jt;
         const int j = jt % 12;
-        const float asc = st.actions[gi] * m->action_scale;          // no hip reduction (legged_robot.py:380)
-        const float q = lds[L.dof + jt * 2], qd = lds[L.dof + jt * 2 + 1], lim = m->torque_limits[j];
+        const float asc = ST_LATE(late, st, actions)[gi] * ma->action_scale;          // no hip reduction (legged_robot.py:380)
+        const float q = lds[L.dof + jt * 2], qd = lds[L.dof + jt * 2 + 1], lim = ma->torque_limits[j];
         float tau = asc;
-        if (ctrl == MQE_CTRL_P) tau = m->kp * (asc + m->default_dof_pos[j] - q) - m->kd * qd;
-        else if (ctrl == MQE_CTRL_V) tau = m->kp * (asc - qd) - m->kd * (qd - st.last_dof_vel[gi]) / m->dt;
+        if (ctrl == MQE_CTRL_P) tau = ma->kp * (asc + ma->default_dof_pos[j] - q) - ma->kd * qd;
+        else if (ctrl == MQE_CTRL_V) tau = ma->kp * (asc - qd) - ma->kd * (qd - ST_LATE(late, st, last_dof_vel)[gi]) / ma->dt;
         tau = clampf(tau, -lim, lim);
         lds[L.tau + jt] = tau;
         if (evalid) {
-          st.sub_tau[((size_t)e * 4 + (k < 4 ? k : 3)) * nj + jt] = tau;
-          if (last) st.torques[gi] = tau;
+          ST_LATE(late, st, sub_tau)[((size_t)e_k * 4 + (k < 4 ? k : 3)) * nj + jt] = tau;
+          if (last) ST_LATE(late, st, torques)[gi] = tau;
         }
       }
     } else {                           // control type C: actuator network (one call site of the physics body below: it is
                                        // inlined, and two copies of its ~9 k instructions would not fit the instruction cache)
       // weight fragments (A operands): row = hidden unit j32, k = this half-wave's element of each k pair; re-read every substep
       // (L1/L2 resident, 5 kB shared by every wave)
-      const float* b0 = as_global(mk->actuator.b[0]);      // through the laundered pointer: the 70 fragment
-      const float* b1 = as_global(mk->actuator.b[1]);      // loads below stay inside the substep loop (global_load, not flat_load:
-      const float* W2 = as_global(mk->actuator.W[2]); const float* b2 = as_global(mk->actuator.b[2]);     // mqe_common.hpp as_global)
+      const float* b0 = as_global(ma->actuator.b[0]);      // through the laundered pointer: the 70 fragment
+      const float* b1 = as_global(ma->actuator.b[1]);      // loads below stay inside the substep loop (global_load, not flat_load:
+      const float* W2 = as_global(ma->actuator.W[2]); const float* b2 = as_global(ma->actuator.b[2]);     // mqe_common.hpp as_global)
       constexpr bool act16 = !ACT32;
       float a1[3], a2[16], w3[16], bb0[16], bb1[16];
       // (the two matrix operands from the fragment-ordered copy: lane-contiguous, one 256 B request per fragment -- W1[j32 * 32 + u] itself
       // is 64 lanes x a 128 B stride, 64 cache lines per instruction, 16 instructions per substep and wavefront)
-      const float* fragw = as_global(mk->act_frag) + lane_k;
+      const float* fragw = as_global(ma->act_frag) + lane_k;
 #pragma unroll
       for (int s2 = 0; s2 < 3; s2++) a1[s2] = fragw[(16 + s2) * 64];
 #pragma unroll
@@ -2668,7 +2714,7 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
       // the fragment order of v_mfma_f32_32x32x16_f16 -- [k-step][plane][lane][8] -- one 16 B load per fragment
       // (the four fragments live in the sixteen registers the f32 chain keeps its layer-2 operand in: one set of registers for both forms)
       if constexpr (act16) {
-        const h2_gvec* f16w = (const h2_gvec*)(unsigned long long)mk->act_frag16 + lane_k;
+        const h2_gvec* f16w = (const h2_gvec*)(unsigned long long)ma->act_frag16 + lane_k;
 #pragma unroll
         for (int f = 0; f < 4; f++) {
           const h2_u32x4 t = f16w[f * 64];
@@ -2676,9 +2722,9 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
         }
       }
       int pos = 0;
-      if (m->lag_steps > 0) {          // go1.py:337-339: the lag buffer shifts in every _compute_torques call, i.e. per substep
-        const int n = m->lag_steps + 1;
-        pos = lag_pos + k; pos -= (pos / n) * n;
+      if (ma->lag_steps > 0) {          // go1.py:337-339: the lag buffer shifts in every _compute_torques call, i.e. per substep
+        const int n = ma->lag_steps + 1;
+        pos = LATE_ARG(late, lag_pos, 4) + k; pos -= (pos / n) * n;
       }
       // the network's columns are the joints of the WAVEFRONT: 12 A per env, the envs of the wavefront one after the other (EPW = 2:
       // 48 joints in two tiles of 32); a column's lanes read and write the LDS state of the env the joint belongs to
@@ -2691,8 +2737,8 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
         const int jwc = ok ? jw : 0;
         const int ge = EPW == 1 ? 0 : jwc / nj;            // env of the wavefront this column belongs to
         const int jt = jwc - ge * nj, jc = jt, j = jc % 12;
-        const bool ev = EPW == 1 || e_first + ge < m->N;
-        const int eg = ev ? e_first + ge : m->N - 1;
+        const bool ev = EPW == 1 || e_first_k + ge < ma->N;
+        const int eg = ev ? e_first_k + ge : ma->N - 1;
         float* ldsg = lds_wave + ge * L.total;
         float* acthg = ldsg + L.acth;
         const size_t gi = (size_t)eg * nj + jc;
@@ -2700,18 +2746,18 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
         // with actuator lag -- the ring's oldest slot, which this substep's write (into ANOTHER slot: the ring has lag_steps + 1 >= 2) does
         // not change.  One after the other behind `if (lag && ok)` they were three memory round trips per substep that no other
         // wavefront hides: the four of a SIMD reach this phase together.
-        const bool lagged = m->lag_steps > 0;                        // wave-uniform
-        const float a_raw = st.actions[gi], ddp = m->default_dof_pos[j], lim = m->torque_limits[j];
+        const bool lagged = ma->lag_steps > 0;                        // wave-uniform
+        const float a_raw = ST_LATE(late, st, actions)[gi], ddp = ma->default_dof_pos[j], lim = ma->torque_limits[j];
         float lag_old = 0.0f;
         size_t lag_wr = 0;
         if (lagged) {                                                // go1.py:337-339 (kernels_step.hpp lag_target: the same ring)
-          const size_t R12l = (size_t)m->R * 12;
-          const int rd = pos + 1 >= m->lag_steps + 1 ? 0 : pos + 1;
-          lag_old = st.lag_buf[(size_t)rd * R12l + gi];
+          const size_t R12l = (size_t)ma->R * 12;
+          const int rd = pos + 1 >= ma->lag_steps + 1 ? 0 : pos + 1;
+          lag_old = ST_LATE(late, st, lag_buf)[(size_t)rd * R12l + gi];
           lag_wr = (size_t)pos * R12l + gi;
         }
-        float as = a_raw * m->action_scale;
-        if (j % 3 == 0) as *= m->hip_scale_reduction;
+        float as = a_raw * ma->action_scale;
+        if (j % 3 == 0) as *= ma->hip_scale_reduction;
         float tgt = as + ddp;
         if (lagged && ok) tgt = lag_old + ddp;                    // (this substep's slot is written with the torque below: no store in front of a wait)
         const float q = ldsg[L.dof + jc * 2], qd = ldsg[L.dof + jc * 2 + 1];
@@ -2744,42 +2790,49 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
           acthg[nj + jt] = he1; acthg[jt] = err; acthg[3 * nj + jt] = hv1; acthg[2 * nj + jt] = qd;      // go1.py:347-350
           ldsg[L.tau + jt] = tau;
           if (ev) {
-            st.sub_tau[((size_t)eg * 4 + (k < 4 ? k : 3)) * nj + jt] = tau;          // post_decimation_step (legged_robot.py:113)
-            if (last) st.torques[gi] = tau;
-            if (lagged) st.lag_buf[lag_wr] = as;
+            ST_LATE(late, st, sub_tau)[((size_t)eg * 4 + (k < 4 ? k : 3)) * nj + jt] = tau;          // post_decimation_step (legged_robot.py:113)
+            if (last) ST_LATE(late, st, torques)[gi] = tau;
+            if (lagged) ST_LATE(late, st, lag_buf)[lag_wr] = as;
           }
         }
       }
     }
     __syncthreads();
     if constexpr (TIMED) {
-      long long* tt = st.wave_times + 4 * (size_t)gridDim.x + ((size_t)blockIdx.x * 4 + (k < 4 ? k : 3)) * 16;
+      long long* tt = ST_LATE(late, st, wave_times) + 4 * (size_t)gridDim.x + ((size_t)blockIdx.x * 4 + (k < 4 ? k : 3)) * 16;
       const PhysDebug tdbg = {nullptr, nullptr, nullptr, 0, tt, -1};
-      phys_substep<TA, TP, EPW>(mk, st, lds_wave, e_first, lane_k, last ? (PS_STORE_STATE | PS_WRITE_CF) : 0, 0, tdbg, hotv);
+      phys_substep<TA, TP, EPW, late>(mk, st, lds_wave, e_first_k, lane_k, last ? (PS_STORE_STATE | PS_WRITE_CF) : 0, 0, tdbg, hotv, ma);
       if (lane_wave == 0) tt[15] = (long long)wall_clock64();
     } else
-    phys_substep<TA, TP, EPW>(mk, st, lds_wave, e_first, lane_k, last ? (PS_STORE_STATE | PS_WRITE_CF) : 0, 0, nodbg, hotv);
+    phys_substep<TA, TP, EPW, late>(mk, st, lds_wave, e_first_k, lane_k, last ? (PS_STORE_STATE | PS_WRITE_CF) : 0, 0, nodbg, hotv, ma);
     // post_decimation_step (legged_robot.py:114-115): joint velocities and soft-limit flags after this substep, from the LDS state
     if (evalid)
       for (int jt = glane_k; jt < nj; jt += LW) {
         const float q = lds[L.dof + jt * 2], qd = lds[L.dof + jt * 2 + 1];
         const int j = jt % 12;
-        const size_t o = ((size_t)e * 4 + (k < 4 ? k : 3)) * nj + jt;
-        st.sub_dof_vel[o] = qd;
-        st.sub_exceed[o] = (uint8_t)((q < m->soft_lo[j]) | (q > m->soft_hi[j]));
+        const size_t o = ((size_t)e_k * 4 + (k < 4 ? k : 3)) * nj + jt;
+        ST_LATE(late, st, sub_dof_vel)[o] = qd;
+        ST_LATE(late, st, sub_exceed)[o] = (uint8_t)((q < ma->soft_lo[j]) | (q > ma->soft_hi[j]));
       }
   }
   __syncthreads();
+  const int lane_post = late ? lane_wave : lane_run;      // (the same value either way)
+  const int lane_pg = EPW == 1 ? lane_post : lane_post - (lane_post / LW) * LW;
+  if constexpr (late) {
+    st = late_state();                            // from here on every pointer, owned (the epilogue's are spilled, if at all, inside the epilogue)
+    asm volatile("" : "+s"(e_first_k));           // (nothing formed from the env index in front of the loop is kept for this)
+  }
+  const int e_post = EPW == 1 ? e_first_k : e;
   if (evalid)
-    for (int i = lane; i < 4 * nj; i += LW) {
+    for (int i = lane_pg; i < 4 * nj; i += LW) {
       const int w = i / nj, jt = i - w * nj;
-      st.act_hist[(size_t)w * R12 + (size_t)e * nj + jt] = acth[i];
+      st.act_hist[(size_t)w * R12 + (size_t)e_post * nj + jt] = acth[i];
     }
   if constexpr (ShapeClass<TP>::small || TP > 0) if (pa.on) {      // (every kernel of the 16-envs-per-CU class; with the DevState pointers in register pairs of their own none of them spills)
     // ---- post_physics_step of this wavefront's env(s) (legged_robot.py:117-157 + the task wrapper), from the state just written: the
     // writer and the readers are lanes of this one wavefront (one CU, one vector L1), a workgroup-scope fence orders them
     long long* et = nullptr;
-    if constexpr (TIMED) { et = st.wave_times + 68 * (size_t)gridDim.x + (size_t)blockIdx.x * 16; if (lane_wave == 0) et[0] = (long long)wall_clock64(); }
+    if constexpr (TIMED) { et = st.wave_times + 68 * (size_t)gridDim.x + (size_t)blockIdx.x * 16; if (lane_post == 0) et[0] = (long long)wall_clock64(); }
     __threadfence_block();
     __syncthreads();
     constexpr int AMP = (TA == 1 || TA == 2) ? 2 : MQE_MAX_AGENTS;
@@ -2790,15 +2843,15 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
     // checks the actual layout against the same formula and keeps the separate launch when it does not fit
     float* sb = lds_wave + L.body;
     float* act_l = sb + EPW * AMP * (MQE_OBS_BAG + 24) + EPW * post_npc_stride(P);
-    for (int i = lane_wave; i < EPW * nj; i += 64) {          // the wavefront's actions, one coalesced load
+    for (int i = lane_post; i < EPW * nj; i += 64) {          // the wavefront's actions, one coalesced load
       const int ge = i / nj, jt = i - ge * nj;
       if (e_first + ge < m->N) act_l[ge * nj + jt] = st.actions[(size_t)(e_first + ge) * nj + jt];
     }
     __syncthreads();
-    if constexpr (TIMED) { if (lane_wave == 0) et[1] = (long long)wall_clock64(); }
-    post_body<AMP, EPW, true>(m, st, (int)blockIdx.x, lane_wave, sb, sb + EPW * AMP * MQE_OBS_BAG, sb + EPW * AMP * (MQE_OBS_BAG + 24), pa.wrapper_level, pa.push_count, pa.step_no,
+    if constexpr (TIMED) { if (lane_post == 0) et[1] = (long long)wall_clock64(); }
+    post_body<AMP, EPW, true>(m, st, (int)blockIdx.x, lane_post, sb, sb + EPW * AMP * MQE_OBS_BAG, sb + EPW * AMP * (MQE_OBS_BAG + 24), pa.wrapper_level, pa.push_count, pa.step_no,
                         lds_wave + L.root, lds_wave + L.dof, act_l, L.total, nj, post_npc_stride(P), et);
-    if constexpr (TIMED) { if (lane_wave == 0) et[10] = (long long)wall_clock64(); }
+    if constexpr (TIMED) { if (lane_post == 0) et[10] = (long long)wall_clock64(); }
   }
-  if (st.wave_times && lane_wave == 0) st.wave_times[4 * blockIdx.x + 1] = (long long)wall_clock64();
+  if (st.wave_times && lane_post == 0) st.wave_times[4 * blockIdx.x + 1] = (long long)wall_clock64();
 }

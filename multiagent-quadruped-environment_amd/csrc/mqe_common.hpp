@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <stddef.h>
+#include <type_traits>
 
 #include "../../include/mqe_hip.h"
 
@@ -131,6 +133,48 @@ __device__ __forceinline__ void own_state(DevState& st) {
   own_global(st.hist2); own_global(st.wave_times); own_global(st.hist_irr); own_global(st.ep_len); own_global(st.reset_count); own_global(st.reset_buf);
   own_global(st.collide_buf); own_global(st.time_out); own_global(st.r_term); own_global(st.p_term); own_global(st.zh_term); own_global(st.w_have_last);
   own_global(st.w_delayed_reset); own_global(st.npc_pre); own_global(st.env_origins_live); own_global(st.curr_xy); own_global(st.terrain_levels); own_global(st.wdone);
+}
+
+// The same pointer, cut off from what the optimiser knows about it, so that nothing derived from it is formed ahead of this point -- but
+// still a pointer to CONSTANT memory (what a model or weight table is to every kernel): the address-space inference carries that to
+// every access, and a wave-uniform read stays an s_load.  (Out of a plain "+s" asm comes a pointer that may alias the kernel's stores:
+// uniform reads through it are vector loads + v_readfirstlane.)
+#define MQE_AS4 __attribute__((address_space(4)))
+template <class T> __device__ __forceinline__ const T* launder_const(const T* p) {
+  const MQE_AS4 T* c = (const MQE_AS4 T*)p;
+  asm volatile("" : "+s"(c));
+  return (const T*)c;
+}
+// 52 owned pointers are 104 scalar registers, more than the ~100 a wavefront has: k_substeps spilled 45 of them into VGPR lanes at entry
+// and paid a v_readlane (a vector issue slot, and hazard s_nops in front of the scalar consumer) at every later use.  The kernel
+// arguments stay readable for the whole launch, so a pointer that is used once per launch (the state's write-back, the actuator
+// history, everything the epilogue touches) is read from the kernel-argument segment WHERE it is used: an s_load, no vector
+// instruction, and no register across the substep loop.  The empty asm is what keeps the load there (without it the optimiser
+// reads every argument at kernel entry).  MQE_KARG_STATE: offset of the DevState argument of k_substeps(const DevModel*, DevState, ...).
+#define MQE_KARG_STATE 8
+__device__ __forceinline__ const MQE_AS4 char* kernarg_here() {
+  const MQE_AS4 char* ka = (const MQE_AS4 char*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(ka));
+  return ka;
+}
+template <class T> __device__ __forceinline__ T* late_global(size_t kernarg_off) {
+  const unsigned long long u = *(const MQE_AS4 unsigned long long*)(kernarg_here() + kernarg_off);
+  return (T*)(__attribute__((address_space(1))) T*)u;
+}
+// st.field as it stands in the kernel arguments (k_substeps only), or st.field itself (late = false: every other kernel)
+#define ST_LATE(late, st, field) ((late) ? late_global<typename std::remove_pointer<decltype(DevState::field)>::type>(MQE_KARG_STATE + offsetof(DevState, field)) : (st).field)
+// ... and an integer argument behind the state (byte offset `off` from its end): k_substeps(..., int nsub, int lag_pos, ...)
+#define LATE_ARG(late, arg, off) ((late) ? *(const MQE_AS4 int*)(kernarg_here() + MQE_KARG_STATE + sizeof(DevState) + (off)) : (arg))
+// the whole state once more, for the epilogue: read after the last substep, every pointer owned there
+__device__ __forceinline__ DevState late_state() {
+  const MQE_AS4 unsigned long long* a = (const MQE_AS4 unsigned long long*)(kernarg_here() + MQE_KARG_STATE);
+  unsigned long long w[sizeof(DevState) / 8];
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(DevState) / 8); i++) w[i] = a[i];
+  DevState s;
+  __builtin_memcpy(&s, w, sizeof s);
+  own_state(s);
+  return s;
 }
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
