@@ -448,29 +448,124 @@ __global__ void __launch_bounds__(256) k_compute_torques_mfma(const DevModel* m,
 
 // ----------------------------------------------------------------------------------------------------------------
 // post_physics_step (legged_robot.py:117-157, legged_robot_field.py:117-146, go1.py:153-279,110-145, go1_sheep.py:35-64)
-// One thread per env (a few hundred flops each; ~10 kB/env of traffic only when the env resets).
+// Three drivers run it: post_body (a robot per lane; the epilogue of k_substeps and the stand-alone k_post_physics) and k_post_staged (a
+// thread per env, in the reference's five stages).  The formulas of the step are the functions below, stated once and inlined into every
+// driver; their array arguments are the caller's registers or rows of the tensors.
+
+// One robot's body-frame velocities and projected gravity, gait clock (go1.py:240-279) and termination tests from its root row rs[13], gait
+// parameters gpar[5] (loco_obs 7..11), gait index gi0, base contact force f3 and agent origin z.  Returns the termination bits: 0 base
+// contact, 1 roll, 2 pitch, 3 z high, 4 z low.  rpy: the Euler angles of the row's quaternion, the observation's too (~170 instructions).
+__device__ __forceinline__ unsigned robot_frame(const DevModel* m, const float* rs, const float* gpar, float gi0, const float* f3, float aoz, float dtp,
+                                                float* lv, float* av, float* pgr, float* clk, float& gi1, float* rpy) {
+  const float q[4] = {rs[3], rs[4], rs[5], rs[6]}, v[3] = {rs[7], rs[8], rs[9]}, w[3] = {rs[10], rs[11], rs[12]};
+  const float g3[3] = {0.0f, 0.0f, -1.0f};
+  quat_rotate_inverse_f(q, v, lv);
+  quat_rotate_inverse_f(q, w, av);
+  quat_rotate_inverse_f(q, g3, pgr);
+  const float f = gpar[0], ph = gpar[1], off = gpar[2], bnd = gpar[3], dur = gpar[4];
+  float gi = gi0 + dtp * f;
+  gi = gi - floorf(gi);
+  gi1 = gi;
+  float fi[4] = {gi + ph + off + bnd, gi + off, gi + bnd, gi + ph};
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const float r = fi[k] - floorf(fi[k]);
+    if (r < dur) fi[k] = r * (0.5f / dur);
+    else if (r > dur) fi[k] = 0.5f + (r - dur) * (0.5f / (1.0f - dur));       // (r == dur: neither, as upstream)
+    clk[k] = sinf(6.2831855f * fi[k]);
+  }
+  unsigned fl = 0;
+  if (m->terminate_on_base_contact && sqrtf(f3[0] * f3[0] + f3[1] * f3[1] + f3[2] * f3[2]) > 1.0f) fl |= 1u;
+  euler_xyz_f(q, rpy);
+  float r = rpy[0], p = rpy[1];
+  if (r > 3.1415927f) r -= 6.2831855f;
+  if (p > 3.1415927f) p -= 6.2831855f;
+  const float z = rs[2] - aoz;
+  if ((m->termination_flags & MQE_TERM_ROLL) && fabsf(r) > m->roll_thr) fl |= 2u;
+  if ((m->termination_flags & MQE_TERM_PITCH) && fabsf(p) > m->pitch_thr) fl |= 4u;
+  if ((m->termination_flags & MQE_TERM_Z_HIGH) && z > m->zhigh_thr) fl |= 8u;
+  if ((m->termination_flags & MQE_TERM_Z_LOW) && z < m->zlow_thr) fl |= 16u;
+  return fl;
+}
+// the env's flags: fl = the OR of its robots' termination bits, to = time-out, reset = any of them
+__device__ __forceinline__ void env_flags_store(const DevModel* m, const DevState& st, int e, int ep, unsigned fl, uint8_t to, uint8_t reset) {
+  st.ep_len[e] = ep;
+  st.time_out[e] = to;
+  if (m->termination_flags & MQE_TERM_ROLL) st.r_term[e] = (fl >> 1) & 1;
+  if (m->termination_flags & MQE_TERM_PITCH) st.p_term[e] = (fl >> 2) & 1;
+  if (m->termination_flags & MQE_TERM_Z_HIGH) st.zh_term[e] = (fl >> 3) & 1;
+  st.reset_buf[e] = reset;
+  st.wdone[e] = reset;                          // the flag once more, in the packed return batch (byte tail: a torch.bool view, no kernel)
+  if (m->terminate_on_base_contact) st.collide_buf[e] = reset;
+}
+__device__ __forceinline__ void robot_frame_store(const DevState& st, int i, const float* lv, const float* av, const float* pgr, const float* bq, const float* clk, float gi) {
+#pragma unroll
+  for (int k = 0; k < 3; k++) { st.blv[i * 3 + k] = lv[k]; st.bav[i * 3 + k] = av[k]; st.pg[i * 3 + k] = pgr[k]; }
+#pragma unroll
+  for (int k = 0; k < 4; k++) { st.bquat[i * 4 + k] = bq[k]; st.clock[i * 4 + k] = clk[k]; }
+  st.gait[i] = gi;
+}
+// _push_robots (go1.py:237, legged_robot.py:470-476): after this step's frame quantities were taken, before reset_idx -- whose
+// U(-0.5, 0.5) base velocities replace the push in the envs that reset, so the callers skip those.  One draw per robot (the reference
+// draws (num_envs, 2) for a (num_envs * num_agents, 2) slice, which only broadcasts for a single agent).
+__device__ __forceinline__ void push_robots(const DevModel* m, float* root, int e, int A, int push_count) {
+  for (int b = 0; b < A; b++) {
+    float* rv = root + b * 13 + 7;
+    rv[0] = mqe_rand(m, e, (int)(MQE_RNG_PUSH + (uint32_t)push_count), (uint32_t)(2 * b), -m->max_push, m->max_push);
+    rv[1] = mqe_rand(m, e, (int)(MQE_RNG_PUSH + (uint32_t)push_count), (uint32_t)(2 * b + 1), -m->max_push, m->max_push);
+  }
+}
+// compute_observations (legged_robot_field.py:117-146): entries 0..70 of one robot's MQE_OBS_BAG row `ob`, in three pieces with scalar
+// arguments -- per axis, per joint, per clock / quaternion component -- which the caller runs over k < 3, j < 12, k < 4.  Not one function
+// over the arrays: handed over as pointers, post_body's register arrays stay memory until the inliner has run, and k_substeps' substep
+// loop then comes out with other constants hoisted and other registers.  last_act: obs.last_last_action -- in a step a view of the
+// current action (see oracle).
+__device__ __forceinline__ void obs_row_axis(float* ob, int k, float pos, float origin, float rpy, float lv, float av, float pg) {
+  ob[k] = pos - origin; ob[3 + k] = rpy;
+  ob[30 + k] = lv * 2.0f; ob[33 + k] = av * 0.25f; ob[60 + k] = pg;
+}
+__device__ __forceinline__ void obs_row_joint(const DevModel* m, float* ob, int j, float q, float qd, float act, float last_act) {
+  ob[6 + j] = (q - m->default_dof_pos[j]) * 1.0f;
+  ob[18 + j] = qd * 0.05f;
+  ob[36 + j] = act;
+  ob[48 + j] = last_act;
+}
+__device__ __forceinline__ void obs_row_quad(float* ob, int k, float clk, float bq) { ob[63 + k] = clk; ob[67 + k] = bq; }
+// go1.py:145: history[agent_ids] = 0 for an env that resets: its robots' f32 ring and, when present, the two f16 planes (both contiguous
+// over the env's robots) and the continuity bits (all frames zero: every frame continues its predecessor).  By `stride` threads, of which
+// this is thread t < stride: 16 B per request, and the bits of robots t, t + stride, .. of the at most MQE_MAX_AGENTS.
+constexpr int HIST_F4 = MQE_HIST * MQE_FRAME / 4;            // one robot's ring in float4 units
+constexpr int HIST2_U4 = 2 * MQE_HIST * MQE_H2_FRAME / 8;    // its two f16 planes in uint4 units (8 values each)
+__device__ __forceinline__ void zero_env_history(const DevModel* m, const DevState& st, int e, int t, int stride) {
+  const int per = m->A * HIST_F4;
+  float4* h4 = reinterpret_cast<float4*>(st.hist) + (size_t)e * per;
+  for (int k = t; k < per; k += stride) h4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (st.hist2) {
+    uint4* p4 = reinterpret_cast<uint4*>(st.hist2 + (size_t)e * m->A * (HIST2_U4 * 8));
+    const int per2 = m->A * HIST2_U4;
+    for (int k = t; k < per2; k += stride) p4[k] = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+    for (int a0 = 0; a0 < MQE_MAX_AGENTS; a0 += stride)
+      if (t + a0 < m->A) st.hist_irr[(size_t)e * m->A + t + a0] = 0u;
+  }
+}
+
+// the env's observation rows from the tensors (one thread per env); the Euler angles are those of st.bquat
 __device__ __forceinline__ void compute_observations_env(const DevModel* m, const DevState& st, int e, int in_step) {
   int A = m->A;
   for (int a = 0; a < A; a++) {
     int i = e * A + a;
     float* ob = st.obs_bag + (size_t)i * MQE_OBS_BAG;
     const float* rs = st.root + ((size_t)e * (A + m->P) + a) * 13;
-    for (int k = 0; k < 3; k++) ob[k] = rs[k] - as_global(m->env_origins)[e * 3 + k];
-    euler_xyz_f(st.bquat + i * 4, ob + 3);
+    const float* ds = st.dof + ((size_t)e * m->ND + a * 12) * 2;
+    float rpy[3];
+    euler_xyz_f(st.bquat + i * 4, rpy);
+    for (int k = 0; k < 3; k++) obs_row_axis(ob, k, rs[k], as_global(m->env_origins)[e * 3 + k], rpy[k], st.blv[i * 3 + k], st.bav[i * 3 + k], st.pg[i * 3 + k]);
     for (int j = 0; j < 12; j++) {
-      const float* ds = st.dof + ((size_t)e * m->ND + a * 12 + j) * 2;
-      ob[6 + j] = (ds[0] - m->default_dof_pos[j]) * 1.0f;
-      ob[18 + j] = ds[1] * 0.05f;
       float act = st.actions[i * 12 + j];
-      ob[36 + j] = act;
-      ob[48 + j] = in_step ? act : st.last_actions[i * 12 + j];    // view aliasing, see oracle
+      obs_row_joint(m, ob, j, ds[2 * j], ds[2 * j + 1], act, in_step ? act : st.last_actions[i * 12 + j]);
     }
-    for (int k = 0; k < 3; k++) {
-      ob[30 + k] = st.blv[i * 3 + k] * 2.0f;
-      ob[33 + k] = st.bav[i * 3 + k] * 0.25f;
-      ob[60 + k] = st.pg[i * 3 + k];
-    }
-    for (int k = 0; k < 4; k++) { ob[63 + k] = st.clock[i * 4 + k]; ob[67 + k] = st.bquat[i * 4 + k]; }
+    for (int k = 0; k < 4; k++) obs_row_quad(ob, k, st.clock[i * 4 + k], st.bquat[i * 4 + k]);
   }
 }
 
@@ -535,7 +630,7 @@ __device__ __forceinline__ void reset_env_dev(const DevModel* m, const DevState&
   st.reset_buf[e] = 1;
   st.wdone[e] = 1;
   for (int a = 0; a < A; a++) st.gait[e * A + a] = 0.0f;
-  // history zeroing (go1.py:145) is done by k_reset_history, 16 B per thread
+  // history zeroing (go1.py:145) is the caller's: zero_env_history in a step, k_reset_history behind k_reset_all (mqe_reset_all)
   st.reset_count[e] = cnt + 1;
 }
 
@@ -1012,63 +1107,22 @@ __device__ __forceinline__ void post_body(const DevModel* m, const DevState& st,
   }
   // ---- body-frame quantities, gait clock, termination (registers only) ------------------------------------------------------
   float bq[4], lv[3], av[3], pgr[3], clk[4], gi1 = 0.f;
-  float rpy[3] = {0.f, 0.f, 0.f};               // Euler angles of bq: the termination test's and the observation's (one evaluation: ~170 instructions a second one costs)
-  unsigned fl = 0;                              // bit 0 base contact, 1 roll, 2 pitch, 3 z high, 4 z low
+  float rpy[3] = {0.f, 0.f, 0.f};               // Euler angles of bq: the termination test's and the observation's
+  unsigned fl = 0;
   if (mine) {
-    const float q[4] = {rs[3], rs[4], rs[5], rs[6]}, v[3] = {rs[7], rs[8], rs[9]}, w[3] = {rs[10], rs[11], rs[12]};
-    const float g3[3] = {0.0f, 0.0f, -1.0f};
 #pragma unroll
-    for (int k = 0; k < 4; k++) bq[k] = q[k];
-    quat_rotate_inverse_f(q, v, lv);
-    quat_rotate_inverse_f(q, w, av);
-    quat_rotate_inverse_f(q, g3, pgr);
-    const float f = gpar[0], ph = gpar[1], off = gpar[2], bnd = gpar[3], dur = gpar[4];
-    float gi = gi0 + dtp * f;
-    gi = gi - floorf(gi);
-    gi1 = gi;
-    float fi[4] = {gi + ph + off + bnd, gi + off, gi + bnd, gi + ph};
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const float r = fi[k] - floorf(fi[k]);
-      if (r < dur) fi[k] = r * (0.5f / dur);
-      else if (r > dur) fi[k] = 0.5f + (r - dur) * (0.5f / (1.0f - dur));
-      clk[k] = sinf(6.2831855f * fi[k]);
-    }
-    if (m->terminate_on_base_contact && sqrtf(f3[0] * f3[0] + f3[1] * f3[1] + f3[2] * f3[2]) > 1.0f) fl |= 1u;
-    euler_xyz_f(q, rpy);
-    float r = rpy[0], p = rpy[1];
-    if (r > 3.1415927f) r -= 6.2831855f;
-    if (p > 3.1415927f) p -= 6.2831855f;
-    const float z = rs[2] - aoz;
-    if ((m->termination_flags & MQE_TERM_ROLL) && fabsf(r) > m->roll_thr) fl |= 2u;
-    if ((m->termination_flags & MQE_TERM_PITCH) && fabsf(p) > m->pitch_thr) fl |= 4u;
-    if ((m->termination_flags & MQE_TERM_Z_HIGH) && z > m->zhigh_thr) fl |= 8u;
-    if ((m->termination_flags & MQE_TERM_Z_LOW) && z < m->zlow_thr) fl |= 16u;
+    for (int k = 0; k < 4; k++) bq[k] = rs[3 + k];
+    fl = robot_frame(m, rs, gpar, gi0, f3, aoz, dtp, lv, av, pgr, clk, gi1, rpy);
   }
   ETAP(2);
   // any robot of the env: OR over the agent lanes (lane ^ PEPW, ^ 2 PEPW stay inside the PEPW * AM robot lanes)
 #pragma unroll
   for (int d = PEPW; d < PEPW * AM; d <<= 1) fl |= (unsigned)__shfl_xor((int)fl, d);
-  const uint8_t to = ep > m->max_episode_length, rterm = (fl >> 1) & 1, pterm = (fl >> 2) & 1, zh = (fl >> 3) & 1;
+  const uint8_t to = ep > m->max_episode_length;
   const uint8_t reset = (uint8_t)(mine && (fl != 0 || to));       // the same value on all robot lanes of the env
   // ---- stores of the frame quantities and flags ------------------------------------------------------------------------------
-  if (lead) {
-    st.ep_len[e] = ep;
-    st.time_out[e] = to;
-    if (m->termination_flags & MQE_TERM_ROLL) st.r_term[e] = rterm;
-    if (m->termination_flags & MQE_TERM_PITCH) st.p_term[e] = pterm;
-    if (m->termination_flags & MQE_TERM_Z_HIGH) st.zh_term[e] = zh;
-    st.reset_buf[e] = reset;
-    st.wdone[e] = reset;                        // the flag once more, in the packed return batch (byte tail: a torch.bool view, no kernel)
-    if (m->terminate_on_base_contact) st.collide_buf[e] = reset;
-  }
-  if (mine) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) { st.blv[i * 3 + k] = lv[k]; st.bav[i * 3 + k] = av[k]; st.pg[i * 3 + k] = pgr[k]; }
-#pragma unroll
-    for (int k = 0; k < 4; k++) { st.bquat[i * 4 + k] = bq[k]; st.clock[i * 4 + k] = clk[k]; }
-    st.gait[i] = gi1;
-  }
+  if (lead) env_flags_store(m, st, e, ep, fl, to, reset);
+  if (mine) robot_frame_store(st, i, lv, av, pgr, bq, clk, gi1);
   ETAP(3);
   // wrapper's view of root_states_npc: copy taken before the NPC script (legged_robot.py:136); xy/vel only are read
   // (staged in LDS by the whole wavefront: as a per-lane array of P * 13 floats it lived in scratch memory)
@@ -1135,36 +1189,24 @@ __device__ __forceinline__ void post_body(const DevModel* m, const DevState& st,
   if (mine) {
     float* ob = bag + a * MQE_OBS_BAG;
 #pragma unroll
-    for (int k = 0; k < 3; k++) { ob[k] = rs[k] - eo[k]; ob[3 + k] = rpy[k]; }
+    for (int k = 0; k < 3; k++) obs_row_axis(ob, k, rs[k], eo[k], rpy[k], lv[k], av[k], pgr[k]);
+#pragma unroll
+    for (int j = 0; j < 12; j++) obs_row_joint(m, ob, j, dq[2 * j], dq[2 * j + 1], act[j], act[j]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) obs_row_quad(ob, k, clk[k], bq[k]);
+#pragma unroll
+    for (int k = 71; k < MQE_OBS_BAG; k++) ob[k] = 0.0f;               // row padding (the LDS copy is stored whole)
 #pragma unroll
     for (int j = 0; j < 12; j++) {
-      ob[6 + j] = (dq[2 * j] - m->default_dof_pos[j]) * 1.0f;
-      ob[18 + j] = dq[2 * j + 1] * 0.05f;
-      ob[36 + j] = act[j];
-      ob[48 + j] = act[j];
       la[a * 12 + j] = act[j];
       la[PEPW * AM * 12 + a * 12 + j] = dq[2 * j + 1];             // legged_robot.py:152
     }
-#pragma unroll
-    for (int k = 0; k < 3; k++) { ob[30 + k] = lv[k] * 2.0f; ob[33 + k] = av[k] * 0.25f; ob[60 + k] = pgr[k]; }
-#pragma unroll
-    for (int k = 0; k < 4; k++) { ob[63 + k] = clk[k]; ob[67 + k] = bq[k]; }
-#pragma unroll
-    for (int k = 71; k < MQE_OBS_BAG; k++) ob[k] = 0.0f;               // row padding (the LDS copy is stored whole)
   }
   __syncthreads();
   ETAP(7);
   if (lead) {
     wrapper_env_dev<true>(m, st, e, 0, npc_pre, wrapper_level, bag);
-    // _push_robots (go1.py:237, legged_robot.py:470-476): after this step's frame quantities were taken, before reset_idx --
-    // whose U(-0.5, 0.5) base velocities replace the push in the envs that reset.  One draw per robot (the reference draws
-    // (num_envs, 2) for a (num_envs * num_agents, 2) slice, which only broadcasts for a single agent).
-    if (push_count > 0 && !reset)
-      for (int b = 0; b < A; b++) {
-        float* rv = root + b * 13 + 7;
-        rv[0] = mqe_rand(m, e, (int)(MQE_RNG_PUSH + (uint32_t)push_count), (uint32_t)(2 * b), -m->max_push, m->max_push);
-        rv[1] = mqe_rand(m, e, (int)(MQE_RNG_PUSH + (uint32_t)push_count), (uint32_t)(2 * b + 1), -m->max_push, m->max_push);
-      }
+    if (push_count > 0 && !reset) push_robots(m, root, e, A, push_count);
   }
   ETAP(8);
   {
@@ -1173,23 +1215,13 @@ __device__ __forceinline__ void post_body(const DevModel* m, const DevState& st,
     post_flush_rows(st.last_actions + r0 * 12, s_la, nrow * 12, tid);
     post_flush_rows(st.last_dof_vel + r0 * 12, s_la + PEPW * AM * 12, nrow * 12, tid);
   }
-  // go1.py:145: history[agent_ids] = 0 for the envs that reset this step -- rare, so the whole wavefront zeroes them,
-  // 16 B per lane per request: the f32 ring and, when present, its two f16 planes
+  // the envs that reset this step are rare, so the whole wavefront zeroes the history of each
   ETAP(9);
   unsigned long long rm = __ballot(lead && reset != 0);
   while (rm) {
     const int l = __ffsll((long long)rm) - 1;
     rm &= rm - 1;
-    const int er = blk * PEPW + l;
-    const int per = m->A * (MQE_HIST * MQE_FRAME / 4);                 // float4 units of this env's robots (contiguous)
-    float4* h4 = reinterpret_cast<float4*>(st.hist) + (size_t)er * per;
-    for (int k = tid; k < per; k += 64) h4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (st.hist2) {                                                    // same robots, 2 planes interleaved: the same bytes
-      uint4* p4 = reinterpret_cast<uint4*>(st.hist2 + (size_t)er * m->A * (2 * MQE_HIST * MQE_H2_FRAME));
-      const int per2 = m->A * (2 * MQE_HIST * MQE_H2_FRAME / 8);
-      for (int k = tid; k < per2; k += 64) p4[k] = make_uint4(0u, 0u, 0u, 0u);
-      if ((int)tid < m->A) st.hist_irr[(size_t)er * m->A + tid] = 0u;      // all frames zero: every frame continues its predecessor
-    }
+    zero_env_history(m, st, blk * PEPW + l, tid, 64);
   }
 }
 
@@ -1206,15 +1238,13 @@ __global__ void __launch_bounds__(64) k_post_physics(const DevModel* m, DevState
 // go1.py:145: history[agent_ids] = 0 for envs that reset this step.  One float4 per thread, R*540 threads.
 __global__ void k_reset_history(const DevModel* m, DevState st) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  const int per = MQE_HIST * MQE_FRAME / 4;
-  int i = idx / per;
+  int i = idx / HIST_F4;
   if (i >= m->R) return;
   if (!st.reset_buf[i / m->A]) return;
   reinterpret_cast<float4*>(st.hist)[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
   if (st.hist2) {      // the robot's compact f16 planes: 2 x 30 x 48 values = 360 16-byte words, one per thread of the first 360
-    const int w = idx - i * per;
-    if (w < 2 * MQE_HIST * MQE_H2_FRAME / 8)
-      reinterpret_cast<uint4*>(st.hist2 + (size_t)i * (2 * MQE_HIST * MQE_H2_FRAME))[w] = make_uint4(0u, 0u, 0u, 0u);
+    const int w = idx - i * HIST_F4;
+    if (w < HIST2_U4) reinterpret_cast<uint4*>(st.hist2)[(size_t)i * HIST2_U4 + w] = make_uint4(0u, 0u, 0u, 0u);
     if (w == 0) st.hist_irr[i] = 0u;
   }
 }
@@ -1261,7 +1291,7 @@ __global__ void k_hist2_rebuild(const DevModel* m, DevState st, int oldest) {
 }
 
 // post_physics_step in the stages the reference's method has (include/mqe_hip.h mqe_post_physics_stage; oracle: post_stages): one thread
-// per env, the per-env device functions of the fused kernel in the same arithmetic (results equal k_post_physics' to the last bit or two).
+// per env, the formulas post_body calls (results equal k_post_physics' to the last bit or two: the compiler contracts per kernel).
 // Not the fast path: it exists so that a subclass's check_termination / _step_npc / reset_idx / compute_observations can run in between.
 __global__ void __launch_bounds__(64) k_post_staged(const DevModel* m, DevState st, int stages, int wrapper_level, int push_count, int step_no) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1275,50 +1305,14 @@ __global__ void __launch_bounds__(64) k_post_staged(const DevModel* m, DevState 
     unsigned fl = 0;
     for (int a = 0; a < A; a++) {
       const int i = e * A + a;
-      float rs[13];
+      float rs[13], lv[3], av[3], pgr[3], clk[4], rpy[3], gi;
       for (int k = 0; k < 13; k++) rs[k] = root[a * 13 + k];
-      const float q[4] = {rs[3], rs[4], rs[5], rs[6]}, v[3] = {rs[7], rs[8], rs[9]}, w[3] = {rs[10], rs[11], rs[12]};
-      const float g3[3] = {0.0f, 0.0f, -1.0f};
-      float lv[3], av[3], pgr[3], clk[4];
-      quat_rotate_inverse_f(q, v, lv);
-      quat_rotate_inverse_f(q, w, av);
-      quat_rotate_inverse_f(q, g3, pgr);
-      const float* lo = st.loco_obs + (size_t)i * MQE_FRAME;
-      const float f = lo[7], ph = lo[8], off = lo[9], bnd = lo[10], dur = lo[11];
-      float gi = st.gait[i] + dtp * f;
-      gi = gi - floorf(gi);
-      float fi[4] = {gi + ph + off + bnd, gi + off, gi + bnd, gi + ph};
-      for (int k = 0; k < 4; k++) {
-        const float r = fi[k] - floorf(fi[k]);
-        if (r < dur) fi[k] = r * (0.5f / dur);
-        else if (r > dur) fi[k] = 0.5f + (r - dur) * (0.5f / (1.0f - dur));
-        clk[k] = sinf(6.2831855f * fi[k]);
-      }
-      const float* f3 = st.cf + ((size_t)e * m->NBR + a * MQE_NREP) * 3;
-      if (m->terminate_on_base_contact && sqrtf(f3[0] * f3[0] + f3[1] * f3[1] + f3[2] * f3[2]) > 1.0f) fl |= 1u;
-      float rpy[3];
-      euler_xyz_f(q, rpy);
-      float r = rpy[0], p = rpy[1];
-      if (r > 3.1415927f) r -= 6.2831855f;
-      if (p > 3.1415927f) p -= 6.2831855f;
-      const float z = rs[2] - as_global(m->agent_origins)[(size_t)i * 3 + 2];
-      if ((m->termination_flags & MQE_TERM_ROLL) && fabsf(r) > m->roll_thr) fl |= 2u;
-      if ((m->termination_flags & MQE_TERM_PITCH) && fabsf(p) > m->pitch_thr) fl |= 4u;
-      if ((m->termination_flags & MQE_TERM_Z_HIGH) && z > m->zhigh_thr) fl |= 8u;
-      if ((m->termination_flags & MQE_TERM_Z_LOW) && z < m->zlow_thr) fl |= 16u;
-      for (int k = 0; k < 3; k++) { st.blv[i * 3 + k] = lv[k]; st.bav[i * 3 + k] = av[k]; st.pg[i * 3 + k] = pgr[k]; }
-      for (int k = 0; k < 4; k++) { st.bquat[i * 4 + k] = q[k]; st.clock[i * 4 + k] = clk[k]; }
-      st.gait[i] = gi;
+      fl |= robot_frame(m, rs, st.loco_obs + (size_t)i * MQE_FRAME + 7, st.gait[i], st.cf + ((size_t)e * m->NBR + a * MQE_NREP) * 3,
+                        as_global(m->agent_origins)[(size_t)i * 3 + 2], dtp, lv, av, pgr, clk, gi, rpy);
+      robot_frame_store(st, i, lv, av, pgr, rs + 3, clk, gi);
     }
-    const uint8_t to = ep > m->max_episode_length, reset = (uint8_t)(fl != 0 || to);
-    st.ep_len[e] = ep;
-    st.time_out[e] = to;
-    if (m->termination_flags & MQE_TERM_ROLL) st.r_term[e] = (fl >> 1) & 1;
-    if (m->termination_flags & MQE_TERM_PITCH) st.p_term[e] = (fl >> 2) & 1;
-    if (m->termination_flags & MQE_TERM_Z_HIGH) st.zh_term[e] = (fl >> 3) & 1;
-    st.reset_buf[e] = reset;
-    st.wdone[e] = reset;
-    if (m->terminate_on_base_contact) st.collide_buf[e] = reset;
+    const uint8_t to = ep > m->max_episode_length;
+    env_flags_store(m, st, e, ep, fl, to, (uint8_t)(fl != 0 || to));
     for (int k = 0; k < P * 13; k++) npc_pre[k] = root[A * 13 + k];       // the wrapper's copy of the NPC rows, before the NPC script (legged_robot.py:136)
   }
   if ((stages & MQE_POST_NPC) && m->npc_kind == MQE_NPC_SHEEP) {
@@ -1338,14 +1332,7 @@ __global__ void __launch_bounds__(64) k_post_staged(const DevModel* m, DevState 
       for (int k = 0; k < P * 13; k++) npc_pre[k] = root[A * 13 + k];
       if (P == 0)
         for (int a = 0; a < A; a++) for (int k = 0; k < 4; k++) st.bquat[(e * A + a) * 4 + k] = root[a * 13 + 3 + k];
-      // go1.py:145: the history of the env's robots (the f32 ring and, when present, its compact f16 planes)
-      float4* h4 = reinterpret_cast<float4*>(st.hist) + (size_t)e * A * (MQE_HIST * MQE_FRAME / 4);
-      for (int k = 0; k < A * (MQE_HIST * MQE_FRAME / 4); k++) h4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (st.hist2) {
-        uint4* p4 = reinterpret_cast<uint4*>(st.hist2 + (size_t)e * A * (2 * MQE_HIST * MQE_H2_FRAME));
-        for (int k = 0; k < A * (2 * MQE_HIST * MQE_H2_FRAME / 8); k++) p4[k] = make_uint4(0u, 0u, 0u, 0u);
-        for (int a = 0; a < A; a++) st.hist_irr[(size_t)e * A + a] = 0u;
-      }
+      zero_env_history(m, st, e, 0, 1);
     }
   }
   if (stages & MQE_POST_OBS) {
@@ -1357,12 +1344,7 @@ __global__ void __launch_bounds__(64) k_post_staged(const DevModel* m, DevState 
   }
   if (stages & MQE_POST_WRAPPER) {
     wrapper_env_dev(m, st, e, 0, npc_pre, wrapper_level);
-    if (push_count > 0 && !st.reset_buf[e])
-      for (int b = 0; b < A; b++) {
-        float* rv = root + b * 13 + 7;
-        rv[0] = mqe_rand(m, e, (int)(MQE_RNG_PUSH + (uint32_t)push_count), (uint32_t)(2 * b), -m->max_push, m->max_push);
-        rv[1] = mqe_rand(m, e, (int)(MQE_RNG_PUSH + (uint32_t)push_count), (uint32_t)(2 * b + 1), -m->max_push, m->max_push);
-      }
+    if (push_count > 0 && !st.reset_buf[e]) push_robots(m, root, e, A, push_count);
   }
 }
 

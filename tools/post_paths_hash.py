@@ -1,0 +1,90 @@
+"""Do two builds of the engine compute the same bits in all three forms of the post-physics step?  For every task at a ragged batch size,
+with seeded random actions, max_episode_length = 4 and a push every third step (so that resets, history zeroing and pushes happen), takes
+40 steps and prints a sha256 of every MQE_T_* tensor after each one -- three times over:
+  fused   mqe_step as it is: the post-physics step is the epilogue of k_substeps
+  single  mqe_step under MQE_NO_FUSE_POST=1: k_post_physics, its own launch
+  staged  the step call by call with the five mqe_post_physics_stage calls (k_post_staged), beside a twin engine that ends its step with
+          mqe_post_physics_step; after the last step of a task a `dev` line per float tensor that ever differed between the two gives the
+          largest deviation seen, absolute and as a multiple of the rtol=2e-6, atol=1e-7 that tests/test_gpu_parity.py allows
+MQE_HIP_LIB=<other libmqe_hip.so> runs another build.  Run once per build, each in a fresh process on the GPU box, and diff the outputs:
+  python tools/post_paths_hash.py > hashes.txt"""
+import hashlib, os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "multiagent-quadruped-environment_amd"), os.path.join(ROOT, "tests")]
+import torch
+from helpers import make_desc, hip_engine
+from mqe.engine import abi
+from engine_variants import TASKS
+
+N, STEPS = 37, 40
+KINDS = sorted((getattr(abi, n), n) for n in dir(abi) if n.startswith("T_") and n != "T_COUNT")
+STAGES = (abi.POST_FRAME, abi.POST_NPC, abi.POST_RESET, abi.POST_OBS, abi.POST_WRAPPER)
+
+
+def engine(task):
+    d, keep, _ = make_desc(task, N, max_episode_length=4)
+    d.push_interval, d.max_push_vel_xy = 3, 1.0
+    e = hip_engine(d, keep)
+    e.reset_all()
+    return e
+
+
+def tensors(e):
+    """{name: host copy} of every tensor this scene has"""
+    out = {}
+    for kind, name in KINDS:
+        try:
+            out[name] = e.tensor(kind).cpu()
+        except Exception:       # not in this scene (no NPC, no curriculum, ...): the same in every build
+            out[name] = None
+    return out
+
+
+def print_hashes(mode, task, t, ts):
+    for name, v in ts.items():
+        h = "-" if v is None else hashlib.sha256(v.contiguous().numpy().tobytes()).hexdigest()[:16]
+        print("%s %s step %d %s %s" % (mode, task, t, name, h), flush=True)
+
+
+def fused(mode, task):
+    e = engine(task)
+    g = torch.Generator().manual_seed(0)
+    for t in range(STEPS):
+        e.step((torch.rand(N, e.tensor(abi.T_WRAPPER_OBS).shape[1], 3, generator=g) * 2 - 1).to(e.torch_device))
+        print_hashes(mode, task, t, tensors(e))
+    e.close()
+
+
+def staged(mode, task):
+    single, stg = engine(task), engine(task)
+    g = torch.Generator().manual_seed(0)
+    dev = {}
+    for t in range(STEPS):
+        cmd = (torch.rand(N * single.desc.num_agents, single.desc.num_command_dims, generator=g) * 2 - 1).to(single.torch_device)
+        for e in (single, stg):
+            e.policy_step(cmd)
+            for k in range(e.desc.decimation):
+                e.compute_torques(); e.simulate(); e.post_decimation_step(k)
+        single.post_physics_step()
+        for s in STAGES:
+            stg.post_physics_stage(s)
+        ta, tb = tensors(single), tensors(stg)
+        print_hashes(mode, task, t, tb)
+        for name, b in tb.items():
+            if b is not None and not torch.equal(ta[name], b):
+                a, b = ta[name].double(), b.double()
+                err = (a - b).abs()
+                was = dev.get(name, (0.0, 0.0))
+                dev[name] = (max(was[0], float(err.max())), max(was[1], float((err / (1e-7 + 2e-6 * b.abs())).max())))
+    for name, (ab, rel) in sorted(dev.items()):
+        print("dev %s %s %s max |staged - single launch| %.3e = %.3f of the allowance" % (mode, task, name, ab, rel), flush=True)
+    single.close(); stg.close()
+
+
+if __name__ == "__main__":
+    for mode, env, run in (("fused", {}, fused), ("single", {"MQE_NO_FUSE_POST": "1"}, fused), ("staged", {}, staged)):
+        os.environ.update(env)
+        for task in TASKS:
+            run(mode, task)
+        for k in env:
+            del os.environ[k]
