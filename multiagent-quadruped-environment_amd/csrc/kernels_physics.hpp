@@ -134,6 +134,19 @@ __device__ __forceinline__ bool sphere_capsule(V3 c, float r, V3 cq, V3 u, float
   return dist > 1e-9f;
 }
 
+// A robot primitive's second 16 B word (half-segment, radius): a box carries MINUS the radius of its bounding capsule, the sign marks it
+__device__ __forceinline__ bool prim_is_box(float4 w1) { return w1.w < 0.0f; }
+// Bilinear sample of a terrain map (ground relief, wall SDF) and its gradient: `cell` = the raster entry (ix, iy), tx / ty the position
+// inside the cell, ny the row length, hs the raster spacing (oracle/mqe_oracle.c::map_sample; the cell and the weights are the caller's,
+// shared by the maps it samples)
+__device__ __forceinline__ float map_sample_dev(const float* cell, int ny, float tx, float ty, float hs, float& gx, float& gy) {
+  const float s00 = cell[0], s01 = cell[1], s10 = cell[ny], s11 = cell[ny + 1];
+  const float a0 = s00 + (s01 - s00) * ty, a1 = s10 + (s11 - s10) * ty;
+  gx = (a1 - a0) / hs;
+  gy = ((s01 - s00) + ((s11 - s10) - (s01 - s00)) * tx) / hs;
+  return a0 + (a1 - a0) * tx;
+}
+
 // Closest approach of the segment p0 + t (p1 - p0), t in [0, 1], swept by the radius r, to a box (centre bc, rotation R, half extents h):
 // the signed distance to a convex set is convex along a line -> golden-section search, two first evaluations and sixteen refinements (the bracket ends at 0.05 % of the segment), the
 // sequence of oracle/mqe_oracle.c::seg_box.  Returns the signed distance at the final t; tb = that t, n = box -> point, pt = the point.
@@ -279,6 +292,18 @@ __device__ __forceinline__ void body_store(float* rec, const float* R, V3 p, V3 
   float4* r4 = reinterpret_cast<float4*>(rec);
   r4[0] = make_float4(R[0], R[1], R[2], R[3]); r4[1] = make_float4(R[4], R[5], R[6], R[7]);
   r4[2] = make_float4(R[8], p.x, p.y, p.z); r4[3] = make_float4(a.x, a.y, a.z, 0.0f);
+}
+__device__ __forceinline__ void body_load(const float* rec, float* R, V3& p) {
+  const float4 q0 = reinterpret_cast<const float4*>(rec)[0], q1 = reinterpret_cast<const float4*>(rec)[1], q2 = reinterpret_cast<const float4*>(rec)[2];
+  R[0] = q0.x; R[1] = q0.y; R[2] = q0.z; R[3] = q0.w; R[4] = q1.x; R[5] = q1.y; R[6] = q1.z; R[7] = q1.w; R[8] = q2.x;
+  p = v3(q2.y, q2.z, q2.w);
+}
+// a primitive of the link `rec` (centre cl, half-axis al in link coordinates) in the world: the link's rotation, the centre, the half-axis
+__device__ __forceinline__ void prim_world(const float* rec, V3 cl, V3 al, float* R, V3& c, V3& u) {
+  V3 p;
+  body_load(rec, R, p);
+  c = p + mat_vec(R, cl);
+  u = mat_vec(R, al);
 }
 // contact record in 16 B words: [actor A, link A, actor B (-1: static), link B] [point, separation] [normal, reported body A]
 // [contact force on A (written after the sweep of the last substep), reported body B]; the tangent frame is a function of the normal
@@ -533,8 +558,8 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
     const int j = bb - 1;
     const float qj = lds[L.dof + (br * 12 + j) * 2];
     qdj = lds[L.dof + (br * 12 + j) * 2 + 1];
-    joff = v3(rm.joint_offset[bb][0], rm.joint_offset[bb][1], rm.joint_offset[bb][2]);
-    jax = v3(rm.joint_axis[bb][0], rm.joint_axis[bb][1], rm.joint_axis[bb][2]);
+    joff = ld3(rm.joint_offset[bb]);
+    jax = ld3(rm.joint_axis[bb]);
     const V3 ax = jax;
     float c, s;
     joint_sincos(qj, s, c);
@@ -882,15 +907,15 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
     if (s < A * nsr) {
       const int r = (int)(s >= nsr) + (int)(s >= 2 * nsr) + (int)(s >= 3 * nsr), si = s - r * nsr;       // s / nsr for at most four robots, without the division
       const float* rec = lds + L.body + (r * MQE_NBODY + rm.sphere_body[si]) * BODY_STRIDE;
-      const float4 q0 = reinterpret_cast<const float4*>(rec)[0], q1 = reinterpret_cast<const float4*>(rec)[1], q2 = reinterpret_cast<const float4*>(rec)[2];
-      const float Rr[9] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x};
-      c = v3(q2.y, q2.z, q2.w) + mat_vec(Rr, v3(rm.sphere_center[si][0], rm.sphere_center[si][1], rm.sphere_center[si][2]));
+      float Rr[9]; V3 pr;
+      body_load(rec, Rr, pr);
+      c = pr + mat_vec(Rr, ld3(rm.sphere_center[si]));
       rad = rm.sphere_radius[si];
     } else {
       const int nsn_ = HI(HOT_NPC_N_SPHERES);
       const int q = s - A * nsr, p = nsn_ == 1 ? q : (nsn_ == 2 ? q >> 1 : q / nsn_), si = q - p * nsn_;      // (one or two spheres per NPC in every shipped scene: no run-time division)
       const float* rec = lds + L.body + (A * MQE_NBODY + p) * BODY_STRIDE;
-      c = ld3(rec + B_P) + mat_vec(rec + B_R, v3(m->npc_sphere_center[si][0], m->npc_sphere_center[si][1], m->npc_sphere_center[si][2]));
+      c = ld3(rec + B_P) + mat_vec(rec + B_R, ld3(m->npc_sphere_center[si]));
       rad = m->npc_sphere_radius[si];
     }
     float* sp = lds + L.sph + s * 4;
@@ -943,17 +968,15 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
   for (int t = lane; need_prims && t < A * npr; t += LW) {
     const int r = (int)(t >= npr) + (int)(t >= 2 * npr) + (int)(t >= 3 * npr), q = t - r * npr;
     const float* rec = lds + L.body + (r * MQE_NBODY + rm.prim_body[q]) * BODY_STRIDE;
-    const float4 q0 = reinterpret_cast<const float4*>(rec)[0], q1 = reinterpret_cast<const float4*>(rec)[1], q2 = reinterpret_cast<const float4*>(rec)[2];
-    const float Rr[9] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x};
-    const V3 c = v3(q2.y, q2.z, q2.w) + mat_vec(Rr, v3(rm.prim_center[q][0], rm.prim_center[q][1], rm.prim_center[q][2]));
-    const V3 u = mat_vec(Rr, v3(rm.prim_axis[q][0], rm.prim_axis[q][1], rm.prim_axis[q][2]));
+    float Rr[9]; V3 c, u;
+    prim_world(rec, ld3(rm.prim_center[q]), ld3(rm.prim_axis[q]), Rr, c, u);
     float4* pw0 = reinterpret_cast<float4*>(lds + L.prim) + t;
     float4* pw1 = pw0 + HI(HOT_NPRIM_ENV);
     pw0[0] = make_float4(c.x, c.y, c.z, rm.prim_bound[q]);
     // radius; a box carries MINUS the radius of its bounding capsule about its longest edge (the sign marks it; screens use |.|)
     float rad = rm.prim_half[q][0];
     if (rm.prim_type[q] == MQE_PRIM_BOX) {
-      const V3 hb = v3(rm.prim_half[q][0], rm.prim_half[q][1], rm.prim_half[q][2]), al = v3(rm.prim_axis[q][0], rm.prim_axis[q][1], rm.prim_axis[q][2]);
+      const V3 hb = ld3(rm.prim_half[q]), al = ld3(rm.prim_axis[q]);
       rad = -sqrtf(fmaxf(dot(hb, hb) - dot(al, al), 1e-12f));
     }
     pw1[0] = make_float4(u.x, u.y, u.z, rad);
@@ -967,15 +990,21 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
   float ssR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, ssTheta = 0.0f;
   if (SS) {
     ssB = ld3(lds + L.root + A * 13);
-    ssPiv = ssB + v3(m->ss_joint_offset[0], m->ss_joint_offset[1], m->ss_joint_offset[2]);
+    ssPiv = ssB + ld3(m->ss_joint_offset);
     ssTheta = lds[L.dof + (12 * A) * 2];
     float cth, sth;
     joint_sincos(ssTheta, sth, cth);                    // (libm beyond |theta| = 8: a revolving door goes round)
     if (m->ss_axis == 3) ssPiv.y += ssTheta;                                                // slider: translation along +y, no rotation
     else if (m->ss_axis == 2) { ssR[0] = cth; ssR[1] = -sth; ssR[3] = sth; ssR[4] = cth; }  // door: rotation about +z
     else { ssR[0] = cth; ssR[2] = sth; ssR[6] = -sth; ssR[8] = cth; }                       // plank: rotation about +y
-    ssC = ssPiv + mat_vec(ssR, v3(m->ss_plank_center[0], m->ss_plank_center[1], m->ss_plank_center[2]));
+    ssC = ssPiv + mat_vec(ssR, ld3(m->ss_plank_center));
   }
+  // the wall-corner map's entry for the raster point nearest to (x, y)
+  auto corner_cell = [&](float x, float y) -> size_t {
+    int ix = (int)floorf(x / HF(HOT_HS) + 0.5f), iy = (int)floorf(y / HF(HOT_HS) + 0.5f);
+    ix = min(max(ix, 0), HI(HOT_SDF_NX) - 1); iy = min(max(iy, 0), HI(HOT_SDF_NY) - 1);
+    return (size_t)ix * HI(HOT_SDF_NY) + iy;
+  };
   // ---- contact generation: terrain (ground plane, wall SDF), canonical order --------------------------------------------
   int nc = 0;
   int ovf = 0;                      // wave-uniform: a touching pair did not fit the bounded list (per-actor cap or list end)
@@ -1020,9 +1049,7 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
       bool nearw = false;
       if (l == 0 && r < A) {
         const V3 pbase = ld3(lds + L.body + r * MQE_NBODY * BODY_STRIDE + B_P);
-        int ix = (int)floorf(pbase.x / HF(HOT_HS) + 0.5f), iy = (int)floorf(pbase.y / HF(HOT_HS) + 0.5f);
-        ix = min(max(ix, 0), HI(HOT_SDF_NX) - 1); iy = min(max(iy, 0), HI(HOT_SDF_NY) - 1);
-        const float2 cc = reinterpret_cast<const float2*>(HP(HOT_WALL_CORNER_LO))[(size_t)ix * HI(HOT_SDF_NY) + iy];
+        const float2 cc = reinterpret_cast<const float2*>(HP(HOT_WALL_CORNER_LO))[corner_cell(pbase.x, pbase.y)];
         const float dx = pbase.x - cc.x, dy = pbase.y - cc.y, rr = 2.0f * HF(HOT_FEATURE_REACH) + 0.1f;
         nearw = dx * dx + dy * dy < rr * rr;
       }
@@ -1037,11 +1064,8 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
       const int ptype = rm.prim_type[q];
       if (isp) {
         const float* rec = lds + L.body + (r * MQE_NBODY + rm.prim_body[q]) * BODY_STRIDE;
-        const float4 q0 = reinterpret_cast<const float4*>(rec)[0], q1 = reinterpret_cast<const float4*>(rec)[1], q2 = reinterpret_cast<const float4*>(rec)[2];
-        Rb[0] = q0.x; Rb[1] = q0.y; Rb[2] = q0.z; Rb[3] = q0.w; Rb[4] = q1.x; Rb[5] = q1.y; Rb[6] = q1.z; Rb[7] = q1.w; Rb[8] = q2.x;
-        cq = v3(q2.y, q2.z, q2.w) + mat_vec(Rb, v3(rm.prim_center[q][0], rm.prim_center[q][1], rm.prim_center[q][2]));
-        uq = mat_vec(Rb, v3(rm.prim_axis[q][0], rm.prim_axis[q][1], rm.prim_axis[q][2]));
-        hb = v3(rm.prim_half[q][0], rm.prim_half[q][1], rm.prim_half[q][2]);
+        prim_world(rec, ld3(rm.prim_center[q]), ld3(rm.prim_axis[q]), Rb, cq, uq);
+        hb = ld3(rm.prim_half[q]);
         ebody = rm.prim_body[q]; erep = r * MQE_NREP + rm.prim_reported[q];
       }
       const float reach = rm.prim_bound[q] + HF(HOT_CONTACT_OFFSET);
@@ -1052,9 +1076,7 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
         if (j == 0) {
           if (isp && (HI(HOT_EDGE_MASK) & 1) != 0 && HP(HOT_WALL_CORNER_LO) != nullptr) {
             const float hs = HF(HOT_HS);
-            int ix = (int)floorf(cq.x / hs + 0.5f), iy = (int)floorf(cq.y / hs + 0.5f);
-            ix = min(max(ix, 0), HI(HOT_SDF_NX) - 1); iy = min(max(iy, 0), HI(HOT_SDF_NY) - 1);
-            const float2 cc = reinterpret_cast<const float2*>(HP(HOT_WALL_CORNER_LO))[(size_t)ix * HI(HOT_SDF_NY) + iy];
+            const float2 cc = reinterpret_cast<const float2*>(HP(HOT_WALL_CORNER_LO))[corner_cell(cq.x, cq.y)];
             const float dx = cq.x - cc.x, dy = cq.y - cc.y;
             if (dx * dx + dy * dy < reach * reach) {
               // the wall's top at the corner: one height per scene or the map's value at the raster point nearest to the corner
@@ -1070,8 +1092,8 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
           }
         } else if (isp && (ptype == MQE_PRIM_CAPSULE ? (HI(HOT_EDGE_MASK) & 2) != 0 : (HI(HOT_EDGE_MASK) & 4) != 0)) {      // capsule axes (bit 2) / box primitives (bit 4)
           const V3 nb = ld3(lds + L.root + A * 13);
-          bc = nb + v3(m->sb_center[j - 1][0], m->sb_center[j - 1][1], m->sb_center[j - 1][2]);
-          hh = v3(m->sb_half[j - 1][0], m->sb_half[j - 1][1], m->sb_half[j - 1][2]);
+          bc = nb + ld3(m->sb_center[j - 1]);
+          hh = ld3(m->sb_half[j - 1]);
           valid = fabsf(cq.x - bc.x) < hh.x + reach && fabsf(cq.y - bc.y) < hh.y + reach && fabsf(cq.z - bc.z) < hh.z + reach;
         }
         if (gballot(valid) == 0ull) continue;                 // (wave-wide skip: nobody near a wall edge / this box)
@@ -1107,21 +1129,15 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
       const float tx = fx - ix, ty = fy - iy;
       gsd = c.z - HF(HOT_GROUND_Z) - rad;
       if (HP(HOT_GROUND_HEIGHT_LO) != nullptr) {       // heightfield ground: first-order distance to the surface along its normal
-        const float* gh = HP(HOT_GROUND_HEIGHT_LO) + (size_t)ix * ny + iy;
-        const float h00 = gh[0], h01 = gh[1], h10 = gh[ny], h11 = gh[ny + 1];
-        const float b0 = h00 + (h01 - h00) * ty, b1 = h10 + (h11 - h10) * ty;
-        const float hx = (b1 - b0) / hs, hy = ((h01 - h00) + ((h11 - h10) - (h01 - h00)) * tx) / hs;
+        float hx, hy;
+        const float h = map_sample_dev(HP(HOT_GROUND_HEIGHT_LO) + (size_t)ix * ny + iy, ny, tx, ty, hs, hx, hy);
         const float inl = 1.0f / sqrtf(hx * hx + hy * hy + 1.0f);
         gn = v3(-hx * inl, -hy * inl, inl);
-        gsd = (c.z - HF(HOT_GROUND_Z) - (b0 + (b1 - b0) * tx)) * inl - rad;
+        gsd = (c.z - HF(HOT_GROUND_Z) - h) * inl - rad;
       }
       gflag = gsd < HF(HOT_CONTACT_OFFSET);
-      const float* sd = HP(HOT_WALL_SDF_LO) + (size_t)ix * ny + iy;
-      const float s00 = sd[0], s01 = sd[1], s10 = sd[ny], s11 = sd[ny + 1];
-      const float a0 = s00 + (s01 - s00) * ty, a1 = s10 + (s11 - s10) * ty;
-      float gx = (a1 - a0) / hs;
-      float gy = ((s01 - s00) + ((s11 - s10) - (s01 - s00)) * tx) / hs;
-      const float sh = a0 + (a1 - a0) * tx;
+      float gx, gy;
+      const float sh = map_sample_dev(HP(HOT_WALL_SDF_LO) + (size_t)ix * ny + iy, ny, tx, ty, hs, gx, gy);
       float gl = sqrtf(gx * gx + gy * gy);
       if (gl < 1e-6f) { gx = 1; gy = 0; gl = 1; }
       gx /= gl; gy /= gl;
@@ -1141,15 +1157,15 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
         bsd = 1e3f;
         for (int bx = 0; bx < shp.n_static; bx++) {
           V3 nn;
-          const float sdb = sphere_box(c, rad, nb + v3(m->sb_center[bx][0], m->sb_center[bx][1], m->sb_center[bx][2]), I3,
-                                       v3(m->sb_half[bx][0], m->sb_half[bx][1], m->sb_half[bx][2]), nn);
+          const float sdb = sphere_box(c, rad, nb + ld3(m->sb_center[bx]), I3,
+                                       ld3(m->sb_half[bx]), nn);
           if (sdb < bsd) { bsd = sdb; bn = nn; }
         }
         bflag = bsd < HF(HOT_CONTACT_OFFSET);
       }
       if (SS && act < A) {
         const float I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        bsd = sphere_box(c, rad, ssB, I3, v3(m->ss_base_half[0], m->ss_base_half[1], m->ss_base_half[2]), bn);
+        bsd = sphere_box(c, rad, ssB, I3, ld3(m->ss_base_half), bn);
         bflag = bsd < HF(HOT_CONTACT_OFFSET) && m->ss_base_half[0] > 0.0f;       // no platform: tug-of-war slider
         const float dx = c.x - ssB.x, dy = c.y - ssB.y, rho = sqrtf(dx * dx + dy * dy);
         if (c.z < ssB.z && c.z > ssB.z - m->ss_col_length && rho > 1e-6f) { csd = rho - m->ss_col_radius - rad; cn3 = v3(dx / rho, dy / rho, 0); cflag = csd < HF(HOT_CONTACT_OFFSET); }
@@ -1166,6 +1182,7 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
       const int cnt = __popcll(wg & mine_m) + __popcll(ww & mine_m) + __popcll(wb & mine_m) + __popcll(wc & mine_m) + __popcll(we & mine_m);
       const bool over = cnt > cap && act >= 0;
       if (__ballot(cnt > cap) != 0ull) {
+        // (oracle/mqe_oracle.c::depth_bucket: the same expression on the float-rounded separation)
         auto bucket = [](float sd) -> int { return sd < -1e-3f ? (int)floorf((sd + 1e-3f) * 500.0f) : 0; };
         const int lw = lane_wave;
         const int kb[5] = {bucket(gsd), bucket(wsd), bucket(bsd), bucket(csd), bucket(esd)};
@@ -1260,6 +1277,47 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
   // robot spheres vs the seesaw plank (dynamic: couples the robots through the hinge); after all terrain contacts
   const int nc_terr = nc;                                   // one-sided contacts end here; two-actor contacts follow
   const int pair_lim = nc_terr + mqe_maxpair(maxc) < maxc ? nc_terr + mqe_maxpair(maxc) : maxc;
+  // THE append of a two-actor contact (oracle/mqe_oracle.c::con_push): the lanes with `hit` take the slots nc, nc + 1, ... in lane order --
+  // the canonical order of one test -- as long as the slot is below pair_lim and the lane's rank below `room` (the site's per-robot share;
+  // NO_ROOM: none); nc moves on by the hits that had room, stops at pair_lim, and every hit that did not get a slot sets ovf.  True for a
+  // lane that stores its contact, into `slot` (con_store stays at the site, so that only these lanes evaluate its arguments).
+  constexpr int NO_ROOM = 1 << 20;
+  int taken = 0;                                     // how many of the last append's hits had room (wave-uniform)
+  auto con_append = [&](bool hit, int room, int& slot) -> bool {
+    const unsigned long long bh = gballot(hit);
+    taken = 0;
+    if (bh == 0ull) return false;
+    const unsigned long long lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const int rk = __popcll(bh & lower);
+    slot = nc + rk;
+    taken = __popcll(bh);
+    if (taken > room) { taken = room < 0 ? 0 : room; ovf = 1; }
+    nc += taken;
+    if (nc > pair_lim) { nc = pair_lim; ovf = 1; }
+    return hit && rk < room && slot < pair_lim;
+  };
+  // Feature point or NPC sphere (centre c, radius r) against primitive q of robot `rob` (its world centre cq and second word w1 from the
+  // table the caller read them from): signed distance and the unit normal from the primitive to the sphere, true when they are within
+  // the contact offset of each other.  The narrow phase of every sphere-against-robot pair; oracle/mqe_oracle.c::feat_vs_prim.
+  auto feat_vs_prim_dev = [&](int rob, int q, V3 c, float r, V3 cq, float4 w1, float& sd, V3& n) -> bool {
+    if (prim_is_box(w1)) {
+      sd = sphere_box(c, r, cq, lds + L.body + (rob * MQE_NBODY + rm.prim_body[q]) * BODY_STRIDE + B_R, ld3(rm.prim_half[q]), n);
+      return sd < HF(HOT_CONTACT_OFFSET);
+    }
+    const bool ok = sphere_capsule(c, r, cq, v3(w1.x, w1.y, w1.z), w1.w, sd, n);
+    return ok && sd < HF(HOT_CONTACT_OFFSET);
+  };
+  // this lane's primitive of robot a (lanes = primitives): its two words of the world-coordinate table, link, reported body
+  struct LanePrim { float4 w0, w1; int body, rep; };
+  auto lane_prim = [&](int a) -> LanePrim {
+    LanePrim lp; lp.w0 = make_float4(0, 0, 0, 0); lp.w1 = lp.w0; lp.body = 0; lp.rep = 0;
+    if (lane < npr) {
+      const float4* pw = reinterpret_cast<const float4*>(lds + L.prim) + (a * npr + lane);
+      lp.w0 = pw[0]; lp.w1 = pw[HI(HOT_NPRIM_ENV)];
+      lp.body = rm.prim_body[lane]; lp.rep = rm.prim_reported[lane];
+    }
+    return lp;
+  };
   // edge contacts of robot a's capsule primitives (lanes) with a moving box of the scene -- the plank / door, the free box -- (desc.edge_contacts
   // bit 2; oracle: "... and the plank's / door's edges", "... and its edges against the robot's primitives"): the closest approach of the
   // capsule's whole axis.  `room` = how many more contacts this robot may add (the plank's per-robot share), actor / reported body of the box.
@@ -1272,10 +1330,7 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
     bool valid = false;
     if (isp) {
       const float* rec = lds + L.body + (a * MQE_NBODY + rm.prim_body[q]) * BODY_STRIDE;
-      const float4 q0 = reinterpret_cast<const float4*>(rec)[0], q1 = reinterpret_cast<const float4*>(rec)[1], q2 = reinterpret_cast<const float4*>(rec)[2];
-      Rr[0] = q0.x; Rr[1] = q0.y; Rr[2] = q0.z; Rr[3] = q0.w; Rr[4] = q1.x; Rr[5] = q1.y; Rr[6] = q1.z; Rr[7] = q1.w; Rr[8] = q2.x;
-      cq = v3(q2.y, q2.z, q2.w) + mat_vec(Rr, v3(rm.prim_center[q][0], rm.prim_center[q][1], rm.prim_center[q][2]));
-      uq = mat_vec(Rr, v3(rm.prim_axis[q][0], rm.prim_axis[q][1], rm.prim_axis[q][2]));
+      prim_world(rec, ld3(rm.prim_center[q]), ld3(rm.prim_axis[q]), Rr, cq, uq);
       // screen: the primitive's bounding sphere against the box's (a point inside the box passes too)
       const V3 dd = cq - bc;
       const float reach = rm.prim_bound[q] + HF(HOT_CONTACT_OFFSET) + sqrtf(dot(hbx, hbx));
@@ -1285,22 +1340,12 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
     bool hit = false; float sd = 0; V3 n = v3(0, 0, 1), pa = v3(0, 0, 0);
     if (valid) {
       const float I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-      hit = (ptq == MQE_PRIM_BOX ? box_edges_vs_prim_dev(cq, v3(rm.prim_half[q][0], rm.prim_half[q][1], rm.prim_half[q][2]), Rr, bc, Rbx, hbx, sd, n, pa)
+      hit = (ptq == MQE_PRIM_BOX ? box_edges_vs_prim_dev(cq, ld3(rm.prim_half[q]), Rr, bc, Rbx, hbx, sd, n, pa)
                                  : edge_vs_box_dev(MQE_PRIM_CAPSULE, cq, uq, rm.prim_half[q][0], v3(0, 0, 0), I9, m->prim_feat_t[q][0], m->prim_feat_t[q][1], bc, Rbx, hbx, false, sd, n, pa))
             && sd < HF(HOT_CONTACT_OFFSET);
     }
-    const unsigned long long bh = gballot(hit);
-    if (bh == 0ull) return;
-    const unsigned long long lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    const int rk = __popcll(bh & lower), slot = nc + rk;
-    if (hit && rk < room && slot < pair_lim) {
-      float* cr = lds + L.con + slot * CON_STRIDE;
-      con_store(cr, a, rm.prim_body[q], actB, 0, pa, n, sd, a * MQE_NREP + rm.prim_reported[q], repB);
-    }
-    int tot = __popcll(bh);
-    if (tot > room) { tot = room < 0 ? 0 : room; ovf = 1; }
-    nc += tot;
-    if (nc > pair_lim) { nc = pair_lim; ovf = 1; }
+    int slot;
+    if (con_append(hit, room, slot)) con_store(lds + L.con + slot * CON_STRIDE, a, rm.prim_body[q], actB, 0, pa, n, sd, a * MQE_NREP + rm.prim_reported[q], repB);
   };
   if (SS) {
     const int capP = mqe_maxpair(maxc) / A;              // per robot, so that the first robot cannot starve the others
@@ -1312,22 +1357,13 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
         { const float4 q = *reinterpret_cast<const float4*>(sp); c = v3(q.x, q.y, q.z); rad = q.w; }
         body = rm.sphere_body[lane]; rep = a * MQE_NREP + rm.sphere_reported[lane];
         sd = m->ss_link_cyl ? sphere_vcyl(c, rad, ssC, m->ss_plank_half[0], m->ss_plank_half[2], n)
-                            : sphere_box(c, rad, ssC, ssR, v3(m->ss_plank_half[0], m->ss_plank_half[1], m->ss_plank_half[2]), n);
+                            : sphere_box(c, rad, ssC, ssR, ld3(m->ss_plank_half), n);
         hit = sd < HF(HOT_CONTACT_OFFSET);
       }
-      const unsigned long long bh = gballot(hit);
-      const unsigned long long lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-      const int rk = __popcll(bh & lower), slot = nc + rk;
-      if (hit && rk < capP && slot < pair_lim) {
-        float* cr = lds + L.con + slot * CON_STRIDE;
-        con_store(cr, a, body, A, 0, c - rad * n, n, sd, rep, A * MQE_NREP + 1);
-      }
-      int tot = __popcll(bh);
-      if (tot > capP) { tot = capP; ovf = 1; }
-      nc += tot;
-      if (nc > pair_lim) { nc = pair_lim; ovf = 1; }
+      int slot;
+      if (con_append(hit, capP, slot)) con_store(lds + L.con + slot * CON_STRIDE, a, body, A, 0, c - rad * n, n, sd, rep, A * MQE_NREP + 1);
       if ((HI(HOT_EDGE_MASK) & 6) != 0 && !m->ss_link_cyl)
-        pair_edges(a, ssC, ssR, v3(m->ss_plank_half[0], m->ss_plank_half[1], m->ss_plank_half[2]), A, A * MQE_NREP + 1, capP - tot);
+        pair_edges(a, ssC, ssR, ld3(m->ss_plank_half), A, A * MQE_NREP + 1, capP - taken);
     }
   }
   TSTAMP(9);
@@ -1351,25 +1387,20 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
           if (lane < nsr) {
             const float* spa = lds + L.sph + (a * nsr + lane) * 4;
             { const float4 q = *reinterpret_cast<const float4*>(spa); c = v3(q.x, q.y, q.z); ra = q.w; }
-            sd = sphere_box(c, ra, pb, brec + B_R, v3(m->npc_box_half[0], m->npc_box_half[1], m->npc_box_half[2]), n);
+            sd = sphere_box(c, ra, pb, brec + B_R, ld3(m->npc_box_half), n);
             hit = sd < HF(HOT_CONTACT_OFFSET);
           }
-          const unsigned long long bh = gballot(hit);
-          const unsigned long long lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-          const int slot = nc + __popcll(bh & lower);
-          if (hit && slot < pair_lim) {
-            float* cr = lds + L.con + slot * CON_STRIDE;
-            con_store(cr, a, rm.sphere_body[lane], b, 0, c - (ra + 0.5f * sd) * n, n, sd, a * MQE_NREP + rm.sphere_reported[lane], A * MQE_NREP + (b - A));
-          }
-          nc += __popcll(bh);
-          if (nc > pair_lim) { nc = pair_lim; ovf = 1; }
+          int slot;
+          if (con_append(hit, NO_ROOM, slot))
+            con_store(lds + L.con + slot * CON_STRIDE, a, rm.sphere_body[lane], b, 0, c - (ra + 0.5f * sd) * n, n, sd, a * MQE_NREP + rm.sphere_reported[lane],
+                      A * MQE_NREP + (b - A));
           // ... and the box's own eight corners (radius 0) against the robot's primitives (lanes = primitives): a corner of the box pressing
           // into a face of the trunk or into a bar between its ends.  Corners farther from the robot's base than any feature point reaches
           // are dropped with one ballot (lane = corner): a robot pushing a face of the 1 m box has none.
           unsigned long long cmask;
           {
             const V3 pbase = ld3(lds + L.body + a * MQE_NBODY * BODY_STRIDE + B_P);
-            const V3 hbx = v3(m->npc_box_half[0], m->npc_box_half[1], m->npc_box_half[2]);
+            const V3 hbx = ld3(m->npc_box_half);
             bool nearc = false;
             if (lane < 8) {
               const V3 cw = pb + mat_vec(brec + B_R, v3((lane & 4) ? hbx.x : -hbx.x, (lane & 2) ? hbx.y : -hbx.y, (lane & 1) ? hbx.z : -hbx.z));
@@ -1380,42 +1411,23 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
             cmask = gballot(nearc);
           }
           if (cmask != 0ull) {
-            float4 w0 = make_float4(0, 0, 0, 0), w1 = w0; int pbody = 0, prep = 0; V3 ph = v3(0, 0, 0);
-            if (lane < npr) {
-              const float4* pw = reinterpret_cast<const float4*>(lds + L.prim) + (a * npr + lane);
-              w0 = pw[0]; w1 = pw[HI(HOT_NPRIM_ENV)];
-              pbody = rm.prim_body[lane]; prep = rm.prim_reported[lane];
-              ph = v3(rm.prim_half[lane][0], rm.prim_half[lane][1], rm.prim_half[lane][2]);
-            }
-            const V3 hbx = v3(m->npc_box_half[0], m->npc_box_half[1], m->npc_box_half[2]);
+            const LanePrim lp = lane_prim(a);
+            const V3 hbx = ld3(m->npc_box_half);
             while (cmask != 0ull) {
               const int cn = __ffsll((long long)cmask) - 1;
               cmask &= cmask - 1ull;
               const V3 cc = pb + mat_vec(brec + B_R, v3((cn & 4) ? hbx.x : -hbx.x, (cn & 2) ? hbx.y : -hbx.y, (cn & 1) ? hbx.z : -hbx.z));
               bool hit2 = false; float sd2 = 0; V3 n2 = v3(0, 0, 1);
-              if (lane < npr) {
-                const V3 cq = v3(w0.x, w0.y, w0.z);
-                if (w1.w < 0.0f) {
-                  sd2 = sphere_box(cc, 0.0f, cq, lds + L.body + (a * MQE_NBODY + pbody) * BODY_STRIDE + B_R, ph, n2);
-                  hit2 = sd2 < HF(HOT_CONTACT_OFFSET);
-                } else {
-                  const bool ok = sphere_capsule(cc, 0.0f, cq, v3(w1.x, w1.y, w1.z), w1.w, sd2, n2);
-                  hit2 = ok && sd2 < HF(HOT_CONTACT_OFFSET);
-                }
-              }
-              const unsigned long long bh2 = gballot(hit2);
-              if (bh2 == 0ull) continue;
-              const int slot2 = nc + __popcll(bh2 & lower);
-              if (hit2 && slot2 < pair_lim) {
-                float* cr = lds + L.con + slot2 * CON_STRIDE;
-                con_store(cr, a, pbody, b, 0, cc - (0.5f * sd2) * n2, v3(-n2.x, -n2.y, -n2.z), sd2, a * MQE_NREP + prep, A * MQE_NREP + (b - A));
-              }
-              nc += __popcll(bh2);
-              if (nc > pair_lim) { nc = pair_lim; ovf = 1; }
+              if (lane < npr)
+                hit2 = feat_vs_prim_dev(a, lane, cc, 0.0f, v3(lp.w0.x, lp.w0.y, lp.w0.z), lp.w1, sd2, n2);
+              int slot2;
+              if (con_append(hit2, NO_ROOM, slot2))
+                con_store(lds + L.con + slot2 * CON_STRIDE, a, lp.body, b, 0, cc - (0.5f * sd2) * n2, v3(-n2.x, -n2.y, -n2.z), sd2, a * MQE_NREP + lp.rep,
+                          A * MQE_NREP + (b - A));
             }
           }
           if ((HI(HOT_EDGE_MASK) & 6) != 0)
-            pair_edges(a, pb, brec + B_R, v3(m->npc_box_half[0], m->npc_box_half[1], m->npc_box_half[2]), b, A * MQE_NREP + (b - A), 64);
+            pair_edges(a, pb, brec + B_R, ld3(m->npc_box_half), b, A * MQE_NREP + (b - A), NO_ROOM);
           continue;
         }
         if (b < A) {
@@ -1453,33 +1465,18 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
               const float4* pw = reinterpret_cast<const float4*>(lds + L.prim) + (qa * npr + q);
               const float4 w0 = pw[0], w1 = pw[HI(HOT_NPRIM_ENV)];
               const V3 cq = v3(w0.x, w0.y, w0.z);
-              const bool qbox = w1.w < 0.0f, qsph = !qbox && w1.x == 0.0f && w1.y == 0.0f && w1.z == 0.0f;      // wave-uniform
+              const bool qsph = !prim_is_box(w1) && w1.x == 0.0f && w1.y == 0.0f && w1.z == 0.0f;      // wave-uniform
               const V3 dq = c - cq;
               const float reach = ra + w0.w + HF(HOT_CONTACT_OFFSET);
               bool cand = lane < nsr && dot(dq, dq) < reach * reach && !(dir == 1 && foot && qsph);
               if (gballot(cand) == 0ull) continue;
               bool hit = false; float sd = 0; V3 n = v3(0, 0, 1);
-              if (cand) {
-                if (qbox) {
-                  sd = sphere_box(c, ra, cq, lds + L.body + (qa * MQE_NBODY + rm.prim_body[q]) * BODY_STRIDE + B_R,
-                                  v3(rm.prim_half[q][0], rm.prim_half[q][1], rm.prim_half[q][2]), n);
-                  hit = sd < HF(HOT_CONTACT_OFFSET);
-                } else {
-                  const bool ok = sphere_capsule(c, ra, cq, v3(w1.x, w1.y, w1.z), w1.w, sd, n);
-                  hit = ok && sd < HF(HOT_CONTACT_OFFSET);
-                }
-              }
-              const unsigned long long bh = gballot(hit);
-              if (bh == 0ull) continue;
-              const unsigned long long lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-              const int slot = nc + __popcll(bh & lower);
-              if (hit && slot < pair_lim) {
-                float* cr = lds + L.con + slot * CON_STRIDE;
-                con_store(cr, fa, rm.sphere_body[lane], qa, rm.prim_body[q], c - (ra + 0.5f * sd) * n, n, sd, fa * MQE_NREP + rm.sphere_reported[lane],
-                          qa * MQE_NREP + rm.prim_reported[q]);
-              }
-              nc += __popcll(bh);
-              if (nc > pair_lim) { nc = pair_lim; ovf = 1; }
+              if (cand)
+                hit = feat_vs_prim_dev(qa, q, c, ra, cq, w1, sd, n);
+              int slot;
+              if (con_append(hit, NO_ROOM, slot))
+                con_store(lds + L.con + slot * CON_STRIDE, fa, rm.sphere_body[lane], qa, rm.prim_body[q], c - (ra + 0.5f * sd) * n, n, sd,
+                          fa * MQE_NREP + rm.sphere_reported[lane], qa * MQE_NREP + rm.prim_reported[q]);
             }
           }
           continue;
@@ -1488,37 +1485,17 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
           // robot a against the collision spheres of free NPC b (ball, sheep): lanes = the robot's primitives, one sphere of b per
           // iteration; the contact's normal points from B (the NPC) to A
           const int nb = HI(HOT_NPC_N_SPHERES), ob = A * nsr + (b - A) * HI(HOT_NPC_N_SPHERES);
-          float4 w0 = make_float4(0, 0, 0, 0), w1 = w0; int ptype = MQE_PRIM_SPHERE, pbody = 0, prep = 0; V3 ph = v3(0, 0, 0);
-          if (lane < npr) {
-            const float4* pw = reinterpret_cast<const float4*>(lds + L.prim) + (a * npr + lane);
-            w0 = pw[0]; w1 = pw[HI(HOT_NPRIM_ENV)];
-            ptype = w1.w < 0.0f ? MQE_PRIM_BOX : MQE_PRIM_CAPSULE; pbody = rm.prim_body[lane]; prep = rm.prim_reported[lane];
-            ph = v3(rm.prim_half[lane][0], rm.prim_half[lane][1], rm.prim_half[lane][2]);
-          }
+          const LanePrim lp = lane_prim(a);
           for (int sb = 0; sb < nb; sb++) {
             const float4 qb = *reinterpret_cast<const float4*>(lds + L.sph + (ob + sb) * 4);
             const V3 cb = v3(qb.x, qb.y, qb.z); const float rb = qb.w;
             bool hit = false; float sd = 0; V3 n = v3(0, 0, 1);
-            if (lane < npr) {
-              const V3 cq = v3(w0.x, w0.y, w0.z);
-              if (ptype == MQE_PRIM_BOX) {
-                sd = sphere_box(cb, rb, cq, lds + L.body + (a * MQE_NBODY + pbody) * BODY_STRIDE + B_R, ph, n);
-                hit = sd < HF(HOT_CONTACT_OFFSET);
-              } else {
-                const bool ok = sphere_capsule(cb, rb, cq, v3(w1.x, w1.y, w1.z), w1.w, sd, n);
-                hit = ok && sd < HF(HOT_CONTACT_OFFSET);
-              }
-            }
-            const unsigned long long bh = gballot(hit);
-            if (bh == 0ull) continue;
-            const unsigned long long lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-            const int slot = nc + __popcll(bh & lower);
-            if (hit && slot < pair_lim) {
-              float* cr = lds + L.con + slot * CON_STRIDE;
-              con_store(cr, a, pbody, b, 0, cb - (rb + 0.5f * sd) * n, v3(-n.x, -n.y, -n.z), sd, a * MQE_NREP + prep, A * MQE_NREP + (b - A));
-            }
-            nc += __popcll(bh);
-            if (nc > pair_lim) { nc = pair_lim; ovf = 1; }
+            if (lane < npr)
+              hit = feat_vs_prim_dev(a, lane, cb, rb, v3(lp.w0.x, lp.w0.y, lp.w0.z), lp.w1, sd, n);
+            int slot;
+            if (con_append(hit, NO_ROOM, slot))
+              con_store(lds + L.con + slot * CON_STRIDE, a, lp.body, b, 0, cb - (rb + 0.5f * sd) * n, v3(-n.x, -n.y, -n.z), sd, a * MQE_NREP + lp.rep,
+                        A * MQE_NREP + (b - A));
           }
           continue;
         }
@@ -1537,17 +1514,11 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
             sd = dist - ra - rb;
             hit = sd < HF(HOT_CONTACT_OFFSET) && dist > 1e-9f;
           }
-          const unsigned long long bh = gballot(hit);
-          if (bh == 0ull) continue;
-          const unsigned long long lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-          const int slot = nc + __popcll(bh & lower);
-          if (hit && slot < pair_lim) {
-            float* cr = lds + L.con + slot * CON_STRIDE;
+          int slot;
+          if (con_append(hit, NO_ROOM, slot)) {
             const V3 n = (1.0f / dist) * ev;
-            con_store(cr, a, 0, b, 0, cb + (rb + 0.5f * sd) * n, n, sd, A * MQE_NREP + (a - A), A * MQE_NREP + (b - A));
+            con_store(lds + L.con + slot * CON_STRIDE, a, 0, b, 0, cb + (rb + 0.5f * sd) * n, n, sd, A * MQE_NREP + (a - A), A * MQE_NREP + (b - A));
           }
-          nc += __popcll(bh);
-          if (nc > pair_lim) { nc = pair_lim; ovf = 1; }
         }
       }
     if (npc_pass && near_npcs) {                       // (wave-uniform: a flock in which no two sheep are within reach of each other skips its pair passes)
@@ -1569,17 +1540,11 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
           sd = dist - qa.w - rb;
           hit = sd < HF(HOT_CONTACT_OFFSET) && dist > 1e-9f;
         }
-        const unsigned long long bh = gballot(hit);
-        if (bh == 0ull) continue;
-        const unsigned long long lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-        const int slot = nc + __popcll(bh & lower);
-        if (hit && slot < pair_lim) {
-          float* cr = lds + L.con + slot * CON_STRIDE;
+        int slot;
+        if (con_append(hit, NO_ROOM, slot)) {
           const V3 n = (1.0f / dist) * ev;
-          con_store(cr, A + i, 0, A + j, 0, cb + (rb + 0.5f * sd) * n, n, sd, A * MQE_NREP + i, A * MQE_NREP + j);
+          con_store(lds + L.con + slot * CON_STRIDE, A + i, 0, A + j, 0, cb + (rb + 0.5f * sd) * n, n, sd, A * MQE_NREP + i, A * MQE_NREP + j);
         }
-        nc += __popcll(bh);
-        if (nc > pair_lim) { nc = pair_lim; ovf = 1; }
       }
     }
     // links of one robot against each other (asset.self_collisions = 0): lanes = the model's candidate (feature point, primitive)
@@ -1626,27 +1591,12 @@ __device__ __forceinline__ void phys_substep(const DevModel* __restrict__ m, con
             f = selfp[k] & 255; q = selfp[k] >> 8;
             c = v3(si4[k].x, si4[k].y, si4[k].z); ra = si4[k].w;
             const V3 cq = v3(sj4[k].x, sj4[k].y, sj4[k].z);
-            const float4 w1 = pp0[HI(HOT_NPRIM_ENV) + q];
-            if (w1.w < 0.0f) {
-              sd = sphere_box(c, ra, cq, lds + L.body + (a * MQE_NBODY + rm.prim_body[q]) * BODY_STRIDE + B_R,
-                              v3(rm.prim_half[q][0], rm.prim_half[q][1], rm.prim_half[q][2]), n);
-              hit = sd < HF(HOT_CONTACT_OFFSET);
-            } else {
-              const bool ok = sphere_capsule(c, ra, cq, v3(w1.x, w1.y, w1.z), w1.w, sd, n);
-              hit = ok && sd < HF(HOT_CONTACT_OFFSET);
-            }
+            hit = feat_vs_prim_dev(a, q, c, ra, cq, pp0[HI(HOT_NPRIM_ENV) + q], sd, n);
           }
-          const unsigned long long bh = gballot(hit);
-          if (bh == 0ull) continue;
-          const unsigned long long lower = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-          const int slot = nc + __popcll(bh & lower);
-          if (hit && slot < pair_lim) {
-            float* cr = lds + L.con + slot * CON_STRIDE;
-            con_store(cr, a, rm.sphere_body[f], a, rm.prim_body[q], c - (ra + 0.5f * sd) * n, n, sd, a * MQE_NREP + rm.sphere_reported[f],
-                      a * MQE_NREP + rm.prim_reported[q]);
-          }
-          nc += __popcll(bh);
-          if (nc > pair_lim) { nc = pair_lim; ovf = 1; }
+          int slot;
+          if (con_append(hit, NO_ROOM, slot))
+            con_store(lds + L.con + slot * CON_STRIDE, a, rm.sphere_body[f], a, rm.prim_body[q], c - (ra + 0.5f * sd) * n, n, sd,
+                      a * MQE_NREP + rm.sphere_reported[f], a * MQE_NREP + rm.prim_reported[q]);
         }
       }
   }

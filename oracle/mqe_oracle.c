@@ -747,6 +747,11 @@ static void chol_solve(const real* L, int n, int ld, real* b) {
   }
 }
 
+/* storage of an env's contact list: the list itself + room for ONE robot's one-sided candidates before their reduction to CAP_ROBOT
+ * (manifold reduction: a robot collects every touching feature point -- at most four static surfaces each -- and primitive behind the
+ * at most MAXC contacts of the actors before it, then keeps CAP_ROBOT of them) */
+#define CON_ROOM (MAXC + 320)
+_Static_assert(MAXC + 4 * MQE_MAX_SPHERES + MQE_MAX_PRIMS <= CON_ROOM, "a robot's one-sided candidates must fit behind a full contact list");
 typedef struct {
   bodyk_t bk[MAXA][NB];
   real L[MAXA][RD * RD];       /* Cholesky factor of each robot's mass matrix */
@@ -756,7 +761,7 @@ typedef struct {
   real prim_c[MAXA][MQE_MAX_PRIMS][3], prim_u[MAXA][MQE_MAX_PRIMS][3];   /* robots' primitives: centre, capsule half-segment (world) */
   real npcR[MAXP][9];
   real v[MAXDOF], tau[MAXDOF];
-  contact_t con[MAXC + 320];          /* + room for a robot's one-sided candidates before their reduction to CAP_ROBOT */
+  contact_t con[CON_ROOM];
   int nc;
 } envwork_t;
 
@@ -801,6 +806,26 @@ static void fill_jac(const mqo_sim* s, const envwork_t* w, int act, int body, co
       for (int q = 0; q < 3; q++) { J[q][o + k] += sign * dirs[q][k]; if (!lin_only) J[q][o + 3 + k] += sign * dot3(dirs[q], wv); }
     }
   }
+}
+
+/* THE append of a touching pair to the env's bounded contact list (the engine: kernels_physics.hpp con_append and the terrain pass's own
+ * ranking).  The callers come in the canonical order; a pair gets the next slot while the list is below `lim` (maxc for one-sided contacts,
+ * pair_lim for two-actor contacts, CON_ROOM while a robot collects for the manifold reduction) and the actor's own count *mine below `cap`
+ * (mine = NULL: no per-actor share).  Returns the zeroed record with kind / actors / separation set -- the caller fills bodies, reported
+ * bodies, normal and point -- or NULL for a pair that did not fit, which is what *ovf counts. */
+static contact_t* con_push(envwork_t* w, int lim, int* mine, int cap, int* ovf, int kind, int actA, int actB, real sd) {
+  if (!(w->nc < lim && (mine == NULL || *mine < cap))) { *ovf = 1; return NULL; }
+  if (mine != NULL) ++*mine;
+  contact_t* ct = &w->con[w->nc++];
+  memset(ct, 0, sizeof *ct);
+  ct->kind = kind; ct->actA = actA; ct->actB = actB; ct->sd = sd;
+  return ct;
+}
+/* depth class of the manifold reduction, from the float-rounded separation (the f64 build ranks what the engine ranks): 0 down to 1 mm of
+ * penetration, then one class per 2 mm (kernels_physics.hpp `bucket`) */
+static int depth_bucket(real sd) {
+  const float sdf = (float)sd;
+  return sdf < -1e-3f ? (int)floor((double)((sdf + 1e-3f) * 500.0f)) : 0;
 }
 
 /* feature point (sphere: centre c, radius r) against primitive q of robot `rob` (go1.urdf <collision> shapes, include/mqe_hip.h):
@@ -1036,10 +1061,8 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
      * 1-5 kept the first CAP_ROBOT and counted the rest as overflow; an NPC's cap still works that way.)  The engine does the same with a
      * ranking over the wavefront's candidate lanes (kernels_physics.hpp "keeps the DEEPEST ones"). */
     const int robot_first = w->nc;
-    const int robot_cap = cap;
-    const int reduce = (d->edge_contacts & 8) != 0;      /* optional (include/mqe_hip.h edge_contacts bit 8); off: the first CAP_ROBOT in feature order, the rest is overflow */
-    const int cap_eff = (act < A && reduce) ? MAXC + 320 : cap;      /* robots then collect without a cap and reduce */
-#define cap cap_eff
+    const int reduce = act < A && (d->edge_contacts & 8) != 0;      /* optional (include/mqe_hip.h edge_contacts bit 8); off: the first CAP_ROBOT in feature order, the rest is overflow */
+    const int cap_eff = reduce ? CON_ROOM : cap, lim_eff = reduce ? CON_ROOM : maxc;      /* a robot then collects without a cap, behind the list's end if need be, and reduces */
     for (int si = 0; si < w->sph_n[act]; si++) {
       const real* c = w->sph_c[act][si];
       real r = w->sph_r[act][si];
@@ -1093,12 +1116,9 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
             sd = dist - r; n[0] = gx * sh / dist; n[1] = gy * sh / dist; n[2] = dz / dist;
           }
         }
-        if (sd < d->contact_offset && !(w->nc < ((act < A && reduce) ? MAXC + 320 : maxc) && mine < cap)) ovf = 1;
-        if (sd < d->contact_offset && w->nc < ((act < A && reduce) ? MAXC + 320 : maxc) && mine < cap) {
-          mine++;
-          contact_t* ct = &w->con[w->nc++];
-          memset(ct, 0, sizeof *ct);
-          ct->kind = 0; ct->actA = act; ct->actB = -1; ct->sd = sd; ct->repB = -1;
+        contact_t* ct = sd < d->contact_offset ? con_push(w, lim_eff, &mine, cap_eff, &ovf, 0, act, -1, sd) : NULL;
+        if (ct) {
+          ct->repB = -1;
           ct->bodyA = act < A ? m->sphere_body[si] : 0;
           ct->repA = act < A ? act * MQE_NREP + m->sphere_reported[si] : A * MQE_NREP + (act - A);
           for (int k = 0; k < 3; k++) { ct->n[k] = n[k]; ct->p[k] = c[k] - r * n[k]; }
@@ -1136,29 +1156,23 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
           }
         }
         if (!got) continue;
-        if (sd < d->contact_offset && !(w->nc < ((act < A && reduce) ? MAXC + 320 : maxc) && mine < cap)) ovf = 1;
-        if (sd < d->contact_offset && w->nc < ((act < A && reduce) ? MAXC + 320 : maxc) && mine < cap) {
-          mine++;
-          contact_t* ct = &w->con[w->nc++];
-          memset(ct, 0, sizeof *ct);
-          ct->kind = 0; ct->actA = act; ct->actB = -1; ct->sd = sd; ct->repB = -1;
+        contact_t* ct = sd < d->contact_offset ? con_push(w, lim_eff, &mine, cap_eff, &ovf, 0, act, -1, sd) : NULL;
+        if (ct) {
+          ct->repB = -1;
           ct->bodyA = m->prim_body[q]; ct->repA = act * MQE_NREP + m->prim_reported[q];
           for (int k = 0; k < 3; k++) { ct->n[k] = n[k]; ct->p[k] = pa[k]; }
         }
       }
-#undef cap
-    if (act < A && reduce && mine > robot_cap) {
-      int keep[MAXC + 320];
+    if (reduce && mine > cap) {
+      int keep[CON_ROOM];
       for (int i = 0; i < mine; i++) {
-        const float sdi = (float)w->con[robot_first + i].sd;
-        const int bi = sdi < -1e-3f ? (int)floor((double)((sdi + 1e-3f) * 500.0f)) : 0;
+        const int bi = depth_bucket(w->con[robot_first + i].sd);
         int rank = 0;
         for (int j = 0; j < mine; j++) {
-          const float sdj = (float)w->con[robot_first + j].sd;
-          const int bj = sdj < -1e-3f ? (int)floor((double)((sdj + 1e-3f) * 500.0f)) : 0;
+          const int bj = depth_bucket(w->con[robot_first + j].sd);
           if (bj < bi || (bj == bi && j < i)) rank++;
         }
-        keep[i] = rank < robot_cap;
+        keep[i] = rank < cap;
       }
       int o = robot_first;
       for (int i = 0; i < mine; i++)
@@ -1177,12 +1191,8 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
         real r = w->sph_r[act][si], n[3];
         real hp[3] = {d->seesaw_plank_half[0], d->seesaw_plank_half[1], d->seesaw_plank_half[2]};
         real sd = d->seesaw_link_cylinder ? sphere_vcyl(c, r, ssC, hp[0], hp[2], n) : sphere_box(c, r, ssC, ssR, hp, n);
-        if (sd < d->contact_offset && !(w->nc < pair_lim && mine < (maxc / 2) / A)) ovf = 1;
-        if (sd < d->contact_offset && w->nc < pair_lim && mine < (maxc / 2) / A) {
-          mine++;
-          contact_t* ct = &w->con[w->nc++];
-          memset(ct, 0, sizeof *ct);
-          ct->kind = 2; ct->actA = act; ct->actB = A; ct->sd = sd;
+        contact_t* ct = sd < d->contact_offset ? con_push(w, pair_lim, &mine, (maxc / 2) / A, &ovf, 2, act, A, sd) : NULL;
+        if (ct) {
           ct->bodyA = m->sphere_body[si]; ct->repA = act * MQE_NREP + m->sphere_reported[si]; ct->bodyB = 0; ct->repB = A * MQE_NREP + 1;
           for (int k = 0; k < 3; k++) { ct->n[k] = n[k]; ct->p[k] = c[k] - r * n[k]; }
         }
@@ -1192,12 +1202,8 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
         for (int q = 0; q < m->n_prims; q++) {
           real hp[3] = {d->seesaw_plank_half[0], d->seesaw_plank_half[1], d->seesaw_plank_half[2]}, sd, n[3], pa[3];
           if (!edge_vs_box(s, w, act, q, ssC, ssR, hp, 12, d->edge_contacts, &sd, n, pa)) continue;
-          if (sd < d->contact_offset && !(w->nc < pair_lim && mine < (maxc / 2) / A)) ovf = 1;
-          if (sd < d->contact_offset && w->nc < pair_lim && mine < (maxc / 2) / A) {
-            mine++;
-            contact_t* ct = &w->con[w->nc++];
-            memset(ct, 0, sizeof *ct);
-            ct->kind = 2; ct->actA = act; ct->actB = A; ct->sd = sd;
+          contact_t* ct = sd < d->contact_offset ? con_push(w, pair_lim, &mine, (maxc / 2) / A, &ovf, 2, act, A, sd) : NULL;
+          if (ct) {
             ct->bodyA = m->prim_body[q]; ct->repA = act * MQE_NREP + m->prim_reported[q]; ct->bodyB = 0; ct->repB = A * MQE_NREP + 1;
             for (int k = 0; k < 3; k++) { ct->n[k] = n[k]; ct->p[k] = pa[k]; }
           }
@@ -1215,11 +1221,8 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
           const real* ca = w->sph_c[a][sa];
           real n[3];
           real sd = sphere_box(ca, w->sph_r[a][sa], npc_pos[b - A], w->npcR[b - A], hb, n);
-          if (sd < d->contact_offset && !(w->nc < pair_lim)) ovf = 1;
-          if (sd < d->contact_offset && w->nc < pair_lim) {
-            contact_t* ct = &w->con[w->nc++];
-            memset(ct, 0, sizeof *ct);
-            ct->kind = 1; ct->actA = a; ct->actB = b; ct->sd = sd;
+          contact_t* ct = sd < d->contact_offset ? con_push(w, pair_lim, NULL, 0, &ovf, 1, a, b, sd) : NULL;
+          if (ct) {
             ct->bodyA = m->sphere_body[sa]; ct->repA = a * MQE_NREP + m->sphere_reported[sa]; ct->bodyB = 0; ct->repB = A * MQE_NREP + (b - A);
             for (int k = 0; k < 3; k++) { ct->n[k] = n[k]; ct->p[k] = ca[k] - n[k] * (w->sph_r[a][sa] + (real)0.5 * sd); }
           }
@@ -1237,11 +1240,8 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
           for (int q = 0; q < m->n_prims; q++) {
             real n[3], sd;
             if (!feat_vs_prim(m, w, a, q, cc, (real)0, &sd, n)) continue;
-            if (sd < d->contact_offset && !(w->nc < pair_lim)) ovf = 1;
-            if (sd < d->contact_offset && w->nc < pair_lim) {
-              contact_t* ct = &w->con[w->nc++];
-              memset(ct, 0, sizeof *ct);
-              ct->kind = 1; ct->actA = a; ct->actB = b; ct->sd = sd;
+            contact_t* ct = sd < d->contact_offset ? con_push(w, pair_lim, NULL, 0, &ovf, 1, a, b, sd) : NULL;
+            if (ct) {
               ct->bodyA = m->prim_body[q]; ct->repA = a * MQE_NREP + m->prim_reported[q]; ct->bodyB = 0; ct->repB = A * MQE_NREP + (b - A);
               for (int k = 0; k < 3; k++) { ct->n[k] = -n[k]; ct->p[k] = cc[k] - n[k] * ((real)0.5 * sd); }
             }
@@ -1252,11 +1252,8 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
           for (int q = 0; q < m->n_prims; q++) {
             real sd, n[3], pa[3];
             if (!edge_vs_box(s, w, a, q, npc_pos[b - A], w->npcR[b - A], hb, 12, d->edge_contacts, &sd, n, pa)) continue;
-            if (sd < d->contact_offset && !(w->nc < pair_lim)) ovf = 1;
-            if (sd < d->contact_offset && w->nc < pair_lim) {
-              contact_t* ct = &w->con[w->nc++];
-              memset(ct, 0, sizeof *ct);
-              ct->kind = 1; ct->actA = a; ct->actB = b; ct->sd = sd;
+            contact_t* ct = sd < d->contact_offset ? con_push(w, pair_lim, NULL, 0, &ovf, 1, a, b, sd) : NULL;
+            if (ct) {
               ct->bodyA = m->prim_body[q]; ct->repA = a * MQE_NREP + m->prim_reported[q]; ct->bodyB = 0; ct->repB = A * MQE_NREP + (b - A);
               for (int k = 0; k < 3; k++) { ct->n[k] = n[k]; ct->p[k] = pa[k]; }
             }
@@ -1274,11 +1271,8 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
               if (dir == 1 && m->prim_type[q] == MQE_PRIM_SPHERE && m->prim_type[m->sphere_prim[f]] == MQE_PRIM_SPHERE) continue;
               real n[3], sd;
               if (!feat_vs_prim(m, w, qa, q, w->sph_c[fa][f], w->sph_r[fa][f], &sd, n)) continue;
-              if (sd < d->contact_offset && !(w->nc < pair_lim)) ovf = 1;
-              if (sd < d->contact_offset && w->nc < pair_lim) {
-                contact_t* ct = &w->con[w->nc++];
-                memset(ct, 0, sizeof *ct);
-                ct->kind = 1; ct->actA = fa; ct->actB = qa; ct->sd = sd;
+              contact_t* ct = sd < d->contact_offset ? con_push(w, pair_lim, NULL, 0, &ovf, 1, fa, qa, sd) : NULL;
+              if (ct) {
                 ct->bodyA = m->sphere_body[f]; ct->repA = fa * MQE_NREP + m->sphere_reported[f];
                 ct->bodyB = m->prim_body[q]; ct->repB = qa * MQE_NREP + m->prim_reported[q];
                 for (int k = 0; k < 3; k++) { ct->n[k] = n[k]; ct->p[k] = w->sph_c[fa][f][k] - n[k] * (w->sph_r[fa][f] + (real)0.5 * sd); }
@@ -1293,11 +1287,8 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
           for (int q = 0; q < m->n_prims; q++) {
             real n[3], sd;
             if (!feat_vs_prim(m, w, a, q, w->sph_c[b][sb], w->sph_r[b][sb], &sd, n)) continue;     /* n: from the primitive to the sphere */
-            if (sd < d->contact_offset && !(w->nc < pair_lim)) ovf = 1;
-            if (sd < d->contact_offset && w->nc < pair_lim) {
-              contact_t* ct = &w->con[w->nc++];
-              memset(ct, 0, sizeof *ct);
-              ct->kind = 1; ct->actA = a; ct->actB = b; ct->sd = sd;
+            contact_t* ct = sd < d->contact_offset ? con_push(w, pair_lim, NULL, 0, &ovf, 1, a, b, sd) : NULL;
+            if (ct) {
               ct->bodyA = m->prim_body[q]; ct->repA = a * MQE_NREP + m->prim_reported[q]; ct->bodyB = 0; ct->repB = A * MQE_NREP + (b - A);
               for (int k = 0; k < 3; k++) { ct->n[k] = -n[k]; ct->p[k] = w->sph_c[b][sb][k] - n[k] * (w->sph_r[b][sb] + (real)0.5 * sd); }   /* normal from B (the NPC) to A */
             }
@@ -1310,11 +1301,8 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
           real e[3] = {ca[0] - cb[0], ca[1] - cb[1], ca[2] - cb[2]};
           real dist = (real)sqrt((double)dot3(e, e));
           real sd = dist - w->sph_r[a][sa] - w->sph_r[b][sb];
-          if (sd < d->contact_offset && dist > (real)1e-9 && !(w->nc < pair_lim)) ovf = 1;
-          if (sd < d->contact_offset && w->nc < pair_lim && dist > (real)1e-9) {
-            contact_t* ct = &w->con[w->nc++];
-            memset(ct, 0, sizeof *ct);
-            ct->kind = 1; ct->actA = a; ct->actB = b; ct->sd = sd;
+          contact_t* ct = sd < d->contact_offset && dist > (real)1e-9 ? con_push(w, pair_lim, NULL, 0, &ovf, 1, a, b, sd) : NULL;
+          if (ct) {
             ct->bodyA = 0; ct->repA = A * MQE_NREP + (a - A); ct->bodyB = 0; ct->repB = A * MQE_NREP + (b - A);
             for (int k = 0; k < 3; k++) { ct->n[k] = e[k] / dist; ct->p[k] = cb[k] + ct->n[k] * (w->sph_r[b][sb] + (real)0.5 * sd); }
           }
@@ -1329,11 +1317,8 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
         int f = m->self_pair[pi] & 255, q = m->self_pair[pi] >> 8;
         real n[3], sd;
         if (!feat_vs_prim(m, w, a, q, w->sph_c[a][f], w->sph_r[a][f], &sd, n)) continue;
-        if (sd < d->contact_offset && !(w->nc < pair_lim)) ovf = 1;
-        if (sd < d->contact_offset && w->nc < pair_lim) {
-          contact_t* ct = &w->con[w->nc++];
-          memset(ct, 0, sizeof *ct);
-          ct->kind = 1; ct->actA = a; ct->actB = a; ct->sd = sd;
+        contact_t* ct = sd < d->contact_offset ? con_push(w, pair_lim, NULL, 0, &ovf, 1, a, a, sd) : NULL;
+        if (ct) {
           ct->bodyA = m->sphere_body[f]; ct->repA = a * MQE_NREP + m->sphere_reported[f];
           ct->bodyB = m->prim_body[q]; ct->repB = a * MQE_NREP + m->prim_reported[q];
           for (int k = 0; k < 3; k++) { ct->n[k] = n[k]; ct->p[k] = w->sph_c[a][f][k] - n[k] * (w->sph_r[a][f] + (real)0.5 * sd); }

@@ -7,24 +7,29 @@ with seeded random actions, max_episode_length = 4 and a push every third step (
           mqe_post_physics_step; after the last step of a task a `dev` line per float tensor that ever differed between the two gives the
           largest deviation seen, absolute and as a multiple of the rtol=2e-6, atol=1e-7 that tests/test_gpu_parity.py allows
 MQE_HIP_LIB=<other libmqe_hip.so> runs another build.  Run once per build, each in a fresh process on the GPU box, and diff the outputs:
-  python tools/post_paths_hash.py > hashes.txt"""
-import hashlib, os, sys
+  python tools/post_paths_hash.py > hashes.txt
+--oracle f32 | f64 steps the CPU checker (OracleEngine.step, mode "oracle") instead: the same scenes, seeds and lines, no GPU.  MQE_ORACLE_LIB=<file
+name in oracle/> selects another f32 build; another f64 build is compared by putting it in the place of oracle/libmqe_oracle_f64.so.
+--episode-length L replaces the 4 (robots are reset before they fall or meet; L > --steps: no time-out at all), --steps the 40.  After a
+task's last step a `seen` line gives the largest MQE_T_CONTACT_OVERFLOW / MQE_T_CONTACT_REDUCED value of the run: whether the bounded contact
+list ever filled up."""
+import argparse, hashlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "multiagent-quadruped-environment_amd"), os.path.join(ROOT, "tests")]
+sys.path[:0] = [os.path.join(ROOT, "multiagent-quadruped-environment_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 import torch
-from helpers import make_desc, hip_engine
+from helpers import make_desc, hip_engine, oracle_engine
 from mqe.engine import abi
 from engine_variants import TASKS
 
-N, STEPS = 37, 40
+N, STEPS, EPISODE, ORACLE = 37, 40, 4, None
 KINDS = sorted((getattr(abi, n), n) for n in dir(abi) if n.startswith("T_") and n != "T_COUNT")
 STAGES = (abi.POST_FRAME, abi.POST_NPC, abi.POST_RESET, abi.POST_OBS, abi.POST_WRAPPER)
 
 
 def engine(task):
-    d, keep, _ = make_desc(task, N, max_episode_length=4)
+    d, keep, _ = make_desc(task, N, max_episode_length=EPISODE)
     d.push_interval, d.max_push_vel_xy = 3, 1.0
-    e = hip_engine(d, keep)
+    e = hip_engine(d, keep) if ORACLE is None else oracle_engine(d, keep, f64=ORACLE == "f64")
     e.reset_all()
     return e
 
@@ -49,9 +54,15 @@ def print_hashes(mode, task, t, ts):
 def fused(mode, task):
     e = engine(task)
     g = torch.Generator().manual_seed(0)
+    seen = {"T_CONTACT_OVERFLOW": 0, "T_CONTACT_REDUCED": 0}
     for t in range(STEPS):
         e.step((torch.rand(N, e.tensor(abi.T_WRAPPER_OBS).shape[1], 3, generator=g) * 2 - 1).to(e.torch_device))
-        print_hashes(mode, task, t, tensors(e))
+        ts = tensors(e)
+        print_hashes(mode, task, t, ts)
+        for name in seen:
+            if ts.get(name) is not None:
+                seen[name] = max(seen[name], int(ts[name].max()))
+    print("seen %s %s %s" % (mode, task, " ".join("%s %d" % kv for kv in sorted(seen.items()))), flush=True)
     e.close()
 
 
@@ -82,6 +93,16 @@ def staged(mode, task):
 
 
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--oracle", choices=("f32", "f64"), default=None)
+    ap.add_argument("--episode-length", type=int, default=EPISODE)
+    ap.add_argument("--steps", type=int, default=STEPS)
+    a = ap.parse_args()
+    ORACLE, EPISODE, STEPS = a.oracle, a.episode_length, a.steps
+    if ORACLE is not None:
+        for task in TASKS:
+            fused("oracle", task)
+        sys.exit(0)
     for mode, env, run in (("fused", {}, fused), ("single", {"MQE_NO_FUSE_POST": "1"}, fused), ("staged", {}, staged)):
         os.environ.update(env)
         for task in TASKS:
