@@ -2479,10 +2479,6 @@ __global__ void __launch_bounds__(64) k_simulate_a2(const DevModel* __restrict__
 // Root/dof state is loaded once, stays in LDS across the substeps and is written back once; the actuator history
 // (two past position errors and velocities per joint) lives in registers for the whole launch; torques go straight
 // into the LDS slot the physics reads.  Control type "C" only (the reference's hierarchical controller).
-typedef float f32x16_p __attribute__((ext_vector_type(16)));
-// 1 + |x| >= 1: the hardware reciprocal (1 ulp) needs none of the range scaling a general division carries
-__device__ __forceinline__ float softsign_p(float x) { return x * __builtin_amdgcn_rcpf(1.0f + fabsf(x)); }
-
 #define ACT_TILES 2       // 2 x 32 joints >= 12 * MQE_MAX_AGENTS(=4)... agents <= 4 need 48 joints
 
 // Occupancy class of a scene shape.  Scenes of two robots and at most one more object (link, ball, box, scenery) need < 10 KiB of LDS
@@ -2623,9 +2619,7 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
         const int j = jt % 12;
         const float asc = ST_LATE(late, st, actions)[gi] * ma->action_scale;          // no hip reduction (legged_robot.py:380)
         const float q = lds[L.dof + jt * 2], qd = lds[L.dof + jt * 2 + 1], lim = ma->torque_limits[j];
-        float tau = asc;
-        if (ctrl == MQE_CTRL_P) tau = ma->kp * (asc + ma->default_dof_pos[j] - q) - ma->kd * qd;
-        else if (ctrl == MQE_CTRL_V) tau = ma->kp * (asc - qd) - ma->kd * (qd - ST_LATE(late, st, last_dof_vel)[gi]) / ma->dt;
+        float tau = joint_pd_torque(ctrl, asc, q, qd, ST_LATE(late, st, last_dof_vel) + gi, j, ma);
         tau = clampf(tau, -lim, lim);
         lds[L.tau + jt] = tau;
         if (evalid) {
@@ -2635,42 +2629,11 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
       }
     } else {                           // control type C: actuator network (one call site of the physics body below: it is
                                        // inlined, and two copies of its ~9 k instructions would not fit the instruction cache)
-      // weight fragments (A operands): row = hidden unit j32, k = this half-wave's element of each k pair; re-read every substep
-      // (L1/L2 resident, 5 kB shared by every wave)
-      const float* b0 = as_global(ma->actuator.b[0]);      // through the laundered pointer: the 70 fragment
-      const float* b1 = as_global(ma->actuator.b[1]);      // loads below stay inside the substep loop (global_load, not flat_load:
-      const float* W2 = as_global(ma->actuator.W[2]); const float* b2 = as_global(ma->actuator.b[2]);     // mqe_common.hpp as_global)
+      // this lane's weight fragments, re-read every substep through the laundered pointer: the 70 loads stay inside the substep loop
+      // (mqe_common.hpp act_load)
       constexpr bool act16 = !ACT32;
-      float a1[3], a2[16], w3[16], bb0[16], bb1[16];
-      // (the two matrix operands from the fragment-ordered copy: lane-contiguous, one 256 B request per fragment -- W1[j32 * 32 + u] itself
-      // is 64 lanes x a 128 B stride, 64 cache lines per instruction, 16 instructions per substep and wavefront)
-      const float* fragw = as_global(ma->act_frag) + lane_k;
-#pragma unroll
-      for (int s2 = 0; s2 < 3; s2++) a1[s2] = fragw[(16 + s2) * 64];
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int u = (r & 3) + 8 * (r >> 2) + 4 * h;
-        if constexpr (!act16) a2[r] = fragw[r * 64];
-        w3[r] = W2[u]; bb0[r] = b0[u]; bb1[r] = b1[u];
-#ifdef MQE_ACT_DUPLOAD
-        {   // experiment: the 48 two-address dword loads issued once more (volatile: kept) -- what do they cost at 4 wavefronts per SIMD?
-          const float d0 = *(const volatile float*)(W2 + u), d1 = *(const volatile float*)(b0 + u), d2 = *(const volatile float*)(b1 + u);
-          asm volatile("" :: "v"(d0), "v"(d1), "v"(d2));
-        }
-#endif
-      }
-      const float bout = b2[0];
-      // layer 2 on the f16 matrix cores (DevModel::act_f16; MQE_ACT_F32=1 keeps the f32 MFMA chain above): W1 as two f16 planes of 2^14 w in
-      // the fragment order of v_mfma_f32_32x32x16_f16 -- [k-step][plane][lane][8] -- one 16 B load per fragment
-      // (the four fragments live in the sixteen registers the f32 chain keeps its layer-2 operand in: one set of registers for both forms)
-      if constexpr (act16) {
-        const h2_gvec* f16w = (const h2_gvec*)(unsigned long long)ma->act_frag16 + lane_k;
-#pragma unroll
-        for (int f = 0; f < 4; f++) {
-          const h2_u32x4 t = f16w[f * 64];
-          a2[4 * f] = __uint_as_float(t.x); a2[4 * f + 1] = __uint_as_float(t.y); a2[4 * f + 2] = __uint_as_float(t.z); a2[4 * f + 3] = __uint_as_float(t.w);
-        }
-      }
+      ActNet net;
+      act_load<act16>(ma, lane_k, h, net);
       int pos = 0;
       if (ma->lag_steps > 0) {          // go1.py:337-339: the lag buffer shifts in every _compute_torques call, i.e. per substep
         const int n = ma->lag_steps + 1;
@@ -2700,11 +2663,10 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
         const float a_raw = ST_LATE(late, st, actions)[gi], ddp = ma->default_dof_pos[j], lim = ma->torque_limits[j];
         float lag_old = 0.0f;
         size_t lag_wr = 0;
-        if (lagged) {                                                // go1.py:337-339 (kernels_step.hpp lag_target: the same ring)
-          const size_t R12l = (size_t)ma->R * 12;
-          const int rd = pos + 1 >= ma->lag_steps + 1 ? 0 : pos + 1;
-          lag_old = ST_LATE(late, st, lag_buf)[(size_t)rd * R12l + gi];
-          lag_wr = (size_t)pos * R12l + gi;
+        if (lagged) {                                                // go1.py:337-339 (kernels_step.hpp lag_slots: lag_target's ring)
+          const LagSlots ls = lag_slots(pos, ma->lag_steps, (size_t)ma->R * 12, gi);
+          lag_old = ST_LATE(late, st, lag_buf)[ls.rd];
+          lag_wr = ls.wr;
         }
         float as = a_raw * ma->action_scale;
         if (j % 3 == 0) as *= ma->hip_scale_reduction;
@@ -2713,27 +2675,7 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
         const float q = ldsg[L.dof + jc * 2], qd = ldsg[L.dof + jc * 2 + 1];
         const float he1 = acthg[jc], he2 = acthg[nj + jc], hv1 = acthg[2 * nj + jc], hv2 = acthg[3 * nj + jc];
         const float err = q - tgt;
-        f32x16_p acc1, acc2;
-#pragma unroll
-        for (int r = 0; r < 16; r++) { acc1[r] = bb0[r]; acc2[r] = bb1[r]; }
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[0], h ? he1 : err, acc1, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[1], h ? qd : he2, acc1, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[2], h ? hv2 : hv1, acc1, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc1[r] = softsign_p(acc1[r]);
-        if constexpr (act16) {
-          // layer 2 on the f16 matrix cores (mqe_common.hpp: act_layer2_f16) -- the one phase of the substep that grew at 4 wavefronts per SIMD,
-          // where all four reach it together and queue for the SIMD's one matrix pipe.  Torques then equal the oracle's f32 fmaf chain to
-          // ~1e-6 instead of bit for bit.
-          acc2 = act_layer2_f16(acc1, acc2, a2);
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; r++) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[r], acc1[r], acc2, 0, 0, 0);
-        }
-        float part = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; r++) part = fmaf(w3[r], softsign_p(acc2[r]), part);
-        float tau = part + __shfl_xor(part, 32, 64) + bout;
+        float tau = act_eval<act16>(net, err, he1, he2, qd, hv1, hv2, h);
         tau = clampf(tau, -lim, lim);
         __syncthreads();                                   // every lane has read the history before it shifts
         if (ok && h == 0) {
@@ -2759,10 +2701,7 @@ __global__ void __launch_bounds__(64, EPW == 2 ? 2 : SubstepsClass<TP>::waves) k
     if (evalid)
       for (int jt = glane_k; jt < nj; jt += LW) {
         const float q = lds[L.dof + jt * 2], qd = lds[L.dof + jt * 2 + 1];
-        const int j = jt % 12;
-        const size_t o = ((size_t)e_k * 4 + (k < 4 ? k : 3)) * nj + jt;
-        ST_LATE(late, st, sub_dof_vel)[o] = qd;
-        ST_LATE(late, st, sub_exceed)[o] = (uint8_t)((q < ma->soft_lo[j]) | (q > ma->soft_hi[j]));
+        substep_log(ma, ST_LATE(late, st, sub_dof_vel), ST_LATE(late, st, sub_exceed), ((size_t)e_k * 4 + (k < 4 ? k : 3)) * nj + jt, jt % 12, q, qd);
       }
   }
   __syncthreads();

@@ -38,16 +38,6 @@ __device__ __forceinline__ float mqe_rand(const DevModel* m, int env, int count,
   float u = mqe_u01((uint32_t)m->seed, (uint32_t)(env + m->env_id_offset), (uint32_t)count, k);
   return (hi - lo) * u + lo;
 }
-// joint target delayed by m->lag_steps substeps (go1.py:337-339): ring [(L + 1)][R * 12] of scaled actions, slot `pos` is
-// written, the oldest slot (pos + 1) mod (L + 1) is read.  Both half-waves of an MFMA lane pair write the same value.
-__device__ __forceinline__ float lag_target(const DevModel* m, const DevState& st, size_t idx, float as, int pos) {
-  if (m->lag_steps <= 0) return as;
-  const int n = m->lag_steps + 1;
-  const size_t R12 = (size_t)m->R * 12;
-  st.lag_buf[(size_t)pos * R12 + idx] = as;
-  const int rd = pos + 1 >= n ? 0 : pos + 1;
-  return st.lag_buf[(size_t)rd * R12 + idx];
-}
 
 // ----------------------------------------------------------------------------------------------------------------
 // wrapper.step head: clip(action,-1,1) * action_scale (go1_sheep_wrapper.py:55-56) -> per-robot command; the scripted
@@ -312,10 +302,40 @@ __global__ void k_body_l0_finish(float* __restrict__ P1, int ldp, int col0, int 
 }
 
 // ----------------------------------------------------------------------------------------------------------------
-// Go1._compute_torques (go1.py:315-354) incl. the actuator network (go1.py:367-382): one thread per joint; the 1313
-// weights are wave-uniform, so they arrive through the scalar cache and every FMA is v_fmac(vgpr, sgpr).
-__device__ __forceinline__ float softsign_f(float x) { return x / (1.0f + fabsf(x)); }
+// The joint controller, Go1._compute_torques (go1.py:315-354) and the per-substep logs of post_decimation_step.  Each piece is stated once
+// and has two callers: the staged kernels (k_compute_torques, k_compute_torques_mfma, k_post_decimation) and the substep loop of k_substeps
+// (kernels_physics.hpp).  The actuator network of control type C is act_load / act_eval (mqe_common.hpp).
 
+// Action lag (go1.py:337-339): a ring [(L + 1)][R * 12] of scaled actions.  A call writes slot `pos` and reads the oldest one,
+// (pos + 1) mod (L + 1): the element offsets of the two for joint idx.  When the read and the write are issued is the caller's business.
+struct LagSlots { size_t rd, wr; };
+__device__ __forceinline__ LagSlots lag_slots(int pos, int lag_steps, size_t R12, size_t idx) {
+  const int rd = pos + 1 >= lag_steps + 1 ? 0 : pos + 1;
+  return {(size_t)rd * R12 + idx, (size_t)pos * R12 + idx};
+}
+// joint target delayed by m->lag_steps substeps.  Both half-waves of an MFMA lane pair write the same value.
+__device__ __forceinline__ float lag_target(const DevModel* m, const DevState& st, size_t idx, float as, int pos) {
+  if (m->lag_steps <= 0) return as;
+  const LagSlots s = lag_slots(pos, m->lag_steps, (size_t)m->R * 12, idx);
+  st.lag_buf[s.wr] = as;
+  return st.lag_buf[s.rd];
+}
+// Control types P / V / T (legged_robot.py:380-390): a few FMAs per joint, before the torque limit.  asc = action * action_scale, no hip
+// reduction (:380); last_qd: where the joint's speed at the last policy step stands, read for V only (as a value, loaded by the caller under
+// `ctrl == V`, it cost the k_substeps instances that own their state pointers 1 to 5 more spilled SGPRs).
+__device__ __forceinline__ float joint_pd_torque(int ctrl, float asc, float q, float qd, const float* last_qd, int j, const DevModel* m) {
+  float tau = asc;                                                                          // :389: T
+  if (ctrl == MQE_CTRL_P) tau = m->kp * (asc + m->default_dof_pos[j] - q) - m->kd * qd;        // legged_robot.py:385
+  else if (ctrl == MQE_CTRL_V) tau = m->kp * (asc - qd) - m->kd * (qd - *last_qd) / m->dt;     // :387: velocity targets, D term on the change per policy step
+  return tau;
+}
+// post_decimation_step (legged_robot.py:114-115): joint j's speed and soft-limit flag after a substep, into element o of the two logs
+__device__ __forceinline__ void substep_log(const DevModel* m, float* sub_dof_vel, uint8_t* sub_exceed, size_t o, int j, float q, float qd) {
+  sub_dof_vel[o] = qd;
+  sub_exceed[o] = (uint8_t)((q < m->soft_lo[j]) | (q > m->soft_hi[j]));
+}
+
+// P / V / T, one thread per joint (launch_torques sends control type C to k_compute_torques_mfma)
 __global__ void __launch_bounds__(256) k_compute_torques(const DevModel* m, DevState st, int dec_i, int lag_pos) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
   int R = m->R, A = m->A;
@@ -325,60 +345,17 @@ __global__ void __launch_bounds__(256) k_compute_torques(const DevModel* m, DevS
   const float* ds = st.dof + ((size_t)env * m->ND + a * 12 + j) * 2;
   float q = ds[0], qd = ds[1];
   float as = st.actions[idx] * m->action_scale;
+  const int ctrl = m->control_type;
   float tau;
-  if (m->control_type == MQE_CTRL_C) {
-    if (j % 3 == 0) as *= m->hip_scale_reduction;
-    float target = lag_target(m, st, (size_t)idx, as, lag_pos) + m->default_dof_pos[j];
-    float err = q - target;
-    float* e1 = st.act_hist; float* e2 = e1 + (size_t)R * 12; float* v1 = e2 + (size_t)R * 12; float* v2 = v1 + (size_t)R * 12;
-    float x[6] = {err, e1[idx], e2[idx], qd, v1[idx], v2[idx]};
-    const float* W0 = m->actuator.W[0]; const float* b0 = m->actuator.b[0];
-    const float* W1 = m->actuator.W[1]; const float* b1 = m->actuator.b[1];
-    const float* W2 = m->actuator.W[2]; const float* b2 = m->actuator.b[2];
-    float h1[32], h2[32];
-#pragma unroll
-    for (int o = 0; o < 32; o++) {
-      float acc = 0.0f;
-#pragma unroll
-      for (int k = 0; k < 6; k++) acc = fmaf(W0[o * 6 + k], x[k], acc);
-      h1[o] = softsign_f(acc + b0[o]);
-    }
-#pragma unroll
-    for (int o = 0; o < 32; o++) {
-      float acc = 0.0f;
-#pragma unroll
-      for (int k = 0; k < 32; k++) acc = fmaf(W1[o * 32 + k], h1[k], acc);
-      h2[o] = softsign_f(acc + b1[o]);
-    }
-    float acc = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 32; k++) acc = fmaf(W2[k], h2[k], acc);
-    tau = acc + b2[0];
-    e2[idx] = e1[idx]; e1[idx] = err;
-    v2[idx] = v1[idx]; v1[idx] = qd;
-  } else if (m->control_type == MQE_CTRL_V) {       // legged_robot.py:387: velocity targets, D term on the change per policy step
-    tau = m->kp * (as - qd) - m->kd * (qd - st.last_dof_vel[idx]) / m->dt;
-  } else if (m->control_type == MQE_CTRL_P) {
-    tau = m->kp * (as + m->default_dof_pos[j] - q) - m->kd * qd;       // legged_robot.py:385
-  } else if (m->control_type == MQE_CTRL_T) {
-    tau = as;
-  } else {
-    tau = 0.0f;
-  }
+  if (ctrl == MQE_CTRL_P || ctrl == MQE_CTRL_V || ctrl == MQE_CTRL_T) tau = joint_pd_torque(ctrl, as, q, qd, st.last_dof_vel + idx, j, m);
+  else tau = 0.0f;
   float lim = m->torque_limits[j];
   tau = clampf(tau, -lim, lim);
   st.torques[idx] = tau;
   if (dec_i >= 0) st.sub_tau[((size_t)env * 4 + dec_i) * 12 * A + a * 12 + j] = tau;   // post_decimation_step :113
 }
 
-// MFMA form of the same computation for control type "C" (the batched actuator-MLP GEMM of the north star):
-// one wavefront = 32 joints.  All three layers are evaluated TRANSPOSED (units x joints) with v_mfma_f32_32x32x2_f32,
-// so the accumulator layout of one layer (lane = joint column, 16 registers = 16 hidden units, split over the two
-// half-waves) is exactly the B-operand layout of the next: step r of layer 2 consumes hidden unit u(r,h) =
-// (r&3)+8(r>>2)+4h from register r of lane (joint, h) -- no LDS transpose, no shuffles; the weights are the A operand,
-// pre-permuted per lane into 3 + 16 VGPRs.  The 32->1 output layer is 16 FMAs per lane + one cross-half add.
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-
+// Control type "C" (the batched actuator-MLP GEMM of the north star): one wavefront = 32 joints, a joint per lane pair
 __global__ void __launch_bounds__(256) k_compute_torques_mfma(const DevModel* m, DevState st, int dec_i, int lag_pos) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j32 = lane & 31, h = lane >> 5;
@@ -389,53 +366,20 @@ __global__ void __launch_bounds__(256) k_compute_torques_mfma(const DevModel* m,
   const int ii = valid ? idx : nj - 1;
   const int i = ii / 12, j = ii - i * 12;
   const int env = i / A, a = i - env * A;
-  const float* W0 = m->actuator.W[0]; const float* b0 = m->actuator.b[0];
-  const float* W1 = m->actuator.W[1]; const float* b1 = m->actuator.b[1];
-  const float* W2 = m->actuator.W[2]; const float* b2 = m->actuator.b[2];
-  // per-lane weight fragments (A operands): row = hidden unit j32, k = the half-wave's element of each k-pair
-  float a1[3], a2[16], w3[16];
-  f32x16_t acc1, acc2;
-#pragma unroll
-  for (int s2 = 0; s2 < 3; s2++) a1[s2] = W0[j32 * 6 + 2 * s2 + h];
-#pragma unroll
-  for (int r = 0; r < 16; r++) {
-    const int u = (r & 3) + 8 * (r >> 2) + 4 * h;
-    a2[r] = W1[j32 * 32 + u];             // (act_f16: overwritten below with the four f16 fragments)
-    w3[r] = W2[u];
-    acc1[r] = b0[u];
-    acc2[r] = b1[u];
-  }
   float* e1 = st.act_hist; float* e2 = e1 + (size_t)R * 12; float* v1 = e2 + (size_t)R * 12; float* v2 = v1 + (size_t)R * 12;
   const float* ds = st.dof + ((size_t)env * m->ND + a * 12 + j) * 2;
   const float q = ds[0], qd = ds[1];
   float as = st.actions[ii] * m->action_scale;
   if (j % 3 == 0) as *= m->hip_scale_reduction;
   const float err = q - (lag_target(m, st, (size_t)ii, as, lag_pos) + m->default_dof_pos[j]);
-  const float x0 = err, x1 = e1[ii], x2 = e2[ii], x3 = qd, x4 = v1[ii], x5 = v2[ii];
-  // layer 1 (K = 6): B operand = input (2s + h) of this lane's joint
-  acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[0], h ? x1 : x0, acc1, 0, 0, 0);
-  acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[1], h ? x3 : x2, acc1, 0, 0, 0);
-  acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[2], h ? x5 : x4, acc1, 0, 0, 0);
-#pragma unroll
-  for (int r = 0; r < 16; r++) acc1[r] = softsign_f(acc1[r]);
-  // layer 2 (K = 32): step r consumes hidden units u(r,0), u(r,1); or -- DevModel::act_f16, the default -- the split-f16 form k_substeps uses
-  // (mqe_common.hpp: act_layer2_f16; the same instruction sequence on the same bits, so the staged step stays the fused one bit for bit)
-  if (m->act_f16) {
-    const mqe_u32x4* f16w = reinterpret_cast<const mqe_u32x4*>(m->act_frag16) + lane;
-#pragma unroll
-    for (int f = 0; f < 4; f++) {
-      const mqe_u32x4 t = f16w[f * 64];
-      a2[4 * f] = __uint_as_float(t.x); a2[4 * f + 1] = __uint_as_float(t.y); a2[4 * f + 2] = __uint_as_float(t.z); a2[4 * f + 3] = __uint_as_float(t.w);
-    }
-    acc2 = act_layer2_f16(acc1, acc2, a2);
-  } else {
-#pragma unroll
-    for (int r = 0; r < 16; r++) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[r], acc1[r], acc2, 0, 0, 0);
-  }
-  float part = 0.0f;
-#pragma unroll
-  for (int r = 0; r < 16; r++) part = fmaf(w3[r], softsign_f(acc2[r]), part);
-  float tau = part + __shfl_xor(part, 32, 64) + b2[0];
+  const float x1 = e1[ii], x2 = e2[ii], x4 = v1[ii], x5 = v2[ii];
+  // the pieces of act_eval (mqe_common.hpp); layer 2 and its operand in the form DevModel::act_f16 names: the split-f16 one (the default) or
+  // the f32 chain, as the k_substeps instance of this scene
+  ActNet w;
+  if (m->act_f16) act_load<true>(m, lane, h, w); else act_load<false>(m, lane, h, w);
+  const mqe_f32x16 s1 = act_layer1(w, err, x1, x2, qd, x4, x5, h);
+  const mqe_f32x16 acc2 = m->act_f16 ? act_layer2<true>(w, s1) : act_layer2<false>(w, s1);
+  float tau = act_out(w, acc2);
   if (valid && h == 0) {
     e2[idx] = x1; e1[idx] = err;
     v2[idx] = x4; v1[idx] = qd;

@@ -20,7 +20,7 @@
 struct DevMlp {
   int n_layers;
   int dims[MQE_MAX_LAYERS + 1];
-  const float* W[MQE_MAX_LAYERS];   // device, (out,in) row-major as given
+  const float* W[MQE_MAX_LAYERS];   // device, (out,in) row-major as given (the actuator's W[0], W[1]: null, uploaded as act_frag / act_frag16 only)
   const float* b[MQE_MAX_LAYERS];
 };
 
@@ -179,9 +179,8 @@ __device__ __forceinline__ DevState late_state() {
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
-// Layer 2 of the actuator network (32 x 32, unitree_go1.pt; go1.py:345) on the f16 matrix cores, shared by k_substeps and the stand-alone
-// k_compute_torques_mfma so that the fused and the staged step stay bit for bit the same: acc2 (= the bias on entry) += W1 s1 with both
-// operands as two f16 planes (x 2^14: |w| <= 1.06, |s1| < 1), products hh + hl + lh on v_mfma_f32_32x32x16_f16 (each exact, f32
+// Layer 2 of the actuator network (32 x 32, unitree_go1.pt; go1.py:345) on the f16 matrix cores (act_layer2<true> below, the
+// fused and the staged step's alike): acc2 (= the bias on entry) += W1 s1 with both operands as two f16 planes (x 2^14: |w| <= 1.06, |s1| < 1), products hh + hl + lh on v_mfma_f32_32x32x16_f16 (each exact, f32
 // accumulation; the dropped ll term is <= 2^-22 of a product): 6 MFMAs of 32 cycles instead of the 16 x 64 cycles of the f32 chain.
 // Layer 1's accumulator IS the B operand: register r of lane (joint, h) holds hidden unit (r & 3) + 8 (r >> 2) + 4 h, i.e. registers
 // 8 s .. 8 s + 7 are the eight k of half h in k-step s once the weight columns are permuted the same way (DevModel::act_frag16).
@@ -215,6 +214,88 @@ __device__ __forceinline__ mqe_f32x16 act_layer2_f16(const mqe_f32x16& s1, mqe_f
 #pragma unroll
   for (int r = 0; r < 16; r++) acc2[r] *= 3.7252902984619140625e-9f;    // 2^-28
   return acc2;
+}
+
+// The 6-32-32-1 actuator network (go1.py:367-382) on the matrix cores, stated once: k_substeps evaluates it at the head of every substep,
+// k_compute_torques_mfma for the staged step.  One wavefront = 32 joints.  All three layers are evaluated TRANSPOSED (units x joints) with
+// v_mfma_f32_32x32x2_f32, so the accumulator layout of one layer (lane = joint column, 16 registers = 16 hidden units, split over the two
+// half-waves) is exactly the B-operand layout of the next: step r of layer 2 consumes hidden unit u(r, h) = (r & 3) + 8 (r >> 2) + 4 h from
+// register r of lane (joint, h) -- no LDS transpose, no shuffles; the weights are the A operand, pre-permuted per lane into 3 + 16 VGPRs.
+// The 32 -> 1 output layer is 16 FMAs per lane + one cross-half add.
+typedef __attribute__((address_space(1))) mqe_u32x4 mqe_gu32x4;
+// 1 + |x| >= 1: the hardware reciprocal (1 ulp) needs none of the range scaling a general division carries
+__device__ __forceinline__ float softsign(float x) { return x * __builtin_amdgcn_rcpf(1.0f + fabsf(x)); }
+// this lane's weight fragments (A operands): row = hidden unit lane & 31, k = the half-wave's element of each k pair; a2: the layer-2 row in
+// f32, or the four f16 fragments [k-step][plane] as 16 dwords; w3, bb0, bb1: output weights and the two bias vectors in the unit order u(r, h)
+struct ActNet { float a1[3], a2[16], w3[16], bb0[16], bb1[16], bout; };
+// ma: the caller's model pointer as it stands (k_substeps: laundered, so that the 70 fragment loads stay inside its substep loop); global_load,
+// not flat_load (as_global).  The two matrix operands come from the fragment-ordered copies: lane-contiguous, one 256 B request per fragment --
+// W1[j32 * 32 + u] itself is 64 lanes x a 128 B stride, 64 cache lines per instruction.  L1/L2 resident, 5 kB shared by every wave.
+// h = lane >> 5 comes from the caller: derived in here, the fourth unit of every register group left the 16-byte load of the other three (this
+// function is simplified before it is inlined, without the lane's value range): 12 loads and 4 v_or more per call in k_substeps.
+template <bool ACT16> __device__ __forceinline__ void act_load(const DevModel* ma, int lane, int h, ActNet& w) {
+  const float* b0 = as_global(ma->actuator.b[0]);
+  const float* b1 = as_global(ma->actuator.b[1]);
+  const float* W2 = as_global(ma->actuator.W[2]); const float* b2 = as_global(ma->actuator.b[2]);
+  const float* fragw = as_global(ma->act_frag) + lane;
+#pragma unroll
+  for (int s2 = 0; s2 < 3; s2++) w.a1[s2] = fragw[(16 + s2) * 64];
+#pragma unroll
+  for (int r = 0; r < 16; r++) {
+    const int u = (r & 3) + 8 * (r >> 2) + 4 * h;
+    if constexpr (!ACT16) w.a2[r] = fragw[r * 64];
+    w.w3[r] = W2[u]; w.bb0[r] = b0[u]; w.bb1[r] = b1[u];
+  }
+  w.bout = b2[0];
+  // layer 2 on the f16 matrix cores (DevModel::act_f16; MQE_ACT_F32=1 keeps the f32 MFMA chain): W1 as two f16 planes of 2^14 w in the
+  // fragment order of v_mfma_f32_32x32x16_f16 -- [k-step][plane][lane][8] -- one 16 B load per fragment
+  // (the four fragments live in the sixteen registers the f32 chain keeps its layer-2 operand in: one set of registers for both forms)
+  if constexpr (ACT16) {
+    const mqe_gu32x4* f16w = (const mqe_gu32x4*)(unsigned long long)ma->act_frag16 + lane;
+#pragma unroll
+    for (int f = 0; f < 4; f++) {
+      const mqe_u32x4 t = f16w[f * 64];
+      w.a2[4 * f] = __uint_as_float(t.x); w.a2[4 * f + 1] = __uint_as_float(t.y); w.a2[4 * f + 2] = __uint_as_float(t.z); w.a2[4 * f + 3] = __uint_as_float(t.w);
+    }
+  }
+}
+// One joint per lane pair (h = lane >> 5): position error and joint speed now and at the two calls before (go1.py:341-350) -> the torque
+// before its limit.  act_eval is the three pieces below in a row; k_compute_torques_mfma, which chooses the form of layer 2 at run time,
+// calls the pieces, so that only layer 2 is there twice (both forms behind one branch around the whole evaluator: 548 vector instructions, not
+// 440).  Layer 1: its B operand is input 2 s + h of the lane's joint.
+__device__ __forceinline__ mqe_f32x16 act_layer1(const ActNet& w, float err, float e1, float e2, float qd, float v1, float v2, int h) {
+  mqe_f32x16 acc1;
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc1[r] = w.bb0[r];
+  acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.a1[0], h ? e1 : err, acc1, 0, 0, 0);
+  acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.a1[1], h ? qd : e2, acc1, 0, 0, 0);
+  acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.a1[2], h ? v2 : v1, acc1, 0, 0, 0);
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc1[r] = softsign(acc1[r]);
+  return acc1;
+}
+template <bool ACT16> __device__ __forceinline__ mqe_f32x16 act_layer2(const ActNet& w, const mqe_f32x16& s1) {
+  mqe_f32x16 acc2;
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc2[r] = w.bb1[r];
+  if constexpr (ACT16) {
+    // act_layer2_f16 above -- the one phase of the substep that grew at 4 wavefronts per SIMD, where all four reach it together and queue
+    // for the SIMD's one matrix pipe.  Torques then equal the oracle's f32 fmaf chain to ~1e-6 instead of bit for bit.
+    acc2 = act_layer2_f16(s1, acc2, w.a2);
+  } else {
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.a2[r], s1[r], acc2, 0, 0, 0);
+  }
+  return acc2;
+}
+__device__ __forceinline__ float act_out(const ActNet& w, const mqe_f32x16& acc2) {
+  float part = 0.0f;
+#pragma unroll
+  for (int r = 0; r < 16; r++) part = fmaf(w.w3[r], softsign(acc2[r]), part);
+  return part + __shfl_xor(part, 32, 64) + w.bout;
+}
+template <bool ACT16> __device__ __forceinline__ float act_eval(const ActNet& w, float err, float e1, float e2, float qd, float v1, float v2, int h) {
+  return act_out(w, act_layer2<ACT16>(w, act_layer1(w, err, e1, e2, qd, v1, v2, h)));
 }
 
 // counter-based RNG of the reset distribution and the domain randomisation: keyed by (seed, GLOBAL env id, count, stream)

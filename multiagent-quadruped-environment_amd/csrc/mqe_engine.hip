@@ -593,7 +593,7 @@ static int stage_scene(mqe_sim* s) {
   return 0;
 }
 
-// the actuator network: plain weights (k_compute_torques) and k_substeps' two fragment orders
+// the actuator network: output layer and biases as given, the two matrix layers in the lanes' fragment orders (mqe_common.hpp act_load)
 static int stage_actuator(mqe_sim* s) {
   const mqe_sim_desc* d = &s->d;
   DevModel& m = s->hm;
@@ -601,11 +601,9 @@ static int stage_actuator(mqe_sim* s) {
   memcpy(m.actuator.dims, d->actuator.dims, sizeof m.actuator.dims);
   if (d->actuator.n_layers != 3 || d->actuator.dims[0] != 6 || d->actuator.dims[1] != 32 || d->actuator.dims[2] != 32 || d->actuator.dims[3] != 1)
     return fail(-6, "actuator network must be 6-32-32-1 (unitree_go1.pt)");
-  for (int l = 0; l < 3; l++) {
-    UP(m.actuator.W[l], d->actuator.W[l], (size_t)d->actuator.dims[l] * d->actuator.dims[l + 1]);
-    UP(m.actuator.b[l], d->actuator.b[l], (size_t)d->actuator.dims[l + 1]);
-  }
-  {   // the same weights in k_substeps' fragment order (DevModel::act_frag): [19][64]
+  for (int l = 0; l < 3; l++) UP(m.actuator.b[l], d->actuator.b[l], (size_t)d->actuator.dims[l + 1]);
+  UP(m.actuator.W[2], d->actuator.W[2], (size_t)d->actuator.dims[2] * d->actuator.dims[3]);
+  {   // layers 1 and 2 in the fragment order of the lanes (DevModel::act_frag): [19][64]
     std::vector<float> fr((size_t)19 * 64);
     for (int lane = 0; lane < 64; lane++) {
       const int j32 = lane & 31, h = lane >> 5;
@@ -1064,8 +1062,7 @@ __global__ void k_post_decimation(const DevModel* m, DevState st, int dec_i) {
   const size_t o = ((size_t)e * 4 + dec_i) * nj + jt;
   const float q = st.dof[((size_t)e * m->ND + jt) * 2], qd = st.dof[((size_t)e * m->ND + jt) * 2 + 1];
   st.sub_tau[o] = st.torques[idx];
-  st.sub_dof_vel[o] = qd;
-  st.sub_exceed[o] = (q < m->soft_lo[j]) | (q > m->soft_hi[j]);
+  substep_log(m, st.sub_dof_vel, st.sub_exceed, o, j, q, qd);
 }
 // clip to clip_actions (legged_robot.py:108-110) -> st.actions
 __global__ void k_set_joint_actions(const DevModel* m, DevState st, const float* __restrict__ a12) {

@@ -1,7 +1,7 @@
 """-m gpu: the actuator network inside the HIP engine, in both of its arithmetic forms -- layer 2 on split-f16 operands (default) and the
 exact f32 MFMA chain (MQE_ACT_F32=1, or a network whose layer-2 weights do not fit the f16 planes) -- against the float64 reference of
 tests/actuator_ref.py, the staged kernel (k_compute_torques_mfma) against the fused one (k_substeps) for every compiled variant, and the
-f32 variants against the oracle.  Every engine is built under MQE_VERBOSE, and the variant line of mqe_sim_create says which kernel ran."""
+f32 variants against the oracle; the P / V / T law likewise, fused against staged.  Every engine is built under MQE_VERBOSE, and the variant line of mqe_sim_create says which kernel ran."""
 import numpy as np
 import pytest
 import torch
@@ -220,6 +220,51 @@ def test_fused_equals_staged_bit_for_bit(monkeypatch, capfd, vid, task, N, env, 
         assert (var["shape"], int(var["epw"]), var["actuator"]) == (shape, epw, "f32" if act_f32 else "f16"), var
         if epw == 2:           # the post-physics epilogue fused into the two-envs-per-wavefront kernel
             assert var["post"] == "fused", var
+
+
+PD_SHAPES = [("go1gate", 5, {}, 1),                                    # 24 joints per env: one pass of the 64-lane joint loop
+             ("go1football-2vs2", 3, {}, 1),                           # 48 joints per env, the generic shape
+             ("go1plane", 3, {"MQE_ENVS_PER_WAVE": "2"}, 2)]           # the odd batch leaves a half-wave without an env
+
+
+@pytest.mark.parametrize("ctrl", ["P", "V", "T"])
+@pytest.mark.parametrize("task,N,env,epw", PD_SHAPES, ids=[s[0] for s in PD_SHAPES])
+def test_fused_pd_law_equals_staged_bit_for_bit(monkeypatch, capfd, task, N, env, epw, ctrl):
+    """control types P / V / T are one function (kernels_step.hpp joint_pd_torque) with two callers: engine A runs step_joint(a) -- the head
+    of k_substeps' substep 0; engine B, from the same desc and the same controlled "wide" state, gets A's clipped actions and runs
+    compute_torques() -- k_compute_torques.  A's substep-0 torques == B's torques bit for bit in the envs A did not reset (>= 90 %)."""
+    def tweak(d):
+        d.control_type = abi.CTRL[ctrl]
+    # V once more with the wide state's speeds / 256: the D term on (qd - 0) / dt puts all but ~1 % of the wide state's torques at the limit
+    for state, qd_scale in (("wide", 1.0),) + ((("wide-slow", 2.0 ** -8),) if ctrl == "V" else ()):
+        eA, d, var = variant_engine(monkeypatch, capfd, task, N, env, tweak=tweak)
+        eB, _, varB = variant_engine(monkeypatch, capfd, task, N, env, tweak=tweak)
+        assert var == varB and int(var["epw"]) == epw, (var, varB)
+        A = d.num_agents
+        dof = _controlled_state(d, "wide")[0].copy()
+        dof[..., 1] *= np.float32(qd_scale)
+        for e in (eA, eB):
+            e.reset_all()
+            e.tensor(abi.T_DOF_STATE)[:, :12 * A].copy_(torch.from_numpy(dof))
+        g = torch.Generator().manual_seed(3)
+        a = ((torch.rand(N * A, 12, generator=g) * 2 - 1) * (1.0 if ctrl != "T" else 8.0)).cuda().contiguous()
+        eA.step_joint(a)
+        torch.cuda.synchronize()
+        eB.tensor(abi.T_ACTIONS).copy_(eA.tensor(abi.T_ACTIONS))
+        eB.compute_torques()
+        torch.cuda.synchronize()
+        keep = (eA.tensor(abi.T_RESET_BUF) == 0).cpu().numpy()
+        assert keep.mean() >= 0.9, f"{task} {ctrl} {state}: only {int(keep.sum())} of {N} envs stayed un-reset"
+        fused = eA.tensor(abi.T_SUBSTEP_TORQUES)[:, 0].cpu().numpy()[keep]
+        staged = eB.tensor(abi.T_TORQUES).cpu().numpy()[keep]
+        diff = fused.view(np.int32) != staged.view(np.int32)
+        assert not diff.any(), (f"{task} {ctrl} {state} {var}: fused substep-0 torques differ from k_compute_torques' in {int(diff.sum())} joints, "
+                                f"max |diff| {np.abs(fused - staged).max():.3e}")
+        _, lim, _ = _joints(d)
+        inside = float((np.abs(staged.reshape(-1)) < lim.reshape(N, -1)[keep].reshape(-1)).mean())
+        _record("pd_fused_staged", {"task": task, "N": N, "env": env, "ctrl": ctrl, "state": state, "variant": var, "envs_compared": int(keep.sum()),
+                                    "torques_inside_limit": inside})
+        eA.close(); eB.close()
 
 
 @pytest.mark.parametrize("vid,task,N,env,shape,epw,tweak", VARIANTS, ids=[v[0] for v in VARIANTS])
