@@ -33,7 +33,8 @@ extern "C" {
  * mqe_sim_create refuses a scene whose caps exceed 64; edge_contacts bit 8 + MQE_T_CONTACT_REDUCED (new tensor): optional manifold reduction of a
  * robot's one-sided contacts to its DEEPEST eight instead of the first eight in feature order.  v16 (round 6) over v15: mqe_debug_epilogue_times
  * (new export).  v17 over v16: MQE_T_RIGID_BODY_STATE (new tensor kind before MQE_T_COUNT), mqe_refresh_rigid_body_state and
- * mqe_set_rigid_body_refresh (new exports). */
+ * mqe_set_rigid_body_refresh (new exports).  v17, additive (no bump: no limit of mqe_abi_limits, tensor kind, descriptor field or existing call
+ * changes): mqe_measure_heights and mqe_set_height_refresh (new exports), MQE_MAX_HEIGHT_POINTS, MQE_HSCAN_SCENERY. */
 #define MQE_ABI_VERSION 17
 #define MQE_MAX_SPHERES 64    /* feature points of one robot (the capsule model has 32, the exact one 60) */
 #define MQE_MAX_PRIMS 20      /* collision primitives of one robot (Go1: 18) */
@@ -47,6 +48,8 @@ extern "C" {
 #define MQE_HIST 30       /* frames of history fed to the locomotion policy (go1.py:395) */
 #define MQE_MAX_LAYERS 6
 #define MQE_MAX_REWARD_TERMS 12
+#define MQE_MAX_HEIGHT_POINTS 1024   /* grid points of one robot's terrain height scan (mqe_measure_heights; the shipped 17 x 11 grid: 187) */
+#define MQE_HSCAN_SCENERY 1          /* mqe_measure_heights flag: the tops of the static scenery boxes count as surface */
 
 /* tasks whose wrapper observation / reward are evaluated in-kernel (reference mqe/envs/wrappers) */
 enum { MQE_TASK_PLAIN = 0, MQE_TASK_GATE = 1, MQE_TASK_SHEEP = 2, MQE_TASK_SEESAW = 3, MQE_TASK_FOOTBALL_DEFENDER = 4, MQE_TASK_PUSHBOX = 5,
@@ -435,6 +438,39 @@ int mqe_refresh_rigid_body_state(mqe_sim* s, void* stream);
  * post-physics step as a launch of its own instead of the physics kernel's epilogue (the same arithmetic).  0 (the default): no step
  * launches it.  mqe_reset_all and mqe_state_load never refresh it.  Host-side switch; not inside an open step. */
 int mqe_set_rigid_body_refresh(mqe_sim* s, int on);
+
+/* legged_gym's measured_heights (legged_robot.py:1047-1061 _init_height_points, :1094-1097 _reward_base_height, go1.py:235-236): the height of
+ * the static surface under a yaw-aligned grid of points around every robot's base.  UNPINNED: upstream's own _get_heights is absent from the
+ * reference snapshot and its call site is commented out, so no reference program fixes the numbers; the meaning is the published legged_gym
+ * one, on the surface THIS engine's physics collides with.  Specification (tests/height_ref.py restates it in float64; csrc/kernels_terrain_scan.hpp):
+ *   grid      points_xy [n_points][2] base-frame offsets; for cfg.terrain.measured_points_x / _y point i * len(y) + j = (x[i], y[j]) (x-major,
+ *             torch.meshgrid flattened); 1 <= n_points <= MQE_MAX_HEIGHT_POINTS.
+ *   point     world (x, y) of robot r, point p = root_xy + Rz (px, py); Rz = upstream's quat_apply_yaw (mqe/utils/math.py:38-42), the rotation
+ *             of the normalised quaternion (0, 0, qz, qw) of the base: cos = (qw^2 - qz^2) / (qz^2 + qw^2), sin = 2 qw qz / (qz^2 + qw^2) -- the
+ *             twist about z, not the Euler yaw of a tilted body; identity when qz^2 + qw^2 < 1e-18.
+ *   height    H(x, y) = world z of the static surface, by the conventions of the physics' terrain test: fx = clamp(x / hs, 0, nx - 1) (as
+ *             fmin(fmax(v, 0), limit): a NaN lands on 0), ix = min((int)fx, nx - 2), tx = fx - ix, y likewise; g = ground_z + the bilinear sample
+ *             of ground_height (scenes with a relief); s = the bilinear sample of wall_sdf; s <= 0 (inside a wall footprint): H = max(g, top),
+ *             top = wall_top[tx < 0.5 ? ix : ix + 1][ty < 0.5 ? iy : iy + 1] or wall_height without that map, a world z as the physics
+ *             compares it; otherwise H = g.
+ *   flags     MQE_HSCAN_SCENERY: each static scenery box (MQE_NPC_STATIC scenes: bridge, wrestling ring; world-aligned, centred at the NPC
+ *             root + static_box_center) whose footprint |x - cx| <= hx, |y - cy| <= hy holds the point raises H to max(H, cz + hz).  Off (the
+ *             default, upstream's meaning): terrain only.  Robots, free NPCs and the 1-dof link are never seen.
+ *   output    out_dev [R][n_points] device floats (R = num_envs * num_agents; caller-owned, 4-byte alignment suffices), ABSOLUTE world heights:
+ *             what _reward_base_height subtracts from root_states[:, 2].
+ * mqe_measure_heights: from the CURRENT root state, one launch on `stream`.  points_xy is a HOST pointer; the handle keeps device copies of
+ * the grid it was last given (one for this call, one for the registered scan) and uploads only when the grid changes (that upload
+ * synchronises the device).  Cost on one MI355X (profiles/height_scan.txt): k_height_scan 7.9 us at 4096 envs x 2 x 187 points, 17.8 us at
+ * 16384; registered, a go1gate 4096 x 2 step takes 0.1943 -> 0.2041 ms (+5.0 %, most of it the given-up epilogue, as with the rigid-body
+ * refresh); nothing registered: the parent's launches and step time (0.1940 vs 0.1939 ms, inside the box-to-box spread). */
+int mqe_measure_heights(mqe_sim* s, float* out_dev, const float* points_xy, int n_points, int flags, void* stream);
+/* registers (out_dev != NULL) or drops (out_dev == NULL; the other arguments are then ignored) the scan that every post-physics step
+ * refreshes first -- after the last substep, before termination, the NPC script and the resets (an env reset in that step shows the
+ * heights under its terminal pose), where mqe_set_rigid_body_refresh's launch sits and in the same calls.  While a scan is registered a
+ * fused step runs its post-physics step as a launch of its own instead of the physics kernel's epilogue (the same arithmetic).  Nothing is
+ * registered by default: no step launches it.  out_dev must stay valid until the scan is dropped or the handle destroyed.  mqe_reset_all and
+ * mqe_state_load never refresh it; derived data, not part of mqe_state_save's blob.  Host-side switch; not inside an open step. */
+int mqe_set_height_refresh(mqe_sim* s, float* out_dev, const float* points_xy, int n_points, int flags);
 
 /* After host writes into MQE_T_HISTORY (obs_history of the reference, go1.py:102,145): rebuilds what the engine derives from the ring --
  * the compact split-f16 operand of layer 0, the presence flags (a frame of 70 zeros is absent), the carrier columns, the continuity

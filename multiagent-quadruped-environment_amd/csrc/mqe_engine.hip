@@ -17,6 +17,7 @@
 #include "kernels_physics.hpp"
 #include "kernels_camera.hpp"
 #include "kernels_bodies.hpp"
+#include "kernels_terrain_scan.hpp"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, const char* a = "") {
@@ -108,6 +109,11 @@ struct mqe_sim {
   float* rbs = nullptr;
   bool rbs_refresh = false;           // mqe_set_rigid_body_refresh: every post-physics step refreshes it first
   RbsArgs rbs_args;
+  // terrain height scan (kernels_terrain_scan.hpp): derived data as well.  The handle's device copies of the grid, [0] mqe_measure_heights',
+  // [1] the registered scan's, each with the host values it holds (uploaded only when they change)
+  struct HscanGrid { float* dev = nullptr; std::vector<float> host; } hscan_grid[2];
+  bool hscan_refresh = false;         // mqe_set_height_refresh: every post-physics step refreshes hscan_args.out first
+  HscanArgs hscan_args;
   // profiling
   bool prof = false, prof_now = false;   // prof_now: this call is one of the sampled ones
   int step_open = 0;                     // 0: no step in flight; 1: after mqe_step_head; 2: after mqe_step_tail / mqe_step_begin (mqe_step_end closes)
@@ -855,6 +861,43 @@ static void launch_rbs(mqe_sim* s, hipStream_t q) {
   hipLaunchKernelGGL(k_rigid_body_state, dim3((s->N + s->rbs_args.epg - 1) / s->rbs_args.epg), dim3(RBS_THREADS), 0, q, s->dm, s->st, s->rbs_args);
 }
 
+// ---- terrain height scan ----------------------------------------------------------------------------------------------------
+static int hscan_check(mqe_sim* s, const float* points_xy, int n_points, int flags, const char* who) {
+  if (!points_xy) return fail(-1, "%s: null points_xy", who);
+  if (n_points < 1 || n_points > MQE_MAX_HEIGHT_POINTS) return fail(-6, "%s: n_points out of range (1 .. MQE_MAX_HEIGHT_POINTS = 1024)", who);
+  if (flags & ~MQE_HSCAN_SCENERY) return fail(-2, "%s: unknown flag bits (MQE_HSCAN_SCENERY is the only one)", who);
+  if (s->hm.sdf_nx < 2 || s->hm.sdf_ny < 2) return fail(-4, "%s: the terrain raster has fewer than 2 x 2 points", who);
+  return 0;
+}
+// the launch constants of a scan of n points into `out` through grid copy `slot`; uploads the grid when it differs from the copy held
+static int hscan_prepare(mqe_sim* s, int slot, float* out, const float* points_xy, int n, int flags, HscanArgs* ha) {
+  mqe_sim::HscanGrid& g = s->hscan_grid[slot];
+  if (!g.dev && dalloc(s, &g.dev, (size_t)MQE_MAX_HEIGHT_POINTS * 2)) return fail(-5, "device alloc failed (height scan grid)");
+  if (g.host.size() != (size_t)n * 2 || memcmp(g.host.data(), points_xy, (size_t)n * 8) != 0) {
+    HIPCHK(hipDeviceSynchronize());            // a scan in flight may still read the copy
+    HIPCHK(hipMemcpy(g.dev, points_xy, (size_t)n * 8, hipMemcpyHostToDevice));
+    g.host.assign(points_xy, points_xy + (size_t)n * 2);
+  }
+  // robots per workgroup: the fewest whose elements leave at most 2 % of the workgroup's last pass idle, else the best there is
+  int rpg = 1;
+  float best = 2.0f;
+  for (int k = 1; k <= HSCAN_MAX_RPG; k++) {
+    const int el = k * n, cap = rup(el, HSCAN_THREADS);
+    const float idle = (float)(cap - el) / (float)cap;
+    if (idle < best) { best = idle; rpg = k; }
+    if (idle <= 0.02f) break;
+  }
+  const DevModel& m = s->hm;
+  ha->out = out; ha->pts = g.dev; ha->root = s->st.root; ha->P = n; ha->rpg = rpg; ha->flags = flags;
+  ha->ground_height = m.ground_height; ha->wall_sdf = m.wall_sdf; ha->wall_top = m.wall_top;
+  ha->nx = m.sdf_nx; ha->ny = m.sdf_ny; ha->hs = m.hs; ha->ground_z = m.ground_z; ha->wall_height = m.wall_height;
+  ha->magic = n == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)n + 1);
+  return 0;
+}
+static void launch_hscan(mqe_sim* s, const HscanArgs& ha, hipStream_t q) {
+  hipLaunchKernelGGL(k_height_scan, dim3((s->R + ha.rpg - 1) / ha.rpg), dim3(HSCAN_THREADS), 0, q, s->dm, ha);
+}
+
 extern "C" int mqe_sim_tensor(mqe_sim* s, int kind, mqe_tensor_view* v) {
   if (!s || !v || kind < 0 || kind >= MQE_T_COUNT) return fail(-1, "bad tensor kind");
   memset(v, 0, sizeof *v);
@@ -1100,9 +1143,9 @@ static int run_substeps_and_post(mqe_sim* s, hipStream_t q, int wrapper_level = 
     // decimation loop in one launch: state stays in LDS; actuator net on MFMA (C) or the PD / torque law (P, V, T) inside the wavefront
     ProfScope ps(s, PROF_SIMULATE, q);
     PostArgs pa = {0, 0, 0, 0};
-    // with the per-step rigid-body refresh on, the refresh sits between the physics and the post-physics step: the separate
+    // with the per-step rigid-body refresh on (or a height scan registered), the refresh sits between the physics and the post-physics step: the separate
     // post-physics launch then (the one MQE_NO_FUSE_POST selects), never the epilogue
-    const bool fuse_post = s->fuse_post && !s->rbs_refresh;
+    const bool fuse_post = s->fuse_post && !s->rbs_refresh && !s->hscan_refresh;
     if (fuse_post) {                           // the post-physics step rides along as the kernel's epilogue
       const PostStep p = begin_post_step(s);
       pa.on = 1; pa.wrapper_level = wrapper_level; pa.step_no = p.step_no; pa.push_count = p.push_count;
@@ -1121,6 +1164,7 @@ static int run_substeps_and_post(mqe_sim* s, hipStream_t q, int wrapper_level = 
     }
   }
   if (s->rbs_refresh) launch_rbs(s, q);       // rigid-body state after the last substep, before termination and reset (legged_robot_field.py:117-119)
+  if (s->hscan_refresh) launch_hscan(s, s->hscan_args, q);      // measured_heights at the same point (go1.py:235-236, _post_physics_step_callback)
   launch_post(s, q, wrapper_level);
   s->prof_now = s->prof;                      // the unfused entry points are always bracketed when profiling is on
   return launched();
@@ -1189,6 +1233,26 @@ extern "C" int mqe_set_rigid_body_refresh(mqe_sim* s, int on) {
   if (s->step_open) return fail(-8, "mqe_set_rigid_body_refresh inside an open step");
   if (on) { if (int rc = rbs_alloc(s)) return rc; }
   s->rbs_refresh = on != 0;
+  return 0;
+}
+extern "C" int mqe_measure_heights(mqe_sim* s, float* out_dev, const float* points_xy, int n_points, int flags, void* stream) {
+  if (!s) return fail(-1, "null engine handle");
+  if (!out_dev) return fail(-1, "mqe_measure_heights: null out_dev");
+  if (int rc = hscan_check(s, points_xy, n_points, flags, "mqe_measure_heights")) return rc;
+  HscanArgs ha;
+  if (int rc = hscan_prepare(s, 0, out_dev, points_xy, n_points, flags, &ha)) return rc;
+  launch_hscan(s, ha, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? 0 : fail(-4, "k_height_scan launch failed");
+}
+extern "C" int mqe_set_height_refresh(mqe_sim* s, float* out_dev, const float* points_xy, int n_points, int flags) {
+  if (!s) return fail(-1, "null engine handle");
+  if (s->step_open) return fail(-8, "mqe_set_height_refresh inside an open step");
+  if (!out_dev) { s->hscan_refresh = false; return 0; }
+  if (int rc = hscan_check(s, points_xy, n_points, flags, "mqe_set_height_refresh")) return rc;
+  HscanArgs ha;
+  if (int rc = hscan_prepare(s, 1, out_dev, points_xy, n_points, flags, &ha)) return rc;
+  s->hscan_args = ha;
+  s->hscan_refresh = true;
   return 0;
 }
 extern "C" int mqe_history_sync(mqe_sim* s, void* stream) {
@@ -1260,6 +1324,7 @@ extern "C" int mqe_post_decimation_step(mqe_sim* s, int dec_i, void* stream) {
 extern "C" int mqe_post_physics_step(mqe_sim* s, void* stream) {
   if (!s) return fail(-1, "null engine handle");
   if (s->rbs_refresh) launch_rbs(s, (hipStream_t)stream);
+  if (s->hscan_refresh) launch_hscan(s, s->hscan_args, (hipStream_t)stream);
   launch_post(s, (hipStream_t)stream, 0);
   return launched();
 }
@@ -1269,6 +1334,7 @@ extern "C" int mqe_post_physics_stage(mqe_sim* s, int stages, void* stream) {
   hipStream_t q = (hipStream_t)stream;
   const PostStep p = begin_post_step(s, (stages & MQE_POST_WRAPPER) != 0);
   if ((stages & MQE_POST_FRAME) && s->rbs_refresh) launch_rbs(s, q);      // after the last substep, before termination and reset
+  if ((stages & MQE_POST_FRAME) && s->hscan_refresh) launch_hscan(s, s->hscan_args, q);
   if (stages & MQE_POST_RESET) launch_curriculum_snapshot(s, q);
   hipLaunchKernelGGL(k_post_staged, dim3((s->N + 63) / 64), dim3(64), 0, q, s->dm, s->st, stages & MQE_POST_ALL, (stages & MQE_POST_WRAPPER_LEVEL) ? 1 : 0, p.push_count, p.step_no);
   return launched();

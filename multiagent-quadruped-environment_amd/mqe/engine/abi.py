@@ -8,6 +8,7 @@ MAX_PRIMS = 20
 PRIM_SPHERE, PRIM_CAPSULE, PRIM_BOX = 0, 1, 2
 MAX_AGENTS, MAX_NPCS, FRAME, HIST, MAX_LAYERS, MAX_REWARD_TERMS = 4, 16, 72, 30, 6, 12
 OBS_BAG = 74
+MAX_HEIGHT_POINTS, HSCAN_SCENERY = 1024, 1      # mqe_measure_heights: grid points per robot, the scenery flag
 
 TASK = dict(plain=0, gate=1, sheep=2, seesaw=3, football_defender=4, pushbox=5, rotation=6, bridge=7, wrestling=8, tug=9)
 NPC = dict(none=0, ball=1, sheep=2, seesaw=3, box=4, rotation=3, bridge=5, wrestling=5, circular=3)     # the revolving door shares the seesaw's fixed-base + 1-dof-link structure

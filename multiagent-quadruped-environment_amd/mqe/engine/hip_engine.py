@@ -178,6 +178,52 @@ class HipEngine(EngineBase):
         (mqe_set_rigid_body_refresh); off (the default): no step touches it"""
         self._call("set_rigid_body_refresh", int(bool(on)))
 
+    def _height_grid(self, points_xy):
+        """(P, 2) base-frame offsets -> contiguous float32 host array (mqe_measure_heights' points_xy)"""
+        if isinstance(points_xy, torch.Tensor):
+            points_xy = points_xy.detach().cpu().numpy()
+        pts = np.ascontiguousarray(points_xy, np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 2:
+            raise ValueError(f"points_xy must be (P, 2) base-frame offsets, got {pts.shape}")
+        return pts
+
+    def _height_call(self, name, out, pts, scenery, *tail):
+        f = getattr(self.lib, "mqe_" + name)
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * len(tail)
+        f.restype = C.c_int
+        rc = f(self.h, C.c_void_p(out.data_ptr() if out is not None else None), C.c_void_p(pts.ctypes.data if pts is not None else None),
+               int(pts.shape[0]) if pts is not None else 0, abi.HSCAN_SCENERY if scenery else 0, *tail)
+        if rc != 0:
+            raise RuntimeError(f"mqe_{name} failed ({rc}): {self.lib.mqe_last_error().decode()}")
+
+    def measure_heights(self, points_xy, out=None, scenery=False):
+        """(R, P) device tensor: the height of the static surface under the yaw-aligned grid `points_xy` ((P, 2) base-frame offsets) around
+        every robot, from the current root state, absolute world z (mqe_measure_heights).  scenery: the static scenery boxes' tops count.
+        `out`: a float32 device tensor of R * P contiguous elements to fill (4-byte alignment suffices)"""
+        pts = self._height_grid(points_xy)
+        R = self.desc.num_envs * self.desc.num_agents
+        if out is None:
+            out = torch.empty(R, pts.shape[0], dtype=torch.float32, device=self.torch_device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == R * pts.shape[0]
+        self._height_call("measure_heights", out, pts, scenery, self._stream())
+        return out
+
+    def set_height_refresh(self, points_xy, scenery=False):
+        """registers the scan every post-physics step refreshes first -- after the physics, before termination and resets
+        (mqe_set_height_refresh) -- and returns the live (R, P) tensor the engine object owns; None drops it (no step launches it: the default)"""
+        if points_xy is None:
+            self._height_call("set_height_refresh", None, None, False)
+            self._height_live = None
+            return None
+        pts = self._height_grid(points_xy)
+        R = self.desc.num_envs * self.desc.num_agents
+        live = getattr(self, "_height_live", None)
+        if live is None or live.shape != (R, pts.shape[0]):
+            live = torch.zeros(R, pts.shape[0], dtype=torch.float32, device=self.torch_device)
+        self._height_call("set_height_refresh", live, pts, scenery)
+        self._height_live = live
+        return live
+
     def history_sync(self):
         """after writing tensor(T_HISTORY): the compact layer-0 operand is rebuilt from the ring (mqe_history_sync)"""
         self._call("history_sync", self._stream())

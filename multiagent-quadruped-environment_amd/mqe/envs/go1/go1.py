@@ -264,6 +264,63 @@ class Go1:
             self._rigid_body_states = t
         return t
 
+    # ---- terrain height scan (legged_robot.py:1047-1061,1094-1097; go1.py:235-236) ---------------------------------------------------
+    def _height_grid(self):
+        """(grid_x, grid_y) of cfg.terrain.measured_points_x / _y, flattened x-major as _init_height_points does (host tensors)"""
+        g = getattr(self, "_height_grid_xy", None)
+        if g is None:
+            x = torch.tensor(self.cfg.terrain.measured_points_x, dtype=torch.float32)
+            y = torch.tensor(self.cfg.terrain.measured_points_y, dtype=torch.float32)
+            gx, gy = torch.meshgrid(x, y, indexing="ij")
+            g = self._height_grid_xy = torch.stack([gx.flatten(), gy.flatten()], dim=1).contiguous()
+        return g
+
+    @property
+    def num_height_points(self):
+        return self._height_grid().shape[0]
+
+    @property
+    def height_points(self):
+        """(N*A, P, 3) the points at which the heights are sampled, in the base frame, z = 0 (_init_height_points, legged_robot.py:1047-1061);
+        built when first read, on any engine"""
+        p = getattr(self, "_height_points", None)
+        if p is None:
+            g = self._height_grid().to(self.engine.torch_device)
+            p = torch.zeros(self.num_envs * self.num_agents, g.shape[0], 3, device=g.device)
+            p[:, :, :2] = g
+            self._height_points = p
+        return p
+
+    def _height_scan_engine(self, what):
+        if not self.cfg.terrain.measure_heights:
+            raise RuntimeError(f"{what} needs cfg.terrain.measure_heights = True (it is False in this config)")
+        e = self.engine
+        if not hasattr(e, "measure_heights"):
+            raise NotImplementedError(f"{what} is computed by the HIP engine (mqe.engine.hip_engine.HipEngine, mqe_measure_heights); "
+                                      f"{type(e).__name__} has no terrain height scan")
+        return e
+
+    def _get_heights(self, env_ids=None):
+        """(N*A, P) terrain heights under height_points around every robot, fresh from the CURRENT state (one launch; upstream's
+        _get_heights is absent from the reference: the published legged_gym meaning, include/mqe_hip.h mqe_measure_heights), absolute
+        world z.  env_ids: the rows (of root_states) to return"""
+        h = self._height_scan_engine("_get_heights").measure_heights(self._height_grid())
+        return h if env_ids is None else h[env_ids]
+
+    @property
+    def measured_heights(self):
+        """(N*A, P) live view of the engine's height scan, the same object on every access: what _reward_base_height subtracts from
+        root_states[:, 2] (legged_robot.py:1094-1097).  The first access registers the scan and refreshes once; from then on every step
+        refreshes it after the physics, before termination and resets (mqe_set_height_refresh), where upstream's
+        _post_physics_step_callback measures (go1.py:235-236).  Until it is read no step pays for it."""
+        t = getattr(self, "_measured_heights", None)
+        if t is None:
+            e = self._height_scan_engine("measured_heights")
+            t = e.set_height_refresh(self._height_grid())
+            e.measure_heights(self._height_grid(), out=t)
+            self._measured_heights = t
+        return t
+
     @property
     def root_states_npc(self):
         return self._root3[:, self.num_agents:, :].reshape(-1, 13)
