@@ -429,6 +429,62 @@ int mqe_step_joint(mqe_sim* s, const float* actions12, void* stream);
 int mqe_render_depth(mqe_sim* s, float* out_dev, int height, int width, float horizontal_fov_deg, const float* cam_pos3, const float* cam_rpy3,
                      float far_m, void* stream);
 
+/* Episode recording: one image of ONE env from a free camera (upstream's FloatingCameraSensor on env 0, mqe/utils/helpers.py:276-298:
+ * create_camera_sensor, set_camera_location(pos, lookat), get_camera_image(IMAGE_COLOR); state machine legged_robot.py:916-957).  Isaac Gym's
+ * rasteriser is closed, so pixels cannot be matched: like the depth camera this is a ray caster over the collision geometry
+ * (csrc/kernels_view.hpp, k_view), and this comment is its specification.
+ *   camera    mqe_render_depth's conventions: the camera looks along its +x, +y is its left, +z up; pixel (0, 0) is top-left;
+ *             yc = -(2 (j + 0.5) / W - 1) tan(hfov / 2), zc = -(2 (i + 0.5) / H - 1) tan(hfov / 2) H / W; the ray d = f + yc l + zc u is
+ *             NOT normalised, so its parameter t is the depth along the optical axis.  The basis comes from (eye, lookat), world points
+ *             (env frames coincide with the world, legged_robot.py:834-835), built on the host in double: f = normalize(lookat - eye),
+ *             l = normalize(z_world x f), u = f x l; when f is within 1e-6 of vertical, l = (0, 1, 0).
+ *   surfaces  what mqe_render_depth sees, by its rules -- the slab or the relief marched in half cells and bisected six times, the wall
+ *             march over the SDF (wall_top / wall_height, 400 steps at most), free NPCs as spheres or the box, the 1-dof link scene's base
+ *             and link (the cylinder as a capsule), the scenery boxes -- and EVERY robot of the env: no own-robot exclusion.  A hit needs
+ *             t > 1e-4; an eye inside a shape sees nothing of it.
+ *   normal    of the nearest surface at the hit point, world frame, turned to face the eye (n . d <= 0).  Sphere: (p - c) / r.  Capsule: p
+ *             minus the closest point of its segment, normalised.  Box: the axis of the face the entry slab belongs to.  Slab: (0, 0, 1).
+ *             Relief: normalize(-gx, -gy, 1), (gx, gy) the gradient of the bilinear sample at the hit point.  Wall: (0, 0, 1) when the hit
+ *             lies within 1 mm of the wall's top, else the normalised horizontal gradient of the bilinear SDF sample ((1, 0, 0) where
+ *             that gradient vanishes).
+ *   id        int32 word: bits 0-7 class (MQE_VIEW_*: 0 nothing, 1 ground, 2 wall, 3 robot, 4 free NPC, 5 1-dof scene, 6 scenery box);
+ *             bits 8-15 robot / NPC / box index; bits 16-23 part: the robot's primitive index (mqe_robot_model::prim_*), for class 5
+ *             0 = base, 1 = link; bit 24, ground only: parity of floor(x) + floor(y) of the hit point, a 1 m checker that makes motion
+ *             over flat ground visible.
+ *   colour    a pure function of (id word, normal): channel c = (uint8)(255 min(1, albedo_c (MQE_VIEW_AMBIENT + MQE_VIEW_DIFFUSE
+ *             max(0, n . L))) + 0.5), L = MQE_VIEW_LIGHT (unit); albedo = the class's row of MQE_VIEW_PALETTE (robot r: row 2 + r % 4),
+ *             the ground's times 1 + MQE_VIEW_CHECKER where bit 24 is set and 1 - MQE_VIEW_CHECKER where it is not; a miss gets
+ *             MQE_VIEW_SKY.  Alpha is always 255.
+ *   outputs   device pointers, each written only if non-null.  rgba_dev: uint8 [H][W][4], Isaac Gym's IMAGE_COLOR layout after upstream's
+ *             reshape (helpers.py:296-298); 4-byte aligned (one store per pixel).  geom_dev: float [H][W][4] = the axial depth in
+ *             IMAGE_DEPTH's convention (negative; the bit pattern of -inf on a miss, as mqe_render_depth writes it), then the normal (zero
+ *             on a miss); 16-byte aligned (one store per pixel).  id_dev: int32 [H][W].
+ * Renders from the CURRENT state with one launch on `stream`: allocates nothing, does not synchronise, reads state only.  eye3 / lookat3
+ * are host pointers.  Refused with a negative code and a message, without a launch: null handle (-1); all three outputs null, null eye3
+ * / lookat3 (-1); env outside [0, num_envs), height or width <= 0, height * width > MQE_VIEW_MAX_PIXELS, fov outside (1, 179), far_m <= 0,
+ * |lookat - eye| < 1e-6, a misaligned output (-6); inside an open step (-8).
+ * Mapping and cost (profiles/view_render.txt): 16 x 16-pixel tiles, one 256-thread workgroup each, a wavefront = an 8 x 8 block. */
+#define MQE_VIEW_MAX_PIXELS (1 << 20)
+#define MQE_VIEW_NONE 0
+#define MQE_VIEW_GROUND 1
+#define MQE_VIEW_WALL 2
+#define MQE_VIEW_ROBOT 3
+#define MQE_VIEW_NPC 4
+#define MQE_VIEW_LINK_SCENE 5
+#define MQE_VIEW_SCENERY 6
+#define MQE_VIEW_ID(cls, index, part) ((cls) | ((index) << 8) | ((part) << 16))
+#define MQE_VIEW_CHECKER_BIT (1 << 24)
+#define MQE_VIEW_AMBIENT 0.35f
+#define MQE_VIEW_DIFFUSE 0.65f
+#define MQE_VIEW_CHECKER 0.08f
+#define MQE_VIEW_LIGHT {0.36f, 0.48f, 0.80f}
+#define MQE_VIEW_SKY {135, 190, 235}
+#define MQE_VIEW_PALETTE_ROWS 9          /* ground, wall, robots 0-3, free NPC, 1-dof scene, scenery box */
+#define MQE_VIEW_PALETTE {{0.55f, 0.58f, 0.50f}, {0.72f, 0.68f, 0.60f}, {0.85f, 0.25f, 0.20f}, {0.20f, 0.40f, 0.85f}, {0.95f, 0.75f, 0.15f}, \
+                          {0.25f, 0.70f, 0.35f}, {0.92f, 0.90f, 0.82f}, {0.60f, 0.42f, 0.25f}, {0.50f, 0.50f, 0.58f}}
+int mqe_render_view(mqe_sim* s, int env, uint8_t* rgba_dev, float* geom_dev, int32_t* id_dev, int height, int width,
+                    float horizontal_fov_deg, const float* eye3, const float* lookat3, float far_m, void* stream);
+
 /* gym.refresh_rigid_body_state_tensor (legged_robot_field.py:117-119): MQE_T_RIGID_BODY_STATE from the CURRENT root and dof state.
  * Enqueued on `stream`. */
 int mqe_refresh_rigid_body_state(mqe_sim* s, void* stream);

@@ -10,8 +10,12 @@
 // follows from the aspect ratio.  Known answers: tests/test_camera_gpu.py.
 // One 256-thread workgroup per env: the link frames of its robots by forward kinematics into LDS, the primitives in world coordinates
 // behind them, then thread = pixel, looping over the env's cameras.
+// The rules -- the staging of an env, the ground, the wall march, the bodies -- are __device__ functions that k_view (kernels_view.hpp,
+// the free camera of episode recording) calls as well; they also report which surface was hit and its normal, which this kernel ignores.
+// Its images are bit for bit those of the kernel that held the rules inline (profiles/view_render.txt).
 #pragma once
 #include "mqe_common.hpp"
+#include "kernels_physics.hpp"      // map_sample_dev: the bilinear sample and its gradient
 
 struct CamArgs { float* out; int H, W; float tan_half_h; float pos[3]; float rpy[3]; float far_; };
 
@@ -113,15 +117,63 @@ __device__ __forceinline__ float ray_box(CV3 o, CV3 d, CV3 c, const float* R, CV
 
 #define CAM_LINK 12          // floats per link frame in LDS: R (9), origin (3)
 #define CAM_PRIM 16          // floats per primitive: type, link, radius, -, centre (3), -, half-axis / half extents (3), -, (4 spare)
-__global__ void __launch_bounds__(256) k_depth_camera(const DevModel* __restrict__ m, DevState st, CamArgs ca) {
-  __shared__ float s_link[MQE_MAX_AGENTS * MQE_NBODY * CAM_LINK];
-  __shared__ float s_prim[MQE_MAX_AGENTS * MQE_MAX_PRIMS * CAM_PRIM];
-  const int e = blockIdx.x, tid = threadIdx.x;
-  const int A = m->A, P = m->P, npr = m->robot.n_prims;
+#define CAM_LINK_FLOATS (MQE_MAX_AGENTS * MQE_NBODY * CAM_LINK)
+#define CAM_PRIM_FLOATS (MQE_MAX_AGENTS * MQE_MAX_PRIMS * CAM_PRIM)
+
+// ---- what both casters share (k_depth_camera below, k_view in kernels_view.hpp): one statement of every rule ---------------------------
+// The nearest hit of one ray so far: t (starts at `far`), the id word of the surface that set it (include/mqe_hip.h, MQE_VIEW_ID; 0 =
+// nothing) and that surface's outward normal at the hit point.  k_depth_camera reads t alone (id and n then cost nothing: they are dead).
+struct CamHit { float t; int id; CV3 n; };
+__device__ __forceinline__ CV3 cunit(CV3 v) { return (1.0f / sqrtf(cdot(v, v))) * v; }
+__device__ __forceinline__ void hit_sphere(CamHit& h, CV3 o, CV3 d, CV3 c, float r, int id) {
+  const float t = ray_sphere(o, d, c, r, h.t);
+  if (t < h.t) { h.t = t; h.id = id; h.n = cunit(o + t * d - c); }                 // (p - c) / r
+}
+__device__ __forceinline__ void hit_capsule(CamHit& h, CV3 o, CV3 d, CV3 c, CV3 u, float r, int id) {
+  const float t = ray_capsule(o, d, c, u, r, h.t);
+  if (t < h.t) {                                                                   // p minus the closest point of the segment
+    const CV3 p = o + t * d, pa = c - u, ba = 2.0f * u;
+    const float baba = cdot(ba, ba);
+    const float s = baba < 1e-12f ? 0.5f : clampf(cdot(p - pa, ba) / baba, 0.0f, 1.0f);
+    h.t = t; h.id = id; h.n = cunit(p - (pa + s * ba));
+  }
+}
+__device__ __forceinline__ void hit_box(CamHit& h, CV3 o, CV3 d, CV3 c, const float* R, CV3 hb, int id) {
+  const float t = ray_box(o, d, c, R, hb, h.t);
+  if (t < h.t) {                                                                   // the axis of the face the entry slab belongs to
+    const CV3 ol = cmulT(R, o - c), dl = cmulT(R, d);
+    const float oo[3] = {ol.x, ol.y, ol.z}, dv[3] = {dl.x, dl.y, dl.z}, hh[3] = {hb.x, hb.y, hb.z};
+    float tin = -3.0e38f, din = 1.0f;
+    int kin = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      if (fabsf(dv[k]) < 1e-9f) continue;
+      const float inv = 1.0f / dv[k];
+      const float ta = fminf((-hh[k] - oo[k]) * inv, (hh[k] - oo[k]) * inv);
+      if (ta > tin) { tin = ta; kin = k; din = dv[k]; }
+    }
+    const CV3 ax = kin == 0 ? cv(R[0], R[3], R[6]) : (kin == 1 ? cv(R[1], R[4], R[7]) : cv(R[2], R[5], R[8]));
+    h.t = t; h.id = id; h.n = (din > 0.0f ? -1.0f : 1.0f) * ax;
+  }
+}
+// true: no point of the ball (c, r) lies on the ray nearer than `best` (the eye outside it) -- what is inside the ball need not be tested
+__device__ __forceinline__ bool ray_clear_of_ball(CV3 o, CV3 d, CV3 c, float r, float best) {
+  const CV3 oc = o - c;
+  const float a = cdot(d, d), b = cdot(d, oc), cc = cdot(oc, oc) - r * r;
+  if (cc <= 0.0f) return false;
+  const float hq = b * b - a * cc;
+  if (hq < 0.0f || b > 0.0f) return true;
+  return -b - sqrtf(hq) >= best * a;
+}
+__device__ __forceinline__ int ground_id(CV3 p) {        // class ground + the 1 m checker: parity of floor(x) + floor(y) of the hit point
+  return MQE_VIEW_GROUND | ((((int)floorf(p.x) + (int)floorf(p.y)) & 1) << 24);
+}
+
+// The env's link frames (thread = (robot, body), walking its chain from the base: <= 3 joints) and, behind a barrier, its robots'
+// primitives in world coordinates, into LDS; a second barrier, then every thread may read both.  Called by all 256 threads.
+__device__ __forceinline__ void cam_stage_env(const DevModel* __restrict__ m, const float* root, const float* dof, float* s_link, float* s_prim, int tid) {
+  const int A = m->A, npr = m->robot.n_prims;
   const mqe_robot_model& rm = m->robot;
-  const float* root = st.root + (size_t)e * (A + P) * 13;
-  const float* dof = st.dof + (size_t)e * m->ND * 2;
-  // ---- link frames: thread = (robot, body), walking its chain from the base (<= 3 joints) -------------------------------------------
   if (tid < A * MQE_NBODY) {
     const int r = tid / MQE_NBODY, bb = tid - r * MQE_NBODY;
     float R[9];
@@ -132,7 +184,6 @@ __global__ void __launch_bounds__(256) k_depth_camera(const DevModel* __restrict
     L[9] = p.x; L[10] = p.y; L[11] = p.z;
   }
   __syncthreads();
-  // ---- the robots' primitives in world coordinates ----------------------------------------------------------------------------------
   if (tid < A * npr) {
     const int r = tid / npr, q = tid - r * npr;
     const int link = r * MQE_NBODY + rm.prim_body[q];
@@ -145,6 +196,156 @@ __global__ void __launch_bounds__(256) k_depth_camera(const DevModel* __restrict
     else { const CV3 u = cmul(L, cv(rm.prim_axis[q][0], rm.prim_axis[q][1], rm.prim_axis[q][2])); Q[8] = u.x; Q[9] = u.y; Q[10] = u.z; }
   }
   __syncthreads();
+}
+
+// ground: the slab plane, or the relief map marched in half cells and bisected.  STEP_BY_PRODUCT: march step k stands at t = k dt instead
+// of at the f32 sum of k steps.  The sum drifts by ~sqrt(k) ulp, which moves the bisection's grid of dt / 64 against the float64
+// specification's and puts ~0.2 % of a low camera's ground pixels one grid cell (2e-4 m at the shipped raster) off; the product does
+// not drift.  k_view marches by the product; k_depth_camera keeps the sum, and with it its images bit for bit.
+template <bool STEP_BY_PRODUCT>
+__device__ __forceinline__ void cam_ground(const DevModel* __restrict__ m, CV3 o, CV3 d, CamHit& h) {
+  const float hs = m->hs;
+  const int nx = m->sdf_nx, ny = m->sdf_ny;
+  if (m->ground_height == nullptr) {
+    if (d.z < -1e-9f) {
+      const float t = (m->ground_z - o.z) / d.z;
+      if (t > 1e-4f && t < h.t) { h.t = t; h.id = ground_id(o + t * d); h.n = cv(0.0f, 0.0f, 1.0f); }
+    }
+  } else {
+    const float dxy = sqrtf(d.x * d.x + d.y * d.y);
+    const float dt = dxy > 1e-6f ? 0.5f * hs / dxy : 0.05f;
+    auto hgt = [&](CV3 p) -> float {
+      float fx = fminf(fmaxf(p.x / hs, 0.0f), (float)(nx - 1)), fy = fminf(fmaxf(p.y / hs, 0.0f), (float)(ny - 1));
+      int ix = min((int)fx, nx - 2), iy = min((int)fy, ny - 2);
+      const float tx = fx - ix, ty = fy - iy;
+      const float* g = m->ground_height + (size_t)ix * ny + iy;
+      const float b0 = g[0] + (g[1] - g[0]) * ty, b1 = g[ny] + (g[ny + 1] - g[ny]) * ty;
+      return m->ground_z + b0 + (b1 - b0) * tx;
+    };
+    float tp = 0.0f;
+    int k = 1;
+    for (float t = dt; t < h.t; t = STEP_BY_PRODUCT ? (float)(++k) * dt : t + dt) {
+      const CV3 p = o + t * d;
+      if (p.z < hgt(p)) {
+        float lo = tp, hi = t;
+        for (int it = 0; it < 6; it++) { const float mid = 0.5f * (lo + hi); const CV3 pm = o + mid * d; if (pm.z < hgt(pm)) hi = mid; else lo = mid; }
+        // the normal: normalize(-gx, -gy, 1) from the bilinear sample's own gradient at the hit point
+        const CV3 ph = o + hi * d;
+        const float fx = fminf(fmaxf(ph.x / hs, 0.0f), (float)(nx - 1)), fy = fminf(fmaxf(ph.y / hs, 0.0f), (float)(ny - 1));
+        const int ix = min((int)fx, nx - 2), iy = min((int)fy, ny - 2);
+        float gx, gy;
+        map_sample_dev(m->ground_height + (size_t)ix * ny + iy, ny, fx - ix, fy - iy, hs, gx, gy);
+        h.t = hi; h.id = ground_id(ph); h.n = cunit(cv(-gx, -gy, 1.0f));
+        break;
+      }
+      tp = t;
+    }
+  }
+}
+
+// wall prisms: march over the signed-distance map of the wall set (a step never crosses more than the distance to the nearest wall)
+__device__ __forceinline__ void cam_walls(const DevModel* __restrict__ m, CV3 o, CV3 d, CamHit& h) {
+  const float hs = m->hs;
+  const int nx = m->sdf_nx, ny = m->sdf_ny;
+  const float dxy = sqrtf(d.x * d.x + d.y * d.y);
+  if (dxy > 1e-6f && m->wall_sdf != nullptr) {
+    float t = 1e-4f;
+    for (int it = 0; it < 400 && t < h.t; it++) {
+      const CV3 p = o + t * d;
+      const float fxr = p.x / hs, fyr = p.y / hs;
+      if (fxr < 0.0f || fyr < 0.0f || fxr > (float)(nx - 1) || fyr > (float)(ny - 1)) break;       // left the map
+      int ix = min((int)fxr, nx - 2), iy = min((int)fyr, ny - 2);
+      const float tx = fxr - ix, ty = fyr - iy;
+      const float* sd = m->wall_sdf + (size_t)ix * ny + iy;
+      const float a0 = sd[0] + (sd[1] - sd[0]) * ty, a1 = sd[ny] + (sd[ny + 1] - sd[ny]) * ty;
+      const float s = a0 + (a1 - a0) * tx;
+      if (s <= 0.002f) {                                     // on / inside a wall's footprint: below its top it is the wall
+        const float top = m->wall_top != nullptr ? m->wall_top[(size_t)(tx < 0.5f ? ix : ix + 1) * ny + (ty < 0.5f ? iy : iy + 1)] : m->wall_height;
+        if (p.z <= top && p.z >= m->ground_z - 1e-3f) {
+          // the normal: up within 1 mm of the wall's top, else the horizontal gradient of the bilinear SDF sample
+          float gx, gy;
+          map_sample_dev(sd, ny, tx, ty, hs, gx, gy);
+          float gl = sqrtf(gx * gx + gy * gy);
+          if (gl < 1e-6f) { gx = 1.0f; gy = 0.0f; gl = 1.0f; }
+          h.t = t; h.id = MQE_VIEW_WALL; h.n = top - p.z <= 1e-3f ? cv(0.0f, 0.0f, 1.0f) : cv(gx / gl, gy / gl, 0.0f);
+          break;
+        }
+        t += 0.25f * hs / dxy;                               // above it: the ray may still come down onto the top face
+      } else t += fmaxf(s, 0.002f) / dxy;
+    }
+  }
+}
+
+// everything that moves: the robots' primitives (robot `skip` left out: the onboard camera does not see its own robot; -1: none),
+// the free NPCs (ball, sheep: spheres in the body frame; the box), the 1-dof link's base and link, the scenery boxes.  A robot is
+// entered only if the ray meets the ball (base origin, feature_reach) nearer than the hit so far, a flock member likewise.
+__device__ __forceinline__ void cam_bodies(const DevModel* __restrict__ m, const float* root, const float* dof, const float* s_link, const float* s_prim,
+                                           CV3 o, CV3 d, int skip, CamHit& h) {
+  const int A = m->A, npr = m->robot.n_prims;
+  for (int r = 0; r < A; r++) {
+    if (r == skip) continue;
+    const float* B = s_link + (r * MQE_NBODY) * CAM_LINK;
+    if (ray_clear_of_ball(o, d, cv(B[9], B[10], B[11]), m->robot.feature_reach + 1e-3f, h.t)) continue;
+    for (int q = 0; q < npr; q++) {
+      const float* Q = s_prim + (r * npr + q) * CAM_PRIM;
+      const int type = (int)Q[0], id = MQE_VIEW_ID(MQE_VIEW_ROBOT, r, q);
+      const CV3 c = cv(Q[4], Q[5], Q[6]);
+      if (type == MQE_PRIM_BOX) hit_box(h, o, d, c, s_link + (int)Q[1] * CAM_LINK, cv(Q[8], Q[9], Q[10]), id);
+      else if (type == MQE_PRIM_CAPSULE) hit_capsule(h, o, d, c, cv(Q[8], Q[9], Q[10]), Q[2], id);
+      else hit_sphere(h, o, d, c, Q[2], id);
+    }
+  }
+  if (m->has_box) {
+    for (int p = 0; p < m->n_npc_dyn; p++) {
+      float Rb[9];
+      cquat(root + (A + p) * 13 + 3, Rb);
+      hit_box(h, o, d, cv(root[(A + p) * 13], root[(A + p) * 13 + 1], root[(A + p) * 13 + 2]), Rb, cv(m->npc_box_half[0], m->npc_box_half[1], m->npc_box_half[2]),
+              MQE_VIEW_ID(MQE_VIEW_NPC, p, 0));
+    }
+  } else {
+    const int ns = m->npc_n_spheres;
+    float reach = 0.0f;                                        // of one NPC's spheres about its origin
+    for (int k = 0; k < ns; k++) {
+      const float* sc = m->npc_sphere_center[k];
+      reach = fmaxf(reach, sqrtf(sc[0] * sc[0] + sc[1] * sc[1] + sc[2] * sc[2]) + m->npc_sphere_radius[k]);
+    }
+    for (int p = 0; p < m->n_npc_dyn; p++) {
+      const CV3 pb = cv(root[(A + p) * 13], root[(A + p) * 13 + 1], root[(A + p) * 13 + 2]);
+      if (ns > 1 && ray_clear_of_ball(o, d, pb, reach + 1e-3f, h.t)) continue;
+      float Rb[9];
+      cquat(root + (A + p) * 13 + 3, Rb);
+      for (int k = 0; k < ns; k++)
+        hit_sphere(h, o, d, pb + cmul(Rb, cv(m->npc_sphere_center[k][0], m->npc_sphere_center[k][1], m->npc_sphere_center[k][2])), m->npc_sphere_radius[k],
+                   MQE_VIEW_ID(MQE_VIEW_NPC, p, 0));
+    }
+  }
+  const float I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  if (m->has_seesaw) {
+    const CV3 sb = cv(root[A * 13], root[A * 13 + 1], root[A * 13 + 2]);
+    if (m->ss_base_half[0] > 0.0f) hit_box(h, o, d, sb, I3, cv(m->ss_base_half[0], m->ss_base_half[1], m->ss_base_half[2]), MQE_VIEW_ID(MQE_VIEW_LINK_SCENE, 0, 0));
+    CV3 piv = sb + cv(m->ss_joint_offset[0], m->ss_joint_offset[1], m->ss_joint_offset[2]);
+    const float th = dof[(12 * A) * 2];
+    float Rp[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (m->ss_axis == 3) piv.y += th; else caxis(m->ss_axis == 2 ? cv(0, 0, 1) : cv(0, 1, 0), th, Rp);
+    const CV3 pc = piv + cmul(Rp, cv(m->ss_plank_center[0], m->ss_plank_center[1], m->ss_plank_center[2]));
+    if (m->ss_link_cyl) hit_capsule(h, o, d, pc, cv(0, 0, fmaxf(m->ss_plank_half[2] - m->ss_plank_half[0], 0.0f)), m->ss_plank_half[0], MQE_VIEW_ID(MQE_VIEW_LINK_SCENE, 0, 1));      // upright cylinder ~ capsule
+    else hit_box(h, o, d, pc, Rp, cv(m->ss_plank_half[0], m->ss_plank_half[1], m->ss_plank_half[2]), MQE_VIEW_ID(MQE_VIEW_LINK_SCENE, 0, 1));
+  }
+  for (int bx = 0; bx < m->n_static; bx++) {
+    const CV3 nb = cv(root[A * 13], root[A * 13 + 1], root[A * 13 + 2]);
+    hit_box(h, o, d, nb + cv(m->sb_center[bx][0], m->sb_center[bx][1], m->sb_center[bx][2]), I3, cv(m->sb_half[bx][0], m->sb_half[bx][1], m->sb_half[bx][2]),
+            MQE_VIEW_ID(MQE_VIEW_SCENERY, bx, 0));
+  }
+}
+
+__global__ void __launch_bounds__(256) k_depth_camera(const DevModel* __restrict__ m, DevState st, CamArgs ca) {
+  __shared__ float s_link[CAM_LINK_FLOATS];
+  __shared__ float s_prim[CAM_PRIM_FLOATS];
+  const int e = blockIdx.x, tid = threadIdx.x;
+  const int A = m->A, P = m->P;
+  const float* root = st.root + (size_t)e * (A + P) * 13;
+  const float* dof = st.dof + (size_t)e * m->ND * 2;
+  cam_stage_env(m, root, dof, s_link, s_prim, tid);
   // ---- rays --------------------------------------------------------------------------------------------------------------------------
   float Rc[9];                                                   // camera in the base frame: ZYX Euler (yaw, pitch, roll) = Rz Ry Rx
   {
@@ -154,8 +355,6 @@ __global__ void __launch_bounds__(256) k_depth_camera(const DevModel* __restrict
   }
   const int npix = ca.H * ca.W;
   const float tan_v = ca.tan_half_h * (float)ca.H / (float)ca.W;
-  const float hs = m->hs;
-  const int nx = m->sdf_nx, ny = m->sdf_ny;
   for (int idx = tid; idx < A * npix; idx += blockDim.x) {
     const int a = idx / npix, pix = idx - a * npix, pi = pix / ca.W, pj = pix - pi * ca.W;
     const float* B = s_link + (a * MQE_NBODY) * CAM_LINK;          // the base link of robot a
@@ -165,99 +364,11 @@ __global__ void __launch_bounds__(256) k_depth_camera(const DevModel* __restrict
     const float yc = -(2.0f * (pj + 0.5f) / ca.W - 1.0f) * ca.tan_half_h;      // column 0 = the camera's left (+y)
     const float zc = -(2.0f * (pi + 0.5f) / ca.H - 1.0f) * tan_v;               // row 0 = the top (+z)
     const CV3 d = cmul(Rw, cv(1.0f, yc, zc));                                    // t = depth along the optical axis
-    float best = ca.far_;
-    // ground: the slab plane, or the relief map marched in half cells and bisected
-    if (m->ground_height == nullptr) {
-      if (d.z < -1e-9f) { const float t = (m->ground_z - o.z) / d.z; if (t > 1e-4f && t < best) best = t; }
-    } else {
-      const float dxy = sqrtf(d.x * d.x + d.y * d.y);
-      const float dt = dxy > 1e-6f ? 0.5f * hs / dxy : 0.05f;
-      auto hgt = [&](CV3 p) -> float {
-        float fx = fminf(fmaxf(p.x / hs, 0.0f), (float)(nx - 1)), fy = fminf(fmaxf(p.y / hs, 0.0f), (float)(ny - 1));
-        int ix = min((int)fx, nx - 2), iy = min((int)fy, ny - 2);
-        const float tx = fx - ix, ty = fy - iy;
-        const float* g = m->ground_height + (size_t)ix * ny + iy;
-        const float b0 = g[0] + (g[1] - g[0]) * ty, b1 = g[ny] + (g[ny + 1] - g[ny]) * ty;
-        return m->ground_z + b0 + (b1 - b0) * tx;
-      };
-      float tp = 0.0f;
-      for (float t = dt; t < best; t += dt) {
-        const CV3 p = o + t * d;
-        if (p.z < hgt(p)) {
-          float lo = tp, hi = t;
-          for (int it = 0; it < 6; it++) { const float mid = 0.5f * (lo + hi); const CV3 pm = o + mid * d; if (pm.z < hgt(pm)) hi = mid; else lo = mid; }
-          best = hi;
-          break;
-        }
-        tp = t;
-      }
-    }
-    // wall prisms: march over the signed-distance map of the wall set (a step never crosses more than the distance to the nearest wall)
-    {
-      const float dxy = sqrtf(d.x * d.x + d.y * d.y);
-      if (dxy > 1e-6f && m->wall_sdf != nullptr) {
-        float t = 1e-4f;
-        for (int it = 0; it < 400 && t < best; it++) {
-          const CV3 p = o + t * d;
-          const float fxr = p.x / hs, fyr = p.y / hs;
-          if (fxr < 0.0f || fyr < 0.0f || fxr > (float)(nx - 1) || fyr > (float)(ny - 1)) break;       // left the map
-          int ix = min((int)fxr, nx - 2), iy = min((int)fyr, ny - 2);
-          const float tx = fxr - ix, ty = fyr - iy;
-          const float* sd = m->wall_sdf + (size_t)ix * ny + iy;
-          const float a0 = sd[0] + (sd[1] - sd[0]) * ty, a1 = sd[ny] + (sd[ny + 1] - sd[ny]) * ty;
-          const float s = a0 + (a1 - a0) * tx;
-          if (s <= 0.002f) {                                     // on / inside a wall's footprint: below its top it is the wall
-            const float top = m->wall_top != nullptr ? m->wall_top[(size_t)(tx < 0.5f ? ix : ix + 1) * ny + (ty < 0.5f ? iy : iy + 1)] : m->wall_height;
-            if (p.z <= top && p.z >= m->ground_z - 1e-3f) { best = t; break; }
-            t += 0.25f * hs / dxy;                               // above it: the ray may still come down onto the top face
-          } else t += fmaxf(s, 0.002f) / dxy;
-        }
-      }
-    }
-    // the other robots' primitives
-    for (int r = 0; r < A; r++) {
-      if (r == a) continue;
-      for (int q = 0; q < npr; q++) {
-        const float* Q = s_prim + (r * npr + q) * CAM_PRIM;
-        const int type = (int)Q[0];
-        const CV3 c = cv(Q[4], Q[5], Q[6]);
-        if (type == MQE_PRIM_BOX) best = ray_box(o, d, c, s_link + (int)Q[1] * CAM_LINK, cv(Q[8], Q[9], Q[10]), best);
-        else if (type == MQE_PRIM_CAPSULE) best = ray_capsule(o, d, c, cv(Q[8], Q[9], Q[10]), Q[2], best);
-        else best = ray_sphere(o, d, c, Q[2], best);
-      }
-    }
-    // free NPCs (ball, sheep: spheres in the body frame, translation only for the sheep; the box), the 1-dof link, the scenery
-    if (m->has_box) {
-      for (int p = 0; p < m->n_npc_dyn; p++) {
-        float Rb[9];
-        cquat(root + (A + p) * 13 + 3, Rb);
-        best = ray_box(o, d, cv(root[(A + p) * 13], root[(A + p) * 13 + 1], root[(A + p) * 13 + 2]), Rb, cv(m->npc_box_half[0], m->npc_box_half[1], m->npc_box_half[2]), best);
-      }
-    } else {
-      for (int p = 0; p < m->n_npc_dyn; p++) {
-        float Rb[9];
-        cquat(root + (A + p) * 13 + 3, Rb);
-        const CV3 pb = cv(root[(A + p) * 13], root[(A + p) * 13 + 1], root[(A + p) * 13 + 2]);
-        for (int k = 0; k < m->npc_n_spheres; k++)
-          best = ray_sphere(o, d, pb + cmul(Rb, cv(m->npc_sphere_center[k][0], m->npc_sphere_center[k][1], m->npc_sphere_center[k][2])), m->npc_sphere_radius[k], best);
-      }
-    }
-    const float I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if (m->has_seesaw) {
-      const CV3 sb = cv(root[A * 13], root[A * 13 + 1], root[A * 13 + 2]);
-      if (m->ss_base_half[0] > 0.0f) best = ray_box(o, d, sb, I3, cv(m->ss_base_half[0], m->ss_base_half[1], m->ss_base_half[2]), best);
-      CV3 piv = sb + cv(m->ss_joint_offset[0], m->ss_joint_offset[1], m->ss_joint_offset[2]);
-      const float th = dof[(12 * A) * 2];
-      float Rp[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-      if (m->ss_axis == 3) piv.y += th; else caxis(m->ss_axis == 2 ? cv(0, 0, 1) : cv(0, 1, 0), th, Rp);
-      const CV3 pc = piv + cmul(Rp, cv(m->ss_plank_center[0], m->ss_plank_center[1], m->ss_plank_center[2]));
-      if (m->ss_link_cyl) best = ray_capsule(o, d, pc, cv(0, 0, fmaxf(m->ss_plank_half[2] - m->ss_plank_half[0], 0.0f)), m->ss_plank_half[0], best);      // upright cylinder ~ capsule
-      else best = ray_box(o, d, pc, Rp, cv(m->ss_plank_half[0], m->ss_plank_half[1], m->ss_plank_half[2]), best);
-    }
-    for (int bx = 0; bx < m->n_static; bx++) {
-      const CV3 nb = cv(root[A * 13], root[A * 13 + 1], root[A * 13 + 2]);
-      best = ray_box(o, d, nb + cv(m->sb_center[bx][0], m->sb_center[bx][1], m->sb_center[bx][2]), I3, cv(m->sb_half[bx][0], m->sb_half[bx][1], m->sb_half[bx][2]), best);
-    }
-    ca.out[((size_t)e * A + a) * npix + pix] = best < ca.far_ ? -best : __uint_as_float(0xFF800000u);       // -inf (the build drops inf arithmetic: written as its bit pattern)
+    CamHit h;
+    h.t = ca.far_; h.id = 0; h.n = cv(0.0f, 0.0f, 0.0f);
+    cam_ground<false>(m, o, d, h);
+    cam_walls(m, o, d, h);
+    cam_bodies(m, root, dof, s_link, s_prim, o, d, a, h);                        // the OTHER robots
+    ca.out[((size_t)e * A + a) * npix + pix] = h.t < ca.far_ ? -h.t : __uint_as_float(0xFF800000u);       // -inf (the build drops inf arithmetic: written as its bit pattern)
   }
 }

@@ -18,6 +18,7 @@
 #include "kernels_camera.hpp"
 #include "kernels_bodies.hpp"
 #include "kernels_terrain_scan.hpp"
+#include "kernels_view.hpp"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, const char* a = "") {
@@ -1221,6 +1222,33 @@ extern "C" int mqe_render_depth(mqe_sim* s, float* out_dev, int height, int widt
   ca.far_ = far_m;
   hipLaunchKernelGGL(k_depth_camera, dim3(s->N), dim3(256), 0, (hipStream_t)stream, s->dm, s->st, ca);
   return hipGetLastError() == hipSuccess ? 0 : fail(-4, "k_depth_camera launch failed");
+}
+extern "C" int mqe_render_view(mqe_sim* s, int env, uint8_t* rgba_dev, float* geom_dev, int32_t* id_dev, int height, int width, float horizontal_fov_deg,
+                               const float* eye3, const float* lookat3, float far_m, void* stream) {
+  if (!s) return fail(-1, "null engine handle");
+  if (!rgba_dev && !geom_dev && !id_dev) return fail(-1, "mqe_render_view: all three outputs are null");
+  if (!eye3 || !lookat3) return fail(-1, "mqe_render_view: null eye3 / lookat3");
+  if (env < 0 || env >= s->N) return fail(-6, "mqe_render_view: env outside [0, num_envs)");
+  if (height <= 0 || width <= 0 || (long long)height * width > MQE_VIEW_MAX_PIXELS) return fail(-6, "mqe_render_view: resolution out of range (height, width > 0, height * width <= MQE_VIEW_MAX_PIXELS)");
+  if (!(horizontal_fov_deg > 1.0f && horizontal_fov_deg < 179.0f) || !(far_m > 0.0f)) return fail(-6, "mqe_render_view: field of view outside (1, 179) / far plane <= 0");
+  if (((uintptr_t)rgba_dev & 3) || ((uintptr_t)geom_dev & 15) || ((uintptr_t)id_dev & 3)) return fail(-6, "mqe_render_view: rgba_dev / id_dev need 4-byte, geom_dev 16-byte alignment");
+  // the basis in double: f = normalize(lookat - eye), l = normalize(z x f) (f vertical: (0, 1, 0)), u = f x l
+  double f[3], l[3], u[3], nf = 0.0;
+  for (int k = 0; k < 3; k++) { f[k] = (double)lookat3[k] - (double)eye3[k]; nf += f[k] * f[k]; }
+  nf = sqrt(nf);
+  if (!(nf >= 1e-6)) return fail(-6, "mqe_render_view: eye and lookat coincide");
+  for (int k = 0; k < 3; k++) f[k] /= nf;
+  const double nl = sqrt(f[0] * f[0] + f[1] * f[1]);
+  if (nl < 1e-6) { l[0] = 0.0; l[1] = 1.0; l[2] = 0.0; } else { l[0] = -f[1] / nl; l[1] = f[0] / nl; l[2] = 0.0; }
+  u[0] = f[1] * l[2] - f[2] * l[1]; u[1] = f[2] * l[0] - f[0] * l[2]; u[2] = f[0] * l[1] - f[1] * l[0];
+  if (s->step_open) return fail(-8, "mqe_render_view inside an open step");
+  ViewArgs va;
+  va.rgba = (uint32_t*)rgba_dev; va.geom = (float4*)geom_dev; va.id = id_dev;
+  va.env = env; va.H = height; va.W = width; va.tan_half_h = tanf(0.5f * horizontal_fov_deg * 3.14159265358979f / 180.0f);
+  for (int k = 0; k < 3; k++) { va.eye[k] = eye3[k]; va.f[k] = (float)f[k]; va.l[k] = (float)l[k]; va.u[k] = (float)u[k]; }
+  va.far_ = far_m;
+  hipLaunchKernelGGL(k_view, dim3((width + VIEW_TILE - 1) / VIEW_TILE, (height + VIEW_TILE - 1) / VIEW_TILE), dim3(256), 0, (hipStream_t)stream, s->dm, s->st, va);
+  return hipGetLastError() == hipSuccess ? 0 : fail(-4, "k_view launch failed");
 }
 extern "C" int mqe_refresh_rigid_body_state(mqe_sim* s, void* stream) {
   if (!s) return fail(-1, "null engine handle");

@@ -10,6 +10,22 @@ MAX_AGENTS, MAX_NPCS, FRAME, HIST, MAX_LAYERS, MAX_REWARD_TERMS = 4, 16, 72, 30,
 OBS_BAG = 74
 MAX_HEIGHT_POINTS, HSCAN_SCENERY = 1024, 1      # mqe_measure_heights: grid points per robot, the scenery flag
 
+# mqe_render_view (include/mqe_hip.h): the id word's classes and bit fields, and the constants of the colour formula
+VIEW_MAX_PIXELS = 1 << 20
+VIEW_NONE, VIEW_GROUND, VIEW_WALL, VIEW_ROBOT, VIEW_NPC, VIEW_LINK_SCENE, VIEW_SCENERY = range(7)
+VIEW_CHECKER_BIT = 1 << 24
+VIEW_AMBIENT, VIEW_DIFFUSE, VIEW_CHECKER = 0.35, 0.65, 0.08
+VIEW_LIGHT = (0.36, 0.48, 0.80)
+VIEW_SKY = (135, 190, 235)
+VIEW_PALETTE = ((0.55, 0.58, 0.50), (0.72, 0.68, 0.60), (0.85, 0.25, 0.20), (0.20, 0.40, 0.85), (0.95, 0.75, 0.15),      # ground, wall, robots 0-3,
+                (0.25, 0.70, 0.35), (0.92, 0.90, 0.82), (0.60, 0.42, 0.25), (0.50, 0.50, 0.58))                          # free NPC, 1-dof scene, scenery box
+
+
+def view_palette_row(cls, index):
+    """row of VIEW_PALETTE that holds the albedo of class `cls` (robot `index`: one of four)"""
+    return {VIEW_GROUND: 0, VIEW_WALL: 1, VIEW_ROBOT: 2 + index % 4}.get(cls, cls + 2)
+
+
 TASK = dict(plain=0, gate=1, sheep=2, seesaw=3, football_defender=4, pushbox=5, rotation=6, bridge=7, wrestling=8, tug=9)
 NPC = dict(none=0, ball=1, sheep=2, seesaw=3, box=4, rotation=3, bridge=5, wrestling=5, circular=3)     # the revolving door shares the seesaw's fixed-base + 1-dof-link structure
 CTRL = dict(C=0, P=1, V=2, T=3)

@@ -169,6 +169,32 @@ class HipEngine(EngineBase):
             raise RuntimeError(f"mqe_render_depth failed ({rc}): {self.lib.mqe_last_error().decode()}")
         return out
 
+    def render_view(self, env, height, width, hfov_deg, eye, lookat, far=60.0, rgba=None, geom=False, ids=False):
+        """one image of env `env` from a free camera at the world point `eye` looking at `lookat`, from the current state (mqe_render_view;
+        include/mqe_hip.h is the specification): the (H, W, 4) uint8 colour image, Isaac Gym's IMAGE_COLOR layout, as a device tensor
+        (`rgba`: a tensor to fill instead of a fresh one).  geom / ids: a tuple that adds the (H, W, 4) float tensor (negative axial depth,
+        -inf on a miss; world normal facing the eye) and / or the (H, W) int32 id words (abi.VIEW_*).  One launch, no synchronisation."""
+        H, W = int(height), int(width)
+        if H <= 0 or W <= 0 or H * W > abi.VIEW_MAX_PIXELS:
+            raise ValueError(f"render_view: resolution {H} x {W} out of range (height * width <= {abi.VIEW_MAX_PIXELS})")
+        dev = self.torch_device
+        if rgba is None:
+            rgba = torch.empty(H, W, 4, dtype=torch.uint8, device=dev)
+        assert rgba.is_cuda and rgba.dtype == torch.uint8 and rgba.is_contiguous() and rgba.numel() == H * W * 4
+        g = torch.empty(H, W, 4, dtype=torch.float32, device=dev) if geom else None
+        i = torch.empty(H, W, dtype=torch.int32, device=dev) if ids else None
+        f = self.lib.mqe_render_view
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                      C.c_float, C.c_void_p]
+        f.restype = C.c_int
+        e3, l3 = (C.c_float * 3)(*[float(x) for x in eye]), (C.c_float * 3)(*[float(x) for x in lookat])
+        rc = f(self.h, int(env), C.c_void_p(rgba.data_ptr()), C.c_void_p(g.data_ptr() if geom else None), C.c_void_p(i.data_ptr() if ids else None),
+               H, W, float(hfov_deg), e3, l3, float(far), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"mqe_render_view failed ({rc}): {self.lib.mqe_last_error().decode()}")
+        out = (rgba,) + ((g,) if geom else ()) + ((i,) if ids else ())
+        return out if len(out) > 1 else rgba
+
     def refresh_rigid_body_state(self):
         """gym.refresh_rigid_body_state_tensor: tensor(T_RIGID_BODY_STATE) from the current root and dof state (mqe_refresh_rigid_body_state)"""
         self._call("refresh_rigid_body_state", self._stream())

@@ -228,6 +228,10 @@ class Go1:
             self.extras["episode"]["terrain_level"] = torch.zeros((), device=dev)
             self._refresh_extras()
         self.common_step_counter = 0
+        # episode recording (legged_robot.py:916-923): off until start_recording()
+        self.record_now = False
+        self.video_frames = []
+        self.complete_video_frames = []
         if self.task == "football_defender":
             self.gate_pos = torch.zeros(N, 3, device=dev)
             self.gate_pos[:, :2] = torch.from_numpy(self._task_gate_pos()).to(dev)
@@ -393,6 +397,7 @@ class Go1:
     def reset(self):
         """Reset all robots (go1.py:147-151): no physics step, observations recomputed."""
         self.engine.reset_all()
+        self.store_recording(range(self.num_envs))      # reset_idx of every env (legged_robot.py:200); no frame is rendered here
         self._refresh_extras()
         return self.obs_buf
 
@@ -482,10 +487,12 @@ class Go1:
                 c = self.cfg.normalization.clip_actions
                 self.actions.copy_(torch.clip(a, -c, c).reshape(self.actions.shape))
                 self._decimation_loop()
+                self._record_step()
                 self._refresh_extras()
                 return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
             self.engine.step_joint(a)
             self.common_step_counter += 1
+            self._record_step()
             self._refresh_extras()
             return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
         cmd = action.reshape(-1, self.engine.desc.num_command_dims).to(self.engine.torch_device, torch.float32).contiguous()   # 3 unless command.cfg says otherwise (go1.py:64-93)
@@ -507,6 +514,7 @@ class Go1:
             e.step_command(cmd)
             self._steps_policy = getattr(self, "_steps_policy", 0) + 1
             self.common_step_counter += 1
+        self._record_step()
         self._refresh_extras()
         return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
 
@@ -527,6 +535,7 @@ class Go1:
             self.engine.step(a, hooks[0])
         self._steps_policy = getattr(self, "_steps_policy", 0) + 1
         self.common_step_counter += 1
+        self._record_step()
         self._refresh_extras()
 
     def get_state(self):
@@ -546,7 +555,79 @@ class Go1:
     def get_privileged_observations(self):
         return None
 
-    def render(self, *a, **k):
+    # ---- episode recording (legged_robot.py:916-957; the camera of mqe/utils/helpers.py:276-298) ----------------------------------------
+    # Upstream films env 0 with a FloatingCameraSensor at cfg.viewer.pos looking at cfg.viewer.lookat, recording_width_px x
+    # recording_height_px, at CameraProperties' default 90 degree field of view, through Isaac Gym's rasteriser.  Here the frame is the
+    # engine's ray-cast view of the collision geometry (mqe_render_view); the state machine below is upstream's, its accidents included:
+    #   * nothing is recorded between start_recording() and the first reset of env 0 (complete_video_frames is None until then);
+    #   * once an episode is complete (env 0 was reset again) recording stops: the frames wait in complete_video_frames;
+    #   * the NEXT reset of env 0 overwrites the complete episode with the empty list and recording resumes -- fetch the frames when
+    #     done[0] is seen, as upstream's loops do (test.py:54-70, openrl_ws/test.py:87-95).
+    # Frames stay device tensors until get_complete_frames(): an episode of L frames holds L x 345 kB of device memory at the default
+    # 360 x 240.  While record_now is false a step pays nothing; while it is set every step reads ONE byte back from the device
+    # (reset_buf[0]: was env 0 reset in this step?), which synchronises the stream, and launches one kernel when a frame is due.
+    def _render_frame(self):
+        """(recording_height_px, recording_width_px, 4) uint8 device tensor: env 0 from the viewer's camera, current state"""
+        env, view = self.cfg.env, self.cfg.viewer
+        return self.engine.render_view(0, int(env.recording_height_px), int(env.recording_width_px), 90.0, view.pos, view.lookat)
+
+    def _render_headless(self):
+        if self.record_now and self.complete_video_frames is not None and len(self.complete_video_frames) == 0:
+            self.video_frame = self._render_frame()
+            self.video_frames.append(self.video_frame)
+
+    def _record_step(self):
+        """end of every step, after the engine's launches (post_physics_step's tail, legged_robot.py:145-157): reset_idx's
+        store_recording for env 0 if this step reset it, then _render_headless.  Does nothing, and reads nothing, unless record_now"""
+        if not self.record_now:
+            return
+        if bool(self.reset_buf[0]):
+            self.store_recording((0,))
+        self._render_headless()
+
+    def start_recording(self):
+        if not getattr(self.cfg.env, "record_video", False):
+            raise RuntimeError("start_recording needs cfg.env.record_video = True (--record_video): without it there is no recording camera")
+        e = self.engine
+        if not hasattr(e, "render_view"):
+            raise NotImplementedError(f"episode recording is rendered by the HIP engine (mqe.engine.hip_engine.HipEngine, mqe_render_view); "
+                                      f"{type(e).__name__} has no free camera")
+        if int(e.desc.env_id_offset) != 0:
+            raise NotImplementedError("episode recording films global env 0, which lives on the shard whose env_id_offset is 0; "
+                                      f"this shard starts at env {int(e.desc.env_id_offset)}")
+        print("start recording")
+        self.complete_video_frames = None
+        self.record_now = True
+
+    def pause_recording(self):
+        print("pause recording")
+        self.complete_video_frames = []
+        self.video_frames = []
+        self.record_now = False
+
+    def get_complete_frames(self):
+        """the last complete episode of env 0 as a list of (H, W, 4) uint8 numpy arrays ([] while there is none): the device -> host copy"""
+        if self.complete_video_frames is None:
+            return []
+        return [f.cpu().numpy() for f in self.complete_video_frames]
+
+    def store_recording(self, env_ids):
+        if getattr(self.cfg.env, "record_video", False) and 0 in env_ids:
+            if self.complete_video_frames is None:
+                self.complete_video_frames = []
+            else:
+                print("Successfully store the video of last episode")
+                self.complete_video_frames = self.video_frames[:]
+            self.video_frames = []
+
+    def render(self, mode=None, *a, **k):
+        """mode="rgb_array": the current frame of env 0 from the viewer's camera as an (H, W, 4) uint8 numpy array (one launch and a
+        device -> host copy); any other mode: None (there is no viewer)"""
+        if mode == "rgb_array":
+            if not hasattr(self.engine, "render_view"):
+                raise NotImplementedError(f"render(mode=\"rgb_array\") is rendered by the HIP engine (mqe.engine.hip_engine.HipEngine, "
+                                          f"mqe_render_view); {type(self.engine).__name__} has no free camera")
+            return self._render_frame().cpu().numpy()
         return None
 
     def close(self):
