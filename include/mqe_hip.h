@@ -34,7 +34,8 @@ extern "C" {
  * robot's one-sided contacts to its DEEPEST eight instead of the first eight in feature order.  v16 (round 6) over v15: mqe_debug_epilogue_times
  * (new export).  v17 over v16: MQE_T_RIGID_BODY_STATE (new tensor kind before MQE_T_COUNT), mqe_refresh_rigid_body_state and
  * mqe_set_rigid_body_refresh (new exports).  v17, additive (no bump: no limit of mqe_abi_limits, tensor kind, descriptor field or existing call
- * changes): mqe_measure_heights and mqe_set_height_refresh (new exports), MQE_MAX_HEIGHT_POINTS, MQE_HSCAN_SCENERY. */
+ * changes): mqe_measure_heights and mqe_set_height_refresh (new exports), MQE_MAX_HEIGHT_POINTS, MQE_HSCAN_SCENERY; mqe_actor_create,
+ * mqe_actor_params and mqe_rollout (new exports), mqe_actor_shape, MQE_ACTOR_*, MQE_ROLLOUT_*. */
 #define MQE_ABI_VERSION 17
 #define MQE_MAX_SPHERES 64    /* feature points of one robot (the capsule model has 32, the exact one 60) */
 #define MQE_MAX_PRIMS 20      /* collision primitives of one robot (Go1: 18) */
@@ -416,6 +417,60 @@ int mqe_step_command(mqe_sim* s, const float* command, void* stream);
  * to clip_actions inside; no locomotion policy runs.  The decimation loop, post-physics step and (plain) wrapper are the
  * fused ones. */
 int mqe_step_joint(mqe_sim* s, const float* actions12, void* stream);
+
+/* ---- on-device rollouts: a small Gaussian actor (and optional critic) evaluated by the engine, T steps per call ----
+ * v17, additive (new exports only; no tensor kind, descriptor field, limit of mqe_abi_limits or state-blob change).
+ * The networks are MLPs on the task wrapper's observation (the D floats of a row of MQE_T_WRAPPER_OBS): actor D -> h... -> 3 with a linear
+ * output = the mean, a state-independent log_std[3], critic D -> h... -> 1.  One kernel (csrc/kernels_actor.hpp, k_actor: arithmetic and
+ * summation order stated there) per rollout step, R' = N x A' rows:
+ *   a_j  = mean_j + exp(log_std_j) z_j,  z_j ~ N(0, 1) from the counter RNG keyed by (seed, GLOBAL env id, MQE_RNG_ACTOR + n, agent * 3 + j),
+ *          MQE_RNG_ACTOR = 0x70000000, n = the handle's count of post-physics steps when the launch is enqueued (the counter that keys the
+ *          NPC script's draws; part of mqe_state_save): a trajectory does not depend on how the envs are sharded and continues bit for bit
+ *          after mqe_state_load;
+ *   logp = sum_j (-z_j^2 / 2 - log_std_j - ln(2 pi) / 2): the density of the UNCLIPPED sample a;
+ *   the following step receives action_gain * a (mqe_step clips to +-1 and applies the task's action scale as for any caller).
+ * Parameter buffer (mqe_actor_params), flat f32: per layer W (out, in) row-major as torch.nn.Linear.weight, then b (out); the actor's
+ * layers first, then the critic's, then log_std[3]. */
+#define MQE_ACTOR_MAX_LAYERS 4        /* Linear layers of one network */
+#define MQE_ACTOR_MAX_HIDDEN 256      /* width of a hidden layer */
+#define MQE_ACTOR_MAX_OBS 128         /* D */
+#define MQE_ACTOR_TANH 0
+#define MQE_ACTOR_RELU 1
+#define MQE_ROLLOUT_MAX_STEPS 4096    /* T of one mqe_rollout call */
+#define MQE_ROLLOUT_DETERMINISTIC 1   /* flags bit 0: a = mean, logp evaluated at z = 0 */
+typedef struct {
+  int32_t obs_dim;                                /* D: must equal the scene's MQE_T_WRAPPER_OBS width */
+  int32_t act_dim;                                /* 3 */
+  int32_t actor_layers;                           /* 1 .. MQE_ACTOR_MAX_LAYERS */
+  int32_t actor_dims[MQE_ACTOR_MAX_LAYERS + 1];   /* obs_dim, hidden ..., 3 */
+  int32_t critic_layers;                          /* 0 = no critic */
+  int32_t critic_dims[MQE_ACTOR_MAX_LAYERS + 1];  /* obs_dim, hidden ..., 1 */
+  int32_t activation;                             /* MQE_ACTOR_TANH / MQE_ACTOR_RELU on every hidden layer of both networks */
+  float action_gain;                              /* 1 for the task wrappers, 0.5 for the OpenRL adapter (which feeds 0.5 * a) */
+} mqe_actor_shape;
+/* Allocates the engine-owned parameter buffer (zeroed) and the action staging buffer; a second call replaces the first.  Refused with
+ * -6 and a message: obs_dim differs from the scene's wrapper-observation width; the scene has no task observation (MQE_TASK_PLAIN: go1plane,
+ * the football stubs); num_command_dims != 3; control type other than C; act_dim != 3; a layer count, width or dims[] end outside the limits above. */
+int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* shape);
+/* the flat parameter buffer as a 1-d f32 view: live device memory like every tensor of the handle -- a trainer copies its updated
+ * parameters into it on the device; launches enqueued later on the same stream see them.  -6 without an actor. */
+int mqe_actor_params(mqe_sim* s, mqe_tensor_view* out);
+/* T steps in one host call: per step k_actor, then the launches of mqe_step (registered rigid-body / height-scan refreshes included), each
+ * step's return buffer redirected into the trajectory; a final value-only launch (no draw) when value_dev is given.  No synchronisation.
+ *   packed_dev   T + 1 rows of row_stride floats, row_stride >= the MQE_T_WRAPPER_PACKED length and a multiple of 4; 16-byte aligned.  Row 0 =
+ *                the starting observation with reward and done bytes zeroed; row t + 1 = what step t returns, in mqe_set_return_buffer's
+ *                obs | reward | done-bytes layout.  Floats of a row beyond that layout are never written.
+ *   obs0_dev     (N, A', D) observation the first action is computed from; NULL = the engine's own MQE_T_WRAPPER_OBS (stale after a step
+ *                that was given a return buffer of the caller's: such a caller passes the observation it holds)
+ *   actions_dev  [T, N, A', 3] the unclipped samples;  logp_dev [T, N, A'] or NULL;  value_dev [T + 1, N, A'] or NULL (NULL is required
+ *                without a critic), entry T = the value of the last observation.  4-byte alignment.
+ *   flags        MQE_ROLLOUT_DETERMINISTIC
+ * Afterwards the return-buffer switch points at the engine's own buffer, and one device-to-device copy has brought that buffer (the
+ * MQE_T_WRAPPER_* views) to row T: a following call with obs0_dev == NULL continues the trajectory.  Refusals enqueue nothing: -1 null handle / packed_dev /
+ * actions_dev; -6 no actor, T <= 0, T > MQE_ROLLOUT_MAX_STEPS, a misaligned pointer, a bad row_stride, value_dev without a critic; -8 inside an
+ * open step (mqe_step_begin / _head without mqe_step_end). */
+int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* packed_dev, long long row_stride, float* actions_dev, float* logp_dev,
+                float* value_dev, int flags, void* stream);
 
 /* The onboard forward depth camera of LeggedRobotField (legged_robot_field.py:23-93: create_camera_sensor + attach_camera_to_body on the
  * base link, :196-223: get_camera_image_gpu_tensor(IMAGE_DEPTH)) for every robot, from the CURRENT state: out_dev [R][height][width]

@@ -578,12 +578,16 @@ __device__ __forceinline__ void reset_env_dev(const DevModel* m, const DevState&
   st.reset_count[e] = cnt + 1;
 }
 
+// mqe_randn_key: the one Box-Muller statement, for any key (seed, GLOBAL env id, count, k); the rollout's actor (kernels_actor.hpp) draws
+// from it with count = MQE_RNG_ACTOR + the number of post-physics steps so far
+__device__ __forceinline__ float mqe_randn_key(uint32_t seed, uint32_t genv, uint32_t cnt, uint32_t k) {
+  const float u1 = mqe_u01(seed, genv, cnt, 2u * k), u2 = mqe_u01(seed, genv, cnt, 2u * k + 1u);
+  return sqrtf(-2.0f * logf(1.0f - u1)) * cosf(6.2831855f * u2);
+}
 // N(0,1) of the sheep's random walk (go1_sheep.py:43: randn_like per step) in MQE_NOISE_HASH mode: Box-Muller over the counter
 // RNG keyed by (seed, GLOBAL env id, ordinal of the post-physics step, sheep * 3 + axis) -- independent of the GPU count
 __device__ __forceinline__ float mqe_randn(const DevModel* m, int e, int step_no, uint32_t k) {
-  const uint32_t cnt = MQE_RNG_NPC + (uint32_t)step_no, genv = (uint32_t)(e + m->env_id_offset);
-  const float u1 = mqe_u01((uint32_t)m->seed, genv, cnt, 2u * k), u2 = mqe_u01((uint32_t)m->seed, genv, cnt, 2u * k + 1u);
-  return sqrtf(-2.0f * logf(1.0f - u1)) * cosf(6.2831855f * u2);
+  return mqe_randn_key((uint32_t)m->seed, (uint32_t)(e + m->env_id_offset), MQE_RNG_NPC + (uint32_t)step_no, k);
 }
 
 // The sheep script (go1_sheep.py:35-64) in three pieces so that k_post_physics can spread an env's sheep over lanes: flock mean

@@ -310,6 +310,7 @@ __host__ __device__ __forceinline__ float mqe_u01(uint32_t seed, uint32_t genv, 
 #define MQE_RNG_CREATE 0xD0D0D0D0u         // `count` of the draws made once per handle (domain parameters)
 #define MQE_RNG_PUSH 0x50000000u           // + ordinal of the push
 #define MQE_RNG_NPC 0x60000000u            // + ordinal of the post-physics step: the sheep's per-step N(0,1) draws
+#define MQE_RNG_ACTOR 0x70000000u          // + post-physics steps so far: the rollout actor's N(0,1) draws (kernels_actor.hpp)
 
 
 // f32 -> two f16 planes of scale * x (h + l == scale * x to 22 significand bits); see k_gemm_h2 in kernels_gemm.hpp

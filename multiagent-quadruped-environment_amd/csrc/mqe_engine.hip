@@ -19,6 +19,7 @@
 #include "kernels_bodies.hpp"
 #include "kernels_terrain_scan.hpp"
 #include "kernels_view.hpp"
+#include "kernels_actor.hpp"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, const char* a = "") {
@@ -115,6 +116,16 @@ struct mqe_sim {
   struct HscanGrid { float* dev = nullptr; std::vector<float> host; } hscan_grid[2];
   bool hscan_refresh = false;         // mqe_set_height_refresh: every post-physics step refreshes hscan_args.out first
   HscanArgs hscan_args;
+  // on-device rollouts (kernels_actor.hpp; mqe_actor_create): the networks' shapes, the flat parameter buffer and the staging buffer the
+  // step reads action_gain * a from.  Parameters are the trainer's, not simulation state: never in state_bufs
+  struct Actor {
+    bool on = false;
+    ActorNet actor, critic;
+    int log_std_off = 0, n_params = 0, ldh = 0, relu = 0;
+    float gain = 1.0f;
+    float* params = nullptr;      // [n_params]
+    float* stage = nullptr;       // [N, A', 3]
+  } act;
   // profiling
   bool prof = false, prof_now = false;   // prof_now: this call is one of the sampled ones
   int step_open = 0;                     // 0: no step in flight; 1: after mqe_step_head; 2: after mqe_step_tail / mqe_step_begin (mqe_step_end closes)
@@ -1461,6 +1472,109 @@ extern "C" int mqe_step_end(mqe_sim* s, void* stream) {
   if (s->step_open != 2) return fail(-8, "mqe_step_end without mqe_step_begin (or mqe_step_head + mqe_step_tail)");
   s->step_open = 0;
   return run_substeps_and_post(s, (hipStream_t)stream);
+}
+
+// ---- on-device rollouts: mqe_actor_create / mqe_actor_params / mqe_rollout (include/mqe_hip.h) ---------------------------------
+// one network's dims[] against the limits; fills its offsets into the flat parameter buffer from *off on
+static int actor_net_shape(const char* who, int layers, const int32_t* dims, int in, int out, ActorNet* net, int* off, int* ldh) {
+  if (layers < 1 || layers > MQE_ACTOR_MAX_LAYERS) return fail(-6, "mqe_actor_create: %s: 1 .. 4 Linear layers (MQE_ACTOR_MAX_LAYERS)", who);
+  if (dims[0] != in) return fail(-6, "mqe_actor_create: %s: dims[0] must be obs_dim", who);
+  if (dims[layers] != out) return fail(-6, "mqe_actor_create: %s: the last width must be 3 for the actor (the mean) and 1 for the critic", who);
+  net->n_layers = layers;
+  for (int l = 0; l <= layers; l++) {
+    if (l > 0 && l < layers && (dims[l] < 1 || dims[l] > MQE_ACTOR_MAX_HIDDEN)) return fail(-6, "mqe_actor_create: %s: a hidden width outside 1 .. 256 (MQE_ACTOR_MAX_HIDDEN)", who);
+    net->dims[l] = dims[l];
+    if (l < layers && dims[l] > *ldh) *ldh = dims[l];
+  }
+  for (int l = 0; l < layers; l++) {
+    net->w_off[l] = *off;
+    *off += dims[l] * dims[l + 1] + dims[l + 1];
+  }
+  return 0;
+}
+static void actor_release(mqe_sim* s) {
+  for (float* p : {s->act.params, s->act.stage}) {
+    if (!p) continue;
+    for (size_t i = 0; i < s->allocs.size(); i++)
+      if (s->allocs[i] == p) { s->allocs.erase(s->allocs.begin() + i); break; }
+    hipFree(p);         // waits for the launches that still read it
+  }
+  s->act = mqe_sim::Actor();
+}
+extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
+  if (!s || !sh) return fail(-1, "mqe_actor_create: null argument");
+  if (s->step_open) return fail(-8, "mqe_actor_create inside an open step");
+  if (s->d.task == MQE_TASK_PLAIN) return fail(-6, "mqe_actor_create: this scene has no task observation (plain / stub wrapper): nothing for an actor to read");
+  if (s->d.control_type != MQE_CTRL_C || s->cmd_general)
+    return fail(-6, "mqe_actor_create: the actor emits (x, y, yaw) per agent: control type C with num_command_dims == 3 and the default command layout");
+  if (sh->obs_dim != s->D) return fail(-6, "mqe_actor_create: obs_dim differs from the width of this scene's MQE_T_WRAPPER_OBS");
+  if (sh->obs_dim > MQE_ACTOR_MAX_OBS) return fail(-6, "mqe_actor_create: obs_dim above MQE_ACTOR_MAX_OBS (128)");
+  if (sh->act_dim != 3) return fail(-6, "mqe_actor_create: act_dim must be 3");
+  if (sh->activation != MQE_ACTOR_TANH && sh->activation != MQE_ACTOR_RELU) return fail(-6, "mqe_actor_create: activation must be MQE_ACTOR_TANH or MQE_ACTOR_RELU");
+  if (!(std::fabs(sh->action_gain) < 1e30f)) return fail(-6, "mqe_actor_create: action_gain is not finite");
+  mqe_sim::Actor a;
+  int off = 0, ldh = 0;
+  memset(&a.actor, 0, sizeof a.actor); memset(&a.critic, 0, sizeof a.critic);
+  if (int rc = actor_net_shape("actor", sh->actor_layers, sh->actor_dims, sh->obs_dim, 3, &a.actor, &off, &ldh)) return rc;
+  if (sh->critic_layers != 0)
+    if (int rc = actor_net_shape("critic", sh->critic_layers, sh->critic_dims, sh->obs_dim, 1, &a.critic, &off, &ldh)) return rc;
+  a.log_std_off = off; a.n_params = off + 3; a.ldh = ldh; a.relu = sh->activation == MQE_ACTOR_RELU; a.gain = sh->action_gain;
+  const size_t lds = actor_lds_bytes(ldh);
+  if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)k_actor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(-5, "mqe_actor_create: cannot reserve LDS for k_actor");
+  actor_release(s);
+  if (dalloc(s, &a.params, (size_t)a.n_params) || dalloc(s, &a.stage, (size_t)s->N * s->Aw * 3)) { actor_release(s); return fail(-5, "device alloc failed (actor)"); }
+  a.on = true;
+  s->act = a;
+  return 0;
+}
+extern "C" int mqe_actor_params(mqe_sim* s, mqe_tensor_view* v) {
+  if (!s || !v) return fail(-1, "mqe_actor_params: null argument");
+  if (!s->act.on) return fail(-6, "mqe_actor_params: no actor (mqe_actor_create)");
+  v->ptr = s->act.params; v->ndim = 1; v->shape[0] = s->act.n_params; v->shape[1] = v->shape[2] = v->shape[3] = 0; v->dtype = 0;
+  return 0;
+}
+// value_only: the launch behind the last step (no draw, nothing but value written)
+static void launch_actor(mqe_sim* s, const float* obs, float* actions, float* logp, float* value, int flags, bool value_only, hipStream_t q) {
+  const mqe_sim::Actor& a = s->act;
+  ActorArgs k;
+  k.params = a.params; k.obs = obs; k.actions = value_only ? nullptr : actions; k.logp = logp; k.value = value; k.stage = a.stage;
+  k.actor = a.actor; k.critic = a.critic; k.log_std_off = a.log_std_off;
+  k.rows = s->N * s->Aw; k.D = s->D; k.Aw = s->Aw; k.ldh = a.ldh; k.relu = a.relu; k.deterministic = (flags & MQE_ROLLOUT_DETERMINISTIC) ? 1 : 0;
+  k.gain = a.gain; k.seed = (uint32_t)s->d.seed; k.genv0 = (uint32_t)s->d.env_id_offset; k.count = MQE_RNG_ACTOR + (uint32_t)s->n_post_steps;
+  hipLaunchKernelGGL(k_actor, dim3((k.rows + ACT_ROWS - 1) / ACT_ROWS), dim3(ACT_THREADS), actor_lds_bytes(a.ldh), q, k);
+}
+extern "C" int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* packed_dev, long long row_stride, float* actions_dev, float* logp_dev,
+                           float* value_dev, int flags, void* stream) {
+  if (!s) return fail(-1, "null engine handle");
+  if (!packed_dev || !actions_dev) return fail(-1, "mqe_rollout: packed_dev and actions_dev are required");
+  if (!s->act.on) return fail(-6, "mqe_rollout: no actor (mqe_actor_create)");
+  if (s->step_open) return fail(-8, "mqe_rollout inside an open step (mqe_step_begin / _head without mqe_step_end)");
+  if (T <= 0 || T > MQE_ROLLOUT_MAX_STEPS) return fail(-6, "mqe_rollout: T must be 1 .. MQE_ROLLOUT_MAX_STEPS (4096)");
+  const size_t pf = packed_floats(s);
+  if (row_stride < (long long)pf || row_stride % 4 != 0) return fail(-6, "mqe_rollout: row_stride must be a multiple of 4 and at least the MQE_T_WRAPPER_PACKED length");
+  if (((uintptr_t)packed_dev & 15) || ((uintptr_t)obs0_dev & 3) || ((uintptr_t)actions_dev & 3) || ((uintptr_t)logp_dev & 3) || ((uintptr_t)value_dev & 3))
+    return fail(-6, "mqe_rollout: misaligned pointer (packed_dev: 16 bytes, the others: 4)");
+  if (value_dev && s->act.critic.n_layers == 0) return fail(-6, "mqe_rollout: value_dev given, but the actor was created without a critic");
+  hipStream_t q = (hipStream_t)stream;
+  const size_t rows = (size_t)s->N * s->Aw, nobs = rows * s->D;
+  // row 0: the starting observation, reward and done bytes zeroed
+  HIPCHK(hipMemcpyAsync(packed_dev, obs0_dev ? obs0_dev : (const float*)s->tens[MQE_T_WRAPPER_OBS], nobs * 4, hipMemcpyDeviceToDevice, q));
+  HIPCHK(hipMemsetAsync(packed_dev + nobs, 0, rows * 4 + (size_t)s->N, q));
+  int rc = 0;
+  for (int t = 0; t < T && rc == 0; t++) {
+    launch_actor(s, packed_dev + (size_t)t * row_stride, actions_dev + (size_t)t * rows * 3, logp_dev ? logp_dev + (size_t)t * rows : nullptr,
+                 value_dev ? value_dev + (size_t)t * rows : nullptr, flags, false, q);
+    set_packed(s, packed_dev + (size_t)(t + 1) * row_stride);      // step t returns into row t + 1
+    rc = mqe_step(s, s->act.stage, stream);
+  }
+  if (rc == 0 && value_dev) launch_actor(s, packed_dev + (size_t)T * row_stride, nullptr, nullptr, value_dev + (size_t)T * rows, flags, true, q);
+  set_packed(s, (float*)s->tens[MQE_T_WRAPPER_PACKED]);
+  if (rc) return rc;
+  // the engine's own buffer follows the trajectory's last row: MQE_T_WRAPPER_* show what the last step returned, and a following
+  // call with obs0_dev == NULL continues from it
+  HIPCHK(hipMemcpyAsync(s->tens[MQE_T_WRAPPER_PACKED], packed_dev + (size_t)T * row_stride, (nobs + rows) * 4 + (size_t)s->N, hipMemcpyDeviceToDevice, q));
+  return launched();
 }
 
 // debug: M^-1 of one robot and the contact list of one env from the current state, without advancing it

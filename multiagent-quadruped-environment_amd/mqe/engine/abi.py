@@ -110,6 +110,38 @@ class SimDesc(C.Structure):
     ]
 
 
+# on-device rollouts (include/mqe_hip.h: mqe_actor_create, mqe_actor_params, mqe_rollout)
+ACTOR_MAX_LAYERS, ACTOR_MAX_HIDDEN, ACTOR_MAX_OBS = 4, 256, 128
+ACTOR_TANH, ACTOR_RELU = 0, 1
+ROLLOUT_MAX_STEPS, ROLLOUT_DETERMINISTIC = 4096, 1
+RNG_ACTOR = 0x70000000           # csrc/mqe_common.hpp MQE_RNG_ACTOR: `count` of the actor's draws = RNG_ACTOR + post-physics steps so far
+
+
+class ActorShape(C.Structure):
+    _fields_ = [("obs_dim", i32), ("act_dim", i32), ("actor_layers", i32), ("actor_dims", i32 * (ACTOR_MAX_LAYERS + 1)),
+                ("critic_layers", i32), ("critic_dims", i32 * (ACTOR_MAX_LAYERS + 1)), ("activation", i32), ("action_gain", f32)]
+
+
+def actor_param_layout(actor_dims, critic_dims=None):
+    """The flat parameter buffer of mqe_actor_params as an ordered {name: (offset, shape)}: per layer W (out, in) row-major as
+    torch.nn.Linear.weight, then b; the actor's layers, then the critic's, then log_std[3].  Names: actor.<layer>.weight / .bias,
+    critic.<layer>.weight / .bias, log_std."""
+    out, off = {}, 0
+    for who, dims in (("actor", actor_dims), ("critic", critic_dims or ())):
+        for l in range(len(dims) - 1):
+            k, n = int(dims[l]), int(dims[l + 1])
+            out[f"{who}.{l}.weight"] = (off, (n, k))
+            out[f"{who}.{l}.bias"] = (off + n * k, (n,))
+            off += n * k + n
+    out["log_std"] = (off, (3,))
+    return out
+
+
+def actor_param_count(actor_dims, critic_dims=None):
+    off, shape = actor_param_layout(actor_dims, critic_dims)["log_std"]
+    return off + shape[0]
+
+
 class TensorView(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("ndim", i32), ("shape", C.c_int64 * 4), ("dtype", i32)]
 

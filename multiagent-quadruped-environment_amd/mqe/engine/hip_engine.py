@@ -28,6 +28,21 @@ def load_library():
     return _LIB
 
 
+class Rollout:
+    """A trajectory of HipEngine.rollout: `packed` (T+1, row_stride) is the one tensor the steps wrote -- row 0 the starting observation, row
+    t + 1 what step t returned (obs | reward | done bytes) -- and obs / reward / done are views of it; actions are the UNCLIPPED samples,
+    logp their log-density, value[t] the critic at obs[t] (value[T]: the bootstrap value), None without a critic."""
+
+    def __init__(self, packed, actions, logp, value, shape):
+        N, Aw, D = shape
+        n, nr = N * Aw * D, N * Aw
+        self.packed, self.actions, self.logp, self.value = packed, actions, logp, value
+        self.T = packed.shape[0] - 1
+        self.obs = packed[:, :n].view(self.T + 1, N, Aw, D)
+        self.reward = packed[1:, n:n + nr].view(self.T, N, Aw)
+        self.done = packed[1:, n + nr:].view(torch.uint8)[:, :N].view(torch.bool)      # the byte tail of every row, seen as bool in place
+
+
 class HipEngine(EngineBase):
     prefix = "mqe_"
     device = "cuda"
@@ -129,6 +144,97 @@ class HipEngine(EngineBase):
             assert packed.is_cuda and packed.dtype == torch.float32 and packed.is_contiguous()
             assert packed.numel() >= self.tensor(abi.T_WRAPPER_PACKED).numel()
         self._call("set_return_buffer", C.c_void_p(packed.data_ptr() if packed is not None else None))
+
+    # ---- on-device rollouts (mqe_actor_create / mqe_actor_params / mqe_rollout) -------------------------------------------------------
+    def create_actor(self, actor_dims, critic_dims=None, activation="tanh", action_gain=1.0):
+        """The engine's actor (and critic): MLPs on the task observation.  actor_dims = (D, hidden ..., 3), critic_dims = (D, hidden ..., 1)
+        or None; activation "tanh" / "relu" on every hidden layer; the step receives action_gain * a.  Parameters start at zero: fill the
+        views of actor_params().  A second call replaces the first."""
+        actor_dims = [int(x) for x in actor_dims]
+        critic_dims = [int(x) for x in critic_dims] if critic_dims is not None else []
+        for who, dims in (("actor", actor_dims), ("critic", critic_dims)):
+            if len(dims) - 1 > abi.ACTOR_MAX_LAYERS:         # mqe_actor_shape has no room for them: never reaches the library
+                raise ValueError(f"create_actor: {who}: {len(dims) - 1} Linear layers, at most {abi.ACTOR_MAX_LAYERS} (abi.ACTOR_MAX_LAYERS)")
+        if activation not in ("tanh", "relu"):
+            raise ValueError(f"activation must be 'tanh' or 'relu', got {activation!r}")
+        sh = abi.ActorShape()
+        sh.obs_dim, sh.act_dim = actor_dims[0], 3
+        sh.actor_layers, sh.critic_layers = len(actor_dims) - 1, max(len(critic_dims) - 1, 0)
+        for i, v in enumerate(actor_dims):
+            sh.actor_dims[i] = v
+        for i, v in enumerate(critic_dims):
+            sh.critic_dims[i] = v
+        sh.activation = abi.ACTOR_RELU if activation == "relu" else abi.ACTOR_TANH
+        sh.action_gain = float(action_gain)
+        f = self.lib.mqe_actor_create
+        f.argtypes, f.restype = [C.c_void_p, C.POINTER(abi.ActorShape)], C.c_int
+        rc = f(self.h, C.byref(sh))
+        if rc != 0:
+            raise RuntimeError(f"mqe_actor_create failed ({rc}): {self.lib.mqe_last_error().decode()}")
+        self._actor = dict(actor_dims=actor_dims, critic_dims=critic_dims or None, activation=activation, action_gain=float(action_gain))
+        self._actor_views = None
+
+    def actor_params(self):
+        """{name: zero-copy view} of the engine's parameter buffer (abi.actor_param_layout: actor.0.weight, actor.0.bias, ..., critic.0.weight,
+        ..., log_std) + "flat", the whole buffer.  Live device memory: copy_ into the views; later launches on the stream see the values."""
+        if getattr(self, "_actor", None) is None:
+            raise RuntimeError("no actor: call create_actor first")
+        if self._actor_views is None:
+            v = abi.TensorView()
+            f = self.lib.mqe_actor_params
+            f.argtypes, f.restype = [C.c_void_p, C.POINTER(abi.TensorView)], C.c_int
+            self._check(f(self.h, C.byref(v)))
+            flat = self._wrap(v.ptr, [int(v.shape[0])], v.dtype)
+            views = {n: flat[o:o + int(np.prod(shp))].view(shp) for n, (o, shp) in abi.actor_param_layout(self._actor["actor_dims"], self._actor["critic_dims"]).items()}
+            views["flat"] = flat
+            self._actor_views = views
+        return self._actor_views
+
+    def rollout_row_stride(self):
+        """floats of one row of a trajectory's packed tensor: the T_WRAPPER_PACKED length rounded up to a multiple of 4"""
+        return (self.tensor(abi.T_WRAPPER_PACKED).numel() + 3) // 4 * 4
+
+    def rollout(self, T, obs0=None, deterministic=False, out=None):
+        """T steps of actor -> step inside the engine, one host call, no synchronisation (mqe_rollout).  obs0: the (N, A', D) observation to
+        start from (None: the engine's own T_WRAPPER_OBS, which a reset, a step without a return buffer of the caller's, and every rollout
+        leave current -- NOT a step that was given its own return buffer, as the task wrappers' step() does).  out: a Rollout of the same T whose tensors are written again instead of fresh
+        ones.  Returns a Rollout: views of the one packed tensor (obs (T+1, N, A', D), reward (T, N, A'), done (T, N) bool) + actions
+        (T, N, A', 3), logp (T, N, A'), value (T+1, N, A') or None without a critic."""
+        if getattr(self, "_actor", None) is None:
+            raise RuntimeError("no actor: call create_actor first")
+        T = int(T)
+        N, Aw, D = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
+        dev = self.torch_device
+        critic = self._actor["critic_dims"] is not None
+        if out is None:
+            stride = self.rollout_row_stride()
+            out = Rollout(torch.zeros(max(T, 0) + 1, stride, dtype=torch.float32, device=dev), torch.empty(max(T, 0), N, Aw, 3, dtype=torch.float32, device=dev),
+                          torch.empty(max(T, 0), N, Aw, dtype=torch.float32, device=dev),
+                          torch.empty(max(T, 0) + 1, N, Aw, dtype=torch.float32, device=dev) if critic else None, (N, Aw, D))
+        else:
+            if out.T != T:
+                raise ValueError(f"out holds a trajectory of {out.T} steps, not {T}")
+            if out.packed.stride(1) != 1 or out.packed.stride(0) < out.packed.shape[1]:
+                raise ValueError("out.packed must be (T + 1, row_stride) with unit stride along a row")
+            for name, t, shape in (("actions", out.actions, (T, N, Aw, 3)), ("logp", out.logp, (T, N, Aw)), ("value", out.value, (T + 1, N, Aw))):
+                if t is None:
+                    continue
+                if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+                    raise ValueError(f"out.{name} must be a contiguous float32 device tensor of shape {shape}")
+            if out.actions is None or out.packed.dtype != torch.float32 or not out.packed.is_cuda:
+                raise ValueError("out.packed and out.actions must be float32 device tensors")
+        if obs0 is not None:
+            assert obs0.is_cuda and obs0.dtype == torch.float32 and obs0.is_contiguous() and tuple(obs0.shape) == (N, Aw, D)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+        f = self.lib.mqe_rollout
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        f.restype = C.c_int
+        rc = f(self.h, T, ptr(obs0), ptr(out.packed), int(out.packed.stride(0)), ptr(out.actions), ptr(out.logp), ptr(out.value),
+               abi.ROLLOUT_DETERMINISTIC if deterministic else 0, self._stream())
+        if rc != 0:
+            raise RuntimeError(f"mqe_rollout failed ({rc}): {self.lib.mqe_last_error().decode()}")
+        self._n_policy = getattr(self, "_n_policy", 0) + T
+        return out
 
     def defender_command(self, out):
         self._call("defender_command", C.c_void_p(out.data_ptr()), self._stream())

@@ -397,6 +397,7 @@ class Go1:
     def reset(self):
         """Reset all robots (go1.py:147-151): no physics step, observations recomputed."""
         self.engine.reset_all()
+        self._obs_epoch = getattr(self, "_obs_epoch", 0) + 1      # an observation a task wrapper holds from before is no longer the current one
         self.store_recording(range(self.num_envs))      # reset_idx of every env (legged_robot.py:200); no frame is rendered here
         self._refresh_extras()
         return self.obs_buf
@@ -546,6 +547,7 @@ class Go1:
 
     def set_state(self, state):
         self.engine.load_state(state["engine"])
+        self._obs_epoch = getattr(self, "_obs_epoch", 0) + 1
         self._steps_policy = int(state["steps_policy"])
         self.common_step_counter = int(state["common_step_counter"])
 

@@ -84,7 +84,27 @@ class FusedTaskWrapper(EmptyWrapper):
 
     def reset(self):
         self.env.reset()
-        return self._wobs.clone()
+        self._hold_obs(self._wobs.clone())
+        return self._last_obs
+
+    def _hold_obs(self, obs):
+        """the observation a following rollout() starts from, with the env's observation epoch: Go1.reset() and Go1.set_state() called
+        below this wrapper advance the epoch, and the held observation is then not used"""
+        self._last_obs, self._last_obs_epoch = obs, getattr(self.env, "_obs_epoch", 0)
+
+    def get_state(self):
+        """Go1.get_state() + the observation this wrapper last returned: the engine's blob does not hold it when the step wrote it into a
+        tensor of the caller's (as step() does), and a rollout() after set_state() starts from it"""
+        state = dict(self.env.get_state())
+        obs = getattr(self, "_last_obs", None)
+        current = obs is not None and getattr(self, "_last_obs_epoch", None) == getattr(self.env, "_obs_epoch", 0)
+        state["last_obs"] = obs.detach().cpu().clone() if current else None
+        return state
+
+    def set_state(self, state):
+        self.env.set_state(state)
+        obs = state.get("last_obs")
+        self._hold_obs(obs.to(self._wobs.device).contiguous() if obs is not None else None)
 
     def step(self, action):
         # fresh tensors every step, like the reference: the HIP engine writes obs | reward | done of this step straight into a
@@ -109,4 +129,84 @@ class FusedTaskWrapper(EmptyWrapper):
         # is a live view of engine memory that the next step overwrites) and all three are VIEWS of the one buffer the step wrote:
         # the done flags are its byte tail, seen as torch.bool in place -- no torch kernel runs in a step
         done = snap[n + nr:].view(torch.uint8)[:self.num_envs].view(torch.bool)
-        return snap[:n].view(self._wobs.shape), snap[n:n + nr].view(self._wrew.shape), done, self.env.extras
+        self._hold_obs(snap[:n].view(self._wobs.shape))                # what a following rollout() starts from
+        return self._last_obs, snap[n:n + nr].view(self._wrew.shape), done, self.env.extras
+
+    # ---- on-device rollouts (mqe_rollout): the actor runs inside the engine, T steps per call ---------------------------------------
+    def _rollout_engine(self, what):
+        eng = self.env.engine
+        if not hasattr(eng, "rollout"):
+            raise NotImplementedError(f"{what} runs inside the HIP engine (mqe.engine.hip_engine.HipEngine, mqe_rollout); "
+                                      f"{type(eng).__name__} has no on-device actor")
+        return eng
+
+    def set_actor(self, actor_module, critic_module=None, log_std=None, action_gain=1.0):
+        """The policy a following rollout() evaluates inside the engine: torch.nn.Sequential stacks of Linear / Tanh / ReLU -- actor
+        (obs_dim -> ... -> 3, the mean), optional critic (obs_dim -> ... -> 1) with the same activation -- and log_std (3 values; a tensor
+        or Parameter is read again by every sync_actor(); None: zeros).  Anything else raises ValueError naming the offending layer.
+        Creates the engine's actor and copies the parameters (on the device when the modules live there)."""
+        from mqe.utils.actor_net import mlp_spec
+        D = self.observation_space.shape[0]
+        a_dims, a_act, a_lin = mlp_spec(actor_module, "actor", D, 3)
+        c_dims, c_act, c_lin = (None, None, [])
+        if critic_module is not None:
+            c_dims, c_act, c_lin = mlp_spec(critic_module, "critic", D, 1)
+            if a_act is not None and c_act is not None and a_act != c_act:
+                raise ValueError(f"critic: mixed activations; the actor uses {a_act}, the critic {c_act}: the engine applies one kind to both networks")
+        if log_std is not None and int(torch.as_tensor(log_std).numel()) != 3:
+            raise ValueError(f"log_std must hold 3 values (one per action column), got {tuple(torch.as_tensor(log_std).shape)}")
+        eng = self._rollout_engine("set_actor")
+        eng.create_actor(a_dims, c_dims, activation=a_act or c_act or "tanh", action_gain=action_gain)
+        self._actor_src = (a_lin, c_lin, log_std)
+        self.sync_actor()
+
+    def sync_actor(self):
+        """copies the modules' current parameters into the engine's buffer again (after an optimiser step); device to device when the
+        modules live on the engine's device, no synchronisation"""
+        if getattr(self, "_actor_src", None) is None:
+            raise RuntimeError("sync_actor: no actor (set_actor first)")
+        a_lin, c_lin, log_std = self._actor_src
+        views = self._rollout_engine("sync_actor").actor_params()
+        with torch.no_grad():
+            for who, lin in (("actor", a_lin), ("critic", c_lin)):
+                for l, layer in enumerate(lin):
+                    views[f"{who}.{l}.weight"].copy_(layer.weight.detach(), non_blocking=True)
+                    views[f"{who}.{l}.bias"].copy_(layer.bias.detach(), non_blocking=True)
+            if log_std is None:
+                views["log_std"].zero_()
+            else:
+                views["log_std"].copy_(torch.as_tensor(log_std).detach().reshape(3).to(torch.float32), non_blocking=True)
+
+    def rollout(self, T, deterministic=False):
+        """T steps with the engine's own actor (set_actor) in one call: a Rollout (mqe.engine.hip_engine) whose tensors -- obs (T+1, N, A', D),
+        reward (T, N, A'), done (T, N) bool, actions (T, N, A', 3) unclipped, logp (T, N, A'), value (T+1, N, A') or None -- are fresh memory
+        that belongs to the caller.  Starts from the observation the last step() / reset() / rollout() returned (set_state() of this
+        wrapper restores it; after a Go1-level reset() or set_state() below the wrapper: from the engine's own observation buffer)."""
+        env = self.env
+        eng = self._rollout_engine("rollout")
+        if type(self).step is not FusedTaskWrapper.step:
+            raise NotImplementedError(f"{type(self).__name__}.step transforms the actions in Python before the engine sees them; the engine's actor "
+                                      "feeds the step directly: roll this task out with step()")
+        if getattr(env, "record_now", False):
+            raise NotImplementedError("rollout while recording is live: a frame is due after every step, and the T steps of a rollout are enqueued "
+                                      "as one; pause_recording() first, or step()")
+        if getattr(env, "between_policy_and_physics", None) is not None or getattr(env, "before_policy_tail", None) is not None:
+            raise NotImplementedError("rollout with the sharded runner's hooks set (between_policy_and_physics / before_policy_tail): its "
+                                      "all-gather sits inside every step; each shard rolls out its own envs without them")
+        if env.has_overrides:
+            raise NotImplementedError("rollout runs entirely inside the engine: a Go1 subclass that overrides any of "
+                                      + " / ".join(env._PLUGIN_POINTS) + " is stepped through Go1.step()")
+        if getattr(self, "_actor_src", None) is None:
+            raise RuntimeError("rollout: no actor (set_actor first)")
+        obs0 = getattr(self, "_last_obs", None)
+        if getattr(self, "_last_obs_epoch", None) != getattr(env, "_obs_epoch", 0):
+            obs0 = None       # the env was reset or restored below this wrapper: the engine's own buffer is what there is
+        traj = eng.rollout(T, obs0=obs0.contiguous() if obs0 is not None else None, deterministic=deterministic)
+        T = traj.T
+        dict.__setitem__(self.reward_buffer, "step count", dict.__getitem__(self.reward_buffer, "step count") + T)
+        env._steps_policy = getattr(env, "_steps_policy", 0) + T
+        env.common_step_counter += T
+        env._refresh_extras()
+        self.returned_batch = traj.packed[T, :self._wpack.numel()].clone()      # step()'s layout and length; a copy: a view would keep all T + 1 rows alive after the caller drops the trajectory
+        self._hold_obs(self.returned_batch[:self._wobs.numel()].view(self._wobs.shape))
+        return traj

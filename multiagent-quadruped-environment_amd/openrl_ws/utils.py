@@ -45,6 +45,16 @@ class mqe_openrl_wrapper(Wrapper):
         obs, reward, termination, info = self.env.step((0.5 * actions).clip(-1, 1))
         return obs, reward.unsqueeze(-1), termination.unsqueeze(-1).repeat(1, self.agent_num)
 
+    def set_actor(self, actor_module, critic_module=None, log_std=None):
+        """the policy rollout_torch evaluates inside the engine (FusedTaskWrapper.set_actor) with this adapter's transform: the step
+        receives 0.5 * a, clipped to +-1 inside the engine"""
+        self.env.set_actor(actor_module, critic_module, log_std=log_std, action_gain=0.5)
+
+    def rollout_torch(self, T, deterministic=False):
+        """T steps of step_torch with the engine's own actor in one call (mqe_rollout, action_gain = 0.5): the wrapper's Rollout -- obs
+        (T+1, N, A, D), reward (T, N, A), done (T, N) bool, actions (T, N, A, 3) as the actor sampled them, logp, value -- fresh device memory"""
+        return self.env.rollout(T, deterministic=deterministic)
+
     def step_dlpack(self, actions):
         """Device-resident hand-off for trainers that do not speak torch (replaces the numpy round trip of
         openrl_ws/utils.py:53-67): `actions` is any object with `__dlpack__` living on the env's device; returns objects with
