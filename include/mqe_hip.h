@@ -35,7 +35,8 @@ extern "C" {
  * (new export).  v17 over v16: MQE_T_RIGID_BODY_STATE (new tensor kind before MQE_T_COUNT), mqe_refresh_rigid_body_state and
  * mqe_set_rigid_body_refresh (new exports).  v17, additive (no bump: no limit of mqe_abi_limits, tensor kind, descriptor field or existing call
  * changes): mqe_measure_heights and mqe_set_height_refresh (new exports), MQE_MAX_HEIGHT_POINTS, MQE_HSCAN_SCENERY; mqe_actor_create,
- * mqe_actor_params and mqe_rollout (new exports), mqe_actor_shape, MQE_ACTOR_*, MQE_ROLLOUT_*. */
+ * mqe_actor_params and mqe_rollout (new exports), mqe_actor_shape, MQE_ACTOR_*, MQE_ROLLOUT_*; mqe_rollout_time_outs and mqe_gae (new exports),
+ * MQE_GAE_NORMALIZE. */
 #define MQE_ABI_VERSION 17
 #define MQE_MAX_SPHERES 64    /* feature points of one robot (the capsule model has 32, the exact one 60) */
 #define MQE_MAX_PRIMS 20      /* collision primitives of one robot (Go1: 18) */
@@ -471,6 +472,41 @@ int mqe_actor_params(mqe_sim* s, mqe_tensor_view* out);
  * open step (mqe_step_begin / _head without mqe_step_end). */
 int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* packed_dev, long long row_stride, float* actions_dev, float* logp_dev,
                 float* value_dev, int flags, void* stream);
+/* registers (NULL: removes) a destination for the per-step time-out flags of the following mqe_rollout calls:
+ * time_outs_dev [capacity_steps][N] uint8, row t = MQE_T_TIME_OUT_BUF as step t of the call left it.
+ * MQE_T_TIME_OUT_BUF is overwritten by every step; a learner that bootstraps timed-out episodes (legged_gym / rsl_rl:
+ * reward += gamma * value * time_outs) needs the flag of every step.  While a destination is registered, mqe_rollout enqueues one N-byte
+ * device-to-device copy behind the launches of each step, on the same stream; with none registered its launch sequence is unchanged.  A
+ * rollout with T > capacity_steps is refused with -6 and enqueues nothing.  The registration is host state of the handle only (not part of
+ * mqe_state_save); the memory stays the caller's.  -1 null handle; -6 capacity_steps <= 0 with a non-null pointer.  v17, additive. */
+int mqe_rollout_time_outs(mqe_sim* s, uint8_t* time_outs_dev, int capacity_steps);
+
+/* ---- GAE(lambda) advantages and returns of a trajectory, on the device (csrc/kernels_gae.hpp: k_gae, k_gae_normalize) ----
+ * v17, additive.  The handle supplies the shapes (N, A', D) and owns one scratch buffer; no actor is needed (the values may come from a
+ * torch critic), and the call runs outside or inside an open step.  R' = N x A', row r = env * A' + agent.
+ *   packed_dev, row_stride  a trajectory in mqe_rollout's layout: the reward of step t, row r, is float (N A' D + r) of packed row t + 1,
+ *                           the done byte of step t, env e, is byte e behind the R' rewards of that row
+ *   value_dev      [T + 1][R']: the critic at obs[t]; entry T bootstraps the last step
+ *   time_outs_dev  [T][N] uint8 (mqe_rollout_time_outs) or NULL
+ *   adv_dev, ret_dev  [T][R'] outputs;  stats_dev float[2] or NULL: (mean, std) of the advantages, written by MQE_GAE_NORMALIZE calls only
+ * Per row, t = T - 1 ... 0, adv = 0 in front, all f32 (the exact statement: csrc/kernels_gae.hpp), d = done[t][e], to = time_outs ?
+ * (time_outs[t][e] & d) : 0, v = value[t][r], vn = value[t + 1][r]:
+ *   rr    = to ? fmaf(gamma, v, reward) : reward          rsl_rl's time-out bootstrap with the value of the step's own observation
+ *   delta = (d ? rr : fmaf(gamma, vn, rr)) - v
+ *   adv   = d ? delta : fmaf(gamma * lam, adv, delta)
+ *   ret   = adv + v
+ * MQE_GAE_NORMALIZE: adv_dev becomes (adv - mean) / (std + 1e-8f), mean and unbiased (n - 1) std over all T x R' values, accumulated and
+ * applied in f64 in a fixed order (no atomics: the same bits on every run), rounded to f32 once; ret_dev is computed from the un-normalised
+ * advantage.  EACH SHARD NORMALISES OVER ITS OWN ROWS: a multi-GPU learner that wants global statistics calls without the flag and
+ * normalises itself.  The call never synchronises, except the FIRST normalising call of a handle, which allocates the scratch buffer (2
+ * doubles per 64 rows, freed with the handle) and synchronises once.
+ * Refusals enqueue nothing and write nothing: -1 null handle / packed_dev / value_dev / adv_dev / ret_dev; -6 with a message naming the
+ * argument: T outside 1 .. MQE_ROLLOUT_MAX_STEPS; row_stride below the packed length or not a multiple of 4; a pointer that is not 4-byte
+ * aligned; gamma or lam outside [0, 1] or NaN; MQE_GAE_NORMALIZE with T x R' < 2; an output range that overlaps an input range or another
+ * output; unknown flag bits. */
+#define MQE_GAE_NORMALIZE 1   /* flags bit 0 */
+int mqe_gae(mqe_sim* s, int T, const float* packed_dev, long long row_stride, const float* value_dev, const uint8_t* time_outs_dev,
+            float gamma, float lam, int flags, float* adv_dev, float* ret_dev, float* stats_dev, void* stream);
 
 /* The onboard forward depth camera of LeggedRobotField (legged_robot_field.py:23-93: create_camera_sensor + attach_camera_to_body on the
  * base link, :196-223: get_camera_image_gpu_tensor(IMAGE_DEPTH)) for every robot, from the CURRENT state: out_dev [R][height][width]

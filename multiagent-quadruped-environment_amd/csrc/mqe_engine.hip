@@ -20,6 +20,7 @@
 #include "kernels_terrain_scan.hpp"
 #include "kernels_view.hpp"
 #include "kernels_actor.hpp"
+#include "kernels_gae.hpp"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, const char* a = "") {
@@ -126,6 +127,11 @@ struct mqe_sim {
     float* params = nullptr;      // [n_params]
     float* stage = nullptr;       // [N, A', 3]
   } act;
+  // the per-step time-out record of mqe_rollout (mqe_rollout_time_outs): the caller's [capacity][N] bytes.  Host state of the handle only
+  uint8_t* to_rec = nullptr;
+  int to_rec_cap = 0;
+  // mqe_gae: the (sum, sum of squares) pair of every k_gae workgroup, made by the first MQE_GAE_NORMALIZE call (kernels_gae.hpp)
+  double* gae_part = nullptr;
   // profiling
   bool prof = false, prof_now = false;   // prof_now: this call is one of the sampled ones
   int step_open = 0;                     // 0: no step in flight; 1: after mqe_step_head; 2: after mqe_step_tail / mqe_step_begin (mqe_step_end closes)
@@ -1556,6 +1562,7 @@ extern "C" int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* pack
   if (((uintptr_t)packed_dev & 15) || ((uintptr_t)obs0_dev & 3) || ((uintptr_t)actions_dev & 3) || ((uintptr_t)logp_dev & 3) || ((uintptr_t)value_dev & 3))
     return fail(-6, "mqe_rollout: misaligned pointer (packed_dev: 16 bytes, the others: 4)");
   if (value_dev && s->act.critic.n_layers == 0) return fail(-6, "mqe_rollout: value_dev given, but the actor was created without a critic");
+  if (s->to_rec && T > s->to_rec_cap) return fail(-6, "mqe_rollout: T exceeds capacity_steps of the registered time-out record (mqe_rollout_time_outs)");
   hipStream_t q = (hipStream_t)stream;
   const size_t rows = (size_t)s->N * s->Aw, nobs = rows * s->D;
   // row 0: the starting observation, reward and done bytes zeroed
@@ -1567,6 +1574,8 @@ extern "C" int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* pack
                  value_dev ? value_dev + (size_t)t * rows : nullptr, flags, false, q);
     set_packed(s, packed_dev + (size_t)(t + 1) * row_stride);      // step t returns into row t + 1
     rc = mqe_step(s, s->act.stage, stream);
+    if (rc == 0 && s->to_rec && hipMemcpyAsync(s->to_rec + (size_t)t * s->N, s->st.time_out, (size_t)s->N, hipMemcpyDeviceToDevice, q) != hipSuccess)
+      rc = fail(-100, "HIP error: %s", "mqe_rollout: the copy into the time-out record");
   }
   if (rc == 0 && value_dev) launch_actor(s, packed_dev + (size_t)T * row_stride, nullptr, nullptr, value_dev + (size_t)T * rows, flags, true, q);
   set_packed(s, (float*)s->tens[MQE_T_WRAPPER_PACKED]);
@@ -1574,6 +1583,63 @@ extern "C" int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* pack
   // the engine's own buffer follows the trajectory's last row: MQE_T_WRAPPER_* show what the last step returned, and a following
   // call with obs0_dev == NULL continues from it
   HIPCHK(hipMemcpyAsync(s->tens[MQE_T_WRAPPER_PACKED], packed_dev + (size_t)T * row_stride, (nobs + rows) * 4 + (size_t)s->N, hipMemcpyDeviceToDevice, q));
+  return launched();
+}
+
+extern "C" int mqe_rollout_time_outs(mqe_sim* s, uint8_t* time_outs_dev, int capacity_steps) {
+  if (!s) return fail(-1, "null engine handle");
+  if (time_outs_dev && capacity_steps <= 0) return fail(-6, "mqe_rollout_time_outs: capacity_steps must be positive");
+  s->to_rec = time_outs_dev;
+  s->to_rec_cap = time_outs_dev ? capacity_steps : 0;
+  return 0;
+}
+
+// ---- mqe_gae (include/mqe_hip.h; kernels_gae.hpp) ---------------------------------------------------------------------------------------
+static bool gae_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return a && b && x < y + nb && y < x + na;
+}
+extern "C" int mqe_gae(mqe_sim* s, int T, const float* packed_dev, long long row_stride, const float* value_dev, const uint8_t* time_outs_dev,
+                       float gamma, float lam, int flags, float* adv_dev, float* ret_dev, float* stats_dev, void* stream) {
+  if (!s) return fail(-1, "null engine handle");
+  if (!packed_dev || !value_dev || !adv_dev || !ret_dev) return fail(-1, "mqe_gae: packed_dev, value_dev, adv_dev and ret_dev are required");
+  if (T <= 0 || T > MQE_ROLLOUT_MAX_STEPS) return fail(-6, "mqe_gae: T must be 1 .. MQE_ROLLOUT_MAX_STEPS (4096)");
+  const size_t pf = packed_floats(s);
+  if (row_stride < (long long)pf || row_stride % 4 != 0) return fail(-6, "mqe_gae: row_stride must be a multiple of 4 and at least the MQE_T_WRAPPER_PACKED length");
+  if (((uintptr_t)packed_dev & 3) || ((uintptr_t)value_dev & 3) || ((uintptr_t)adv_dev & 3) || ((uintptr_t)ret_dev & 3) || ((uintptr_t)stats_dev & 3))
+    return fail(-6, "mqe_gae: misaligned pointer (packed_dev, value_dev, adv_dev, ret_dev, stats_dev: 4 bytes)");
+  if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(-6, "mqe_gae: gamma must lie in [0, 1]");
+  if (!(lam >= 0.0f && lam <= 1.0f)) return fail(-6, "mqe_gae: lam must lie in [0, 1]");
+  if (flags & ~MQE_GAE_NORMALIZE) return fail(-6, "mqe_gae: unknown bits in flags (MQE_GAE_NORMALIZE is the only one)");
+  const size_t rows = (size_t)s->N * s->Aw, n = (size_t)T * rows;
+  const bool norm = (flags & MQE_GAE_NORMALIZE) != 0;
+  if (norm && n < 2) return fail(-6, "mqe_gae: MQE_GAE_NORMALIZE needs T x R' >= 2 values (the unbiased std of one value does not exist)");
+  const struct { const void* p; size_t bytes; const char* name; } in[3] = {{packed_dev, ((size_t)T * row_stride + pf) * 4, "packed_dev"},
+      {value_dev, (n + rows) * 4, "value_dev"}, {time_outs_dev, (size_t)T * s->N, "time_outs_dev"}},
+    out[3] = {{adv_dev, n * 4, "adv_dev"}, {ret_dev, n * 4, "ret_dev"}, {stats_dev, 8, "stats_dev"}};
+  for (int o = 0; o < 3; o++) {
+    for (int i = 0; i < 3; i++)
+      if (gae_overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes)) return fail(-6, "mqe_gae: %s overlaps an input range", out[o].name);
+    for (int o2 = o + 1; o2 < 3; o2++)
+      if (gae_overlap(out[o].p, out[o].bytes, out[o2].p, out[o2].bytes)) return fail(-6, "mqe_gae: %s overlaps another output range", out[o].name);
+  }
+  const int nblk = (int)((rows + GAE_THREADS - 1) / GAE_THREADS);
+  if (norm && !s->gae_part) {          // once per handle: dalloc's memset synchronises
+    if (dalloc(s, &s->gae_part, (size_t)2 * nblk)) return fail(-5, "device alloc failed (mqe_gae scratch)");
+  }
+  hipStream_t q = (hipStream_t)stream;
+  const long long rew_off = (long long)rows * s->D;
+  double* part = norm ? s->gae_part : nullptr;
+  if (time_outs_dev)
+    hipLaunchKernelGGL(k_gae<true>, dim3(nblk), dim3(GAE_THREADS), 0, q, packed_dev, row_stride, rew_off, value_dev, time_outs_dev, gamma, lam, T, (int)rows, s->N, s->Aw, adv_dev, ret_dev, part);
+  else
+    hipLaunchKernelGGL(k_gae<false>, dim3(nblk), dim3(GAE_THREADS), 0, q, packed_dev, row_stride, rew_off, value_dev, time_outs_dev, gamma, lam, T, (int)rows, s->N, s->Aw, adv_dev, ret_dev, part);
+  if (norm) {
+    const long long per = (long long)GAE_NORM_THREADS * 8;       // ~8 values per thread
+    const long long want = ((long long)n + per - 1) / per;
+    const int nb = (int)(want < 2048 ? want : 2048);
+    hipLaunchKernelGGL(k_gae_normalize, dim3(nb), dim3(GAE_NORM_THREADS), 0, q, adv_dev, (long long)n, (const double*)part, nblk, stats_dev);
+  }
   return launched();
 }
 

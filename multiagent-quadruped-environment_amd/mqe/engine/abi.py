@@ -114,6 +114,7 @@ class SimDesc(C.Structure):
 ACTOR_MAX_LAYERS, ACTOR_MAX_HIDDEN, ACTOR_MAX_OBS = 4, 256, 128
 ACTOR_TANH, ACTOR_RELU = 0, 1
 ROLLOUT_MAX_STEPS, ROLLOUT_DETERMINISTIC = 4096, 1
+GAE_NORMALIZE = 1            # mqe_gae flags bit 0
 RNG_ACTOR = 0x70000000           # csrc/mqe_common.hpp MQE_RNG_ACTOR: `count` of the actor's draws = RNG_ACTOR + post-physics steps so far
 
 

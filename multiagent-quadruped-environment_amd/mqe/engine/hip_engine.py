@@ -31,9 +31,11 @@ def load_library():
 class Rollout:
     """A trajectory of HipEngine.rollout: `packed` (T+1, row_stride) is the one tensor the steps wrote -- row 0 the starting observation, row
     t + 1 what step t returned (obs | reward | done bytes) -- and obs / reward / done are views of it; actions are the UNCLIPPED samples,
-    logp their log-density, value[t] the critic at obs[t] (value[T]: the bootstrap value), None without a critic."""
+    logp their log-density, value[t] the critic at obs[t] (value[T]: the bootstrap value), None without a critic.  None unless asked for:
+    time_outs (T, N) bool, the time-out flags of every step (rollout(time_outs=True)); advantages / returns (T, N, A') and adv_stats
+    (float32 [2]: mean, std of the advantages before normalisation; normalising calls only), filled by HipEngine.gae."""
 
-    def __init__(self, packed, actions, logp, value, shape):
+    def __init__(self, packed, actions, logp, value, shape, time_outs=None, advantages=None, returns=None, adv_stats=None):
         N, Aw, D = shape
         n, nr = N * Aw * D, N * Aw
         self.packed, self.actions, self.logp, self.value = packed, actions, logp, value
@@ -41,6 +43,8 @@ class Rollout:
         self.obs = packed[:, :n].view(self.T + 1, N, Aw, D)
         self.reward = packed[1:, n:n + nr].view(self.T, N, Aw)
         self.done = packed[1:, n + nr:].view(torch.uint8)[:, :N].view(torch.bool)      # the byte tail of every row, seen as bool in place
+        self.time_outs = time_outs.view(torch.bool) if time_outs is not None and time_outs.dtype == torch.uint8 else time_outs
+        self.advantages, self.returns, self.adv_stats = advantages, returns, adv_stats
 
 
 class HipEngine(EngineBase):
@@ -194,12 +198,14 @@ class HipEngine(EngineBase):
         """floats of one row of a trajectory's packed tensor: the T_WRAPPER_PACKED length rounded up to a multiple of 4"""
         return (self.tensor(abi.T_WRAPPER_PACKED).numel() + 3) // 4 * 4
 
-    def rollout(self, T, obs0=None, deterministic=False, out=None):
+    def rollout(self, T, obs0=None, deterministic=False, out=None, time_outs=False):
         """T steps of actor -> step inside the engine, one host call, no synchronisation (mqe_rollout).  obs0: the (N, A', D) observation to
         start from (None: the engine's own T_WRAPPER_OBS, which a reset, a step without a return buffer of the caller's, and every rollout
         leave current -- NOT a step that was given its own return buffer, as the task wrappers' step() does).  out: a Rollout of the same T whose tensors are written again instead of fresh
         ones.  Returns a Rollout: views of the one packed tensor (obs (T+1, N, A', D), reward (T, N, A'), done (T, N) bool) + actions
-        (T, N, A', 3), logp (T, N, A'), value (T+1, N, A') or None without a critic."""
+        (T, N, A', 3), logp (T, N, A'), value (T+1, N, A') or None without a critic.  time_outs=True: the call also records T_TIME_OUT_BUF as
+        every step left it (mqe_rollout_time_outs: one N-byte device copy per step) into Rollout.time_outs, (T, N) bool -- a fresh tensor,
+        or out.time_outs; without it the call enqueues what it always did and Rollout.time_outs stays as it was (None on a fresh one)."""
         if getattr(self, "_actor", None) is None:
             raise RuntimeError("no actor: call create_actor first")
         T = int(T)
@@ -223,18 +229,77 @@ class HipEngine(EngineBase):
                     raise ValueError(f"out.{name} must be a contiguous float32 device tensor of shape {shape}")
             if out.actions is None or out.packed.dtype != torch.float32 or not out.packed.is_cuda:
                 raise ValueError("out.packed and out.actions must be float32 device tensors")
+        if time_outs:
+            if out.time_outs is None:
+                out.time_outs = torch.zeros(max(T, 0), N, dtype=torch.uint8, device=dev).view(torch.bool)
+            rec = out.time_outs
+            if not (rec.is_cuda and rec.dtype in (torch.bool, torch.uint8) and rec.is_contiguous() and tuple(rec.shape) == (T, N)):
+                raise ValueError(f"out.time_outs must be a contiguous bool or uint8 device tensor of shape {(T, N)}")
         if obs0 is not None:
             assert obs0.is_cuda and obs0.dtype == torch.float32 and obs0.is_contiguous() and tuple(obs0.shape) == (N, Aw, D)
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
         f = self.lib.mqe_rollout
         f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         f.restype = C.c_int
-        rc = f(self.h, T, ptr(obs0), ptr(out.packed), int(out.packed.stride(0)), ptr(out.actions), ptr(out.logp), ptr(out.value),
-               abi.ROLLOUT_DETERMINISTIC if deterministic else 0, self._stream())
+        reg = self.lib.mqe_rollout_time_outs
+        reg.argtypes, reg.restype = [C.c_void_p, C.c_void_p, C.c_int], C.c_int
+        if time_outs:
+            self._check(reg(self.h, ptr(out.time_outs), max(T, 1)))       # T <= 0: mqe_rollout itself refuses
+        try:
+            rc = f(self.h, T, ptr(obs0), ptr(out.packed), int(out.packed.stride(0)), ptr(out.actions), ptr(out.logp), ptr(out.value),
+                   abi.ROLLOUT_DETERMINISTIC if deterministic else 0, self._stream())
+            msg = self.lib.mqe_last_error().decode() if rc != 0 else ""
+        finally:
+            if time_outs:
+                reg(self.h, None, 0)         # the record belongs to this call alone, refused or not
         if rc != 0:
-            raise RuntimeError(f"mqe_rollout failed ({rc}): {self.lib.mqe_last_error().decode()}")
+            raise RuntimeError(f"mqe_rollout failed ({rc}): {msg}")
         self._n_policy = getattr(self, "_n_policy", 0) + T
         return out
+
+    def gae(self, traj, gamma, lam=0.95, normalize=False, out=None):
+        """GAE(lambda) advantages and returns of a Rollout on the device (mqe_gae; csrc/kernels_gae.hpp states the arithmetic): one launch,
+        two with normalize, no synchronisation (the first normalising call of an engine allocates its scratch and synchronises once).
+        traj.value is required ((T+1, N, A'); it may have been written by a torch critic); traj.time_outs, when recorded, bootstraps
+        timed-out steps with gamma * value (rsl_rl); without it every done is a failure.  normalize: advantages become (adv - mean) /
+        (std + 1e-8) over all T x N x A' values of THIS engine's rows (unbiased std), returns stay un-normalised, and traj.adv_stats holds
+        (mean, std).  out: a Rollout whose advantages / returns (/ adv_stats) tensors are written instead of fresh ones.  Fills
+        traj.advantages, traj.returns (T, N, A') and traj.adv_stats (float32 [2], None without normalize); returns traj."""
+        if traj.value is None:
+            raise ValueError("gae: the trajectory has no values (traj.value is None): create the actor with a critic, or fill traj.value")
+        T = int(traj.T)
+        N, Aw, D = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
+        dev = self.torch_device
+        shape = (T, N, Aw)
+        ok = lambda t, shp: t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shp
+        if not ok(traj.value, (T + 1, N, Aw)):
+            raise ValueError(f"traj.value must be a contiguous float32 device tensor of shape {(T + 1, N, Aw)}")
+        if traj.packed.dtype != torch.float32 or not traj.packed.is_cuda or traj.packed.stride(1) != 1:
+            raise ValueError("traj.packed must be a float32 device tensor (T + 1, row_stride) with unit stride along a row")
+        rec = traj.time_outs
+        if rec is not None and not (rec.is_cuda and rec.dtype in (torch.bool, torch.uint8) and rec.is_contiguous() and tuple(rec.shape) == (T, N)):
+            raise ValueError(f"traj.time_outs must be a contiguous bool or uint8 device tensor of shape {(T, N)}")
+        adv, ret, stats = (out.advantages, out.returns, out.adv_stats) if out is not None else (None, None, None)
+        for name, t in (("advantages", adv), ("returns", ret)):
+            if t is not None and not ok(t, shape):
+                raise ValueError(f"out.{name} must be a contiguous float32 device tensor of shape {shape}")
+        if stats is not None and not ok(stats, (2,)):
+            raise ValueError("out.adv_stats must be a contiguous float32 device tensor of shape (2,)")
+        adv = adv if adv is not None else torch.empty(shape, dtype=torch.float32, device=dev)
+        ret = ret if ret is not None else torch.empty(shape, dtype=torch.float32, device=dev)
+        if normalize and stats is None:
+            stats = torch.empty(2, dtype=torch.float32, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+        f = self.lib.mqe_gae
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                      C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        rc = f(self.h, T, ptr(traj.packed), int(traj.packed.stride(0)), ptr(traj.value), ptr(rec), float(gamma), float(lam),
+               abi.GAE_NORMALIZE if normalize else 0, ptr(adv), ptr(ret), ptr(stats if normalize else None), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"mqe_gae failed ({rc}): {self.lib.mqe_last_error().decode()}")
+        traj.advantages, traj.returns, traj.adv_stats = adv, ret, (stats if normalize else None)
+        return traj
 
     def defender_command(self, out):
         self._call("defender_command", C.c_void_p(out.data_ptr()), self._stream())

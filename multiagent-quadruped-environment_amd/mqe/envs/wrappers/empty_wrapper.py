@@ -177,11 +177,15 @@ class FusedTaskWrapper(EmptyWrapper):
             else:
                 views["log_std"].copy_(torch.as_tensor(log_std).detach().reshape(3).to(torch.float32), non_blocking=True)
 
-    def rollout(self, T, deterministic=False):
+    def rollout(self, T, deterministic=False, gamma=None, lam=0.95, normalize_advantages=False):
         """T steps with the engine's own actor (set_actor) in one call: a Rollout (mqe.engine.hip_engine) whose tensors -- obs (T+1, N, A', D),
         reward (T, N, A'), done (T, N) bool, actions (T, N, A', 3) unclipped, logp (T, N, A'), value (T+1, N, A') or None -- are fresh memory
         that belongs to the caller.  Starts from the observation the last step() / reset() / rollout() returned (set_state() of this
-        wrapper restores it; after a Go1-level reset() or set_state() below the wrapper: from the engine's own observation buffer)."""
+        wrapper restores it; after a Go1-level reset() or set_state() below the wrapper: from the engine's own observation buffer).
+        With a gamma (the actor needs a critic: ValueError otherwise, before anything is enqueued) the rollout also records the time-out
+        flags of every step and the engine computes GAE(lam) on the device (HipEngine.gae): time_outs (T, N) bool, advantages and returns
+        (T, N, A'), adv_stats (mean, std; with normalize_advantages, which normalises over this env's own rows) are filled; with
+        gamma=None they are None and the call enqueues nothing more than it always did."""
         env = self.env
         eng = self._rollout_engine("rollout")
         if type(self).step is not FusedTaskWrapper.step:
@@ -198,10 +202,14 @@ class FusedTaskWrapper(EmptyWrapper):
                                       + " / ".join(env._PLUGIN_POINTS) + " is stepped through Go1.step()")
         if getattr(self, "_actor_src", None) is None:
             raise RuntimeError("rollout: no actor (set_actor first)")
+        if gamma is not None and not self._actor_src[1]:
+            raise ValueError("rollout(gamma=...): advantages need values, and the actor was set without a critic (set_actor(actor, critic))")
         obs0 = getattr(self, "_last_obs", None)
         if getattr(self, "_last_obs_epoch", None) != getattr(env, "_obs_epoch", 0):
             obs0 = None       # the env was reset or restored below this wrapper: the engine's own buffer is what there is
-        traj = eng.rollout(T, obs0=obs0.contiguous() if obs0 is not None else None, deterministic=deterministic)
+        traj = eng.rollout(T, obs0=obs0.contiguous() if obs0 is not None else None, deterministic=deterministic, time_outs=gamma is not None)
+        if gamma is not None:
+            eng.gae(traj, gamma, lam=lam, normalize=normalize_advantages)
         T = traj.T
         dict.__setitem__(self.reward_buffer, "step count", dict.__getitem__(self.reward_buffer, "step count") + T)
         env._steps_policy = getattr(env, "_steps_policy", 0) + T

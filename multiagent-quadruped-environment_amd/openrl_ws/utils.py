@@ -50,10 +50,11 @@ class mqe_openrl_wrapper(Wrapper):
         receives 0.5 * a, clipped to +-1 inside the engine"""
         self.env.set_actor(actor_module, critic_module, log_std=log_std, action_gain=0.5)
 
-    def rollout_torch(self, T, deterministic=False):
+    def rollout_torch(self, T, deterministic=False, gamma=None, lam=0.95, normalize_advantages=False):
         """T steps of step_torch with the engine's own actor in one call (mqe_rollout, action_gain = 0.5): the wrapper's Rollout -- obs
-        (T+1, N, A, D), reward (T, N, A), done (T, N) bool, actions (T, N, A, 3) as the actor sampled them, logp, value -- fresh device memory"""
-        return self.env.rollout(T, deterministic=deterministic)
+        (T+1, N, A, D), reward (T, N, A), done (T, N) bool, actions (T, N, A, 3) as the actor sampled them, logp, value -- fresh device memory.
+        gamma / lam / normalize_advantages: FusedTaskWrapper.rollout's -- time_outs, advantages, returns and adv_stats from the engine (mqe_gae)"""
+        return self.env.rollout(T, deterministic=deterministic, gamma=gamma, lam=lam, normalize_advantages=normalize_advantages)
 
     def step_dlpack(self, actions):
         """Device-resident hand-off for trainers that do not speak torch (replaces the numpy round trip of
