@@ -36,7 +36,7 @@ extern "C" {
  * mqe_set_rigid_body_refresh (new exports).  v17, additive (no bump: no limit of mqe_abi_limits, tensor kind, descriptor field or existing call
  * changes): mqe_measure_heights and mqe_set_height_refresh (new exports), MQE_MAX_HEIGHT_POINTS, MQE_HSCAN_SCENERY; mqe_actor_create,
  * mqe_actor_params and mqe_rollout (new exports), mqe_actor_shape, MQE_ACTOR_*, MQE_ROLLOUT_*; mqe_rollout_time_outs and mqe_gae (new exports),
- * MQE_GAE_NORMALIZE. */
+ * MQE_GAE_NORMALIZE; mqe_ppo_grad, mqe_ppo_optimizer and mqe_ppo_adam (new exports), mqe_ppo_loss, MQE_PPO_*. */
 #define MQE_ABI_VERSION 17
 #define MQE_MAX_SPHERES 64    /* feature points of one robot (the capsule model has 32, the exact one 60) */
 #define MQE_MAX_PRIMS 20      /* collision primitives of one robot (Go1: 18) */
@@ -507,6 +507,54 @@ int mqe_rollout_time_outs(mqe_sim* s, uint8_t* time_outs_dev, int capacity_steps
 #define MQE_GAE_NORMALIZE 1   /* flags bit 0 */
 int mqe_gae(mqe_sim* s, int T, const float* packed_dev, long long row_stride, const float* value_dev, const uint8_t* time_outs_dev,
             float gamma, float lam, int flags, float* adv_dev, float* ret_dev, float* stats_dev, void* stream);
+
+/* ---- The PPO update on the engine's own actor-critic, on the device (csrc/kernels_ppo.hpp: k_ppo_grad, k_ppo_reduce, k_ppo_norm, k_ppo_adam) ----
+ * v17, additive.  rollout -> gae -> (grad, adam) per minibatch: the parameters never leave the buffer k_actor reads, nothing synchronises, and
+ * the gradient has the same bits on every run (no floating-point atomics; a fixed grid and fixed-order reductions).  Needs an actor WITH a critic.
+ * mqe_ppo_grad: the clipped-surrogate loss of rsl_rl and its gradient over one minibatch.
+ *   T, packed_dev, row_stride  a trajectory in mqe_rollout's layout; sample s = t * R' + r, 0 <= s < T * R', has its observation at
+ *                              packed_dev + t * row_stride + r * D
+ *   actions_dev [T][R'][3], logp_dev [T][R'], value_dev [T + 1][R'] (the first T rows are v_old), adv_dev, ret_dev [T][R']
+ *   index_dev, first, count    the minibatch, M = count samples: index_dev[first .. first + count) (int32: a slice of a device permutation) or,
+ *                              with index_dev NULL, the range first .. first + count.  INDEX VALUES ARE THE CALLER'S RESPONSIBILITY to keep inside
+ *                              [0, T * R'): the kernel clamps them, so that a bad one cannot read outside the trajectory -- it is not reported
+ *   loss, flags                clip_ratio c, value_coef, entropy_coef, value_clip c_v (used with MQE_PPO_CLIP_VALUE only)
+ *   grad_dev   [n_params] f32 in exactly mqe_actor_params' layout; EVERY element is written by every call (a parameter without gradient: 0)
+ *   stats_dev  NULL or float[MQE_PPO_STATS]: mean L_pi, mean L_v, H, L, mean of logp_old - logp (approximate KL), share of samples with
+ *              |ratio - 1| > clip_ratio; accumulated in f64
+ * Per sample, all f32 (the exact statement, the gradient at the kinks and the layout: csrc/kernels_ppo.hpp):
+ *   mean = actor(obs), v = critic(obs);  z_j = (a_j - mean_j) exp(-log_std_j);  logp = sum_j (-0.5 z_j^2 - log_std_j) - 1.5 ln(2 pi)
+ *   ratio = exp(logp - logp_old);  L_pi = -min(ratio adv, clamp(ratio, 1 - c, 1 + c) adv)
+ *   L_v = (v - ret)^2, with MQE_PPO_CLIP_VALUE max((v - ret)^2, (v_c - ret)^2), v_c = v_old + clamp(v - v_old, -c_v, c_v)
+ *   H = sum_j log_std_j + 1.5 (1 + ln(2 pi));  L = mean(L_pi) + value_coef mean(L_v) - entropy_coef H
+ * The call changes no parameter and no input and never synchronises, except that the FIRST call after mqe_actor_create allocates the
+ * scratch (256 partial gradients; released with the actor) and synchronises once.  A sharded learner all-reduces grad_dev between this call
+ * and mqe_ppo_adam (each shard's gradient carries its own 1 / M: weight by the row counts).
+ * Refusals enqueue nothing and write nothing: -1 null handle or required pointer (everything but index_dev and stats_dev); -6 with a message
+ * naming the argument: no actor, or an actor without a critic; T outside 1 .. MQE_ROLLOUT_MAX_STEPS; row_stride below the packed length or not
+ * a multiple of 4; a misaligned pointer (4 bytes; packed_dev 16); count < 1, first < 0, first + count > T * R' without an index list;
+ * clip_ratio, value_clip or a coefficient that is negative, NaN or infinite; unknown flag bits; grad_dev or stats_dev overlapping an input,
+ * the parameter buffer or each other.
+ * mqe_ppo_optimizer: live views of Adam's two moment buffers, [n_params] f32 each in the parameters' layout, allocated ZEROED on first use
+ * (here or in mqe_ppo_adam) and released with the actor: a new mqe_actor_create drops them.
+ * mqe_ppo_adam: one torch.optim.Adam step (no weight decay, no amsgrad) in place on the parameter buffer, ordered on the stream.  step >= 1
+ * is the CALLER's count -- the engine keeps none: a checkpoint is the three buffers and that integer, nothing goes into mqe_state_save.
+ *   max_grad_norm > 0: g is first scaled by min(1, max_grad_norm / (norm + 1e-6)), norm = the L2 norm over all parameters, accumulated in f64 in a
+ *   fixed order (clip_grad_norm_);  norm_dev, when given, receives the unscaled norm (f32)
+ *   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= (lr / (1 - b1^step)) m / (sqrt(v) / sqrt(1 - b2^step) + eps)
+ *   (the bias corrections and 1 - b are formed on the host in f64 and passed as f32)
+ * -1 null handle / grad_dev; -6: no actor, step < 1, a misaligned pointer, lr / max_grad_norm not finite, a beta outside [0, 1), eps negative or
+ * not finite, grad_dev or norm_dev overlapping the parameter or moment buffers or each other. */
+typedef struct { float clip_ratio, value_coef, entropy_coef, value_clip; } mqe_ppo_loss;
+#define MQE_PPO_CLIP_VALUE 1      /* flags bit 0 */
+#define MQE_PPO_STATS 6
+int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long long row_stride, const float* actions_dev,
+                 const float* logp_dev, const float* value_dev, const float* adv_dev, const float* ret_dev,
+                 const int32_t* index_dev, long long first, long long count, const mqe_ppo_loss* loss, int flags,
+                 float* grad_dev, float* stats_dev, void* stream);
+int mqe_ppo_optimizer(mqe_sim* s, mqe_tensor_view* m_out, mqe_tensor_view* v_out);   /* live views of the two moment buffers */
+int mqe_ppo_adam(mqe_sim* s, const float* grad_dev, long long step, float lr, float beta1, float beta2, float eps,
+                 float max_grad_norm, float* norm_dev, void* stream);
 
 /* The onboard forward depth camera of LeggedRobotField (legged_robot_field.py:23-93: create_camera_sensor + attach_camera_to_body on the
  * base link, :196-223: get_camera_image_gpu_tensor(IMAGE_DEPTH)) for every robot, from the CURRENT state: out_dev [R][height][width]

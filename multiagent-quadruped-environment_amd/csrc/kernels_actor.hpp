@@ -60,7 +60,8 @@ static inline size_t actor_lds_bytes(int ldh) { return (size_t)(2 * ldh + 4) * A
 
 // one layer for the 64 rows of the workgroup: x (LDS, [K][ACT_LD]) -> y (LDS, [Nout][ACT_LD]); W rows uniform per wavefront.
 // The k loop runs in chunks: all scalar weight loads and LDS reads of a chunk are issued before the first FMA waits for them.
-template <bool VEC4>
+// LD: the LDS row stride (k_ppo_grad's 32-row tiles use 33; everything else ACT_LD).
+template <bool VEC4, int LD = ACT_LD>
 __device__ __forceinline__ void actor_layer(const float* __restrict__ W, const float* __restrict__ b, int K, int Nout, const float* x, float* y,
                                             int lane, int wave, int act) {
   for (int o0 = wave * ACT_NB; o0 < Nout; o0 += ACT_WAVES * ACT_NB) {
@@ -83,7 +84,7 @@ __device__ __forceinline__ void actor_layer(const float* __restrict__ W, const f
           wb[j] = *reinterpret_cast<const float4*>(__builtin_assume_aligned(w[j] + k + 4, 16));
         }
 #pragma unroll
-        for (int q = 0; q < 8; q++) xv[q] = x[(k + q) * ACT_LD + lane];
+        for (int q = 0; q < 8; q++) xv[q] = x[(k + q) * LD + lane];
 #pragma unroll
         for (int j = 0; j < ACT_NB; j++) {
           acc[j] = fmaf(wa[j].x, xv[0], acc[j]); acc[j] = fmaf(wa[j].y, xv[1], acc[j]);
@@ -100,14 +101,14 @@ __device__ __forceinline__ void actor_layer(const float* __restrict__ W, const f
 #pragma unroll
         for (int q = 0; q < 4; q++) wv[j][q] = w[j][k + q];
 #pragma unroll
-      for (int q = 0; q < 4; q++) xv[q] = x[(k + q) * ACT_LD + lane];
+      for (int q = 0; q < 4; q++) xv[q] = x[(k + q) * LD + lane];
 #pragma unroll
       for (int j = 0; j < ACT_NB; j++)
 #pragma unroll
         for (int q = 0; q < 4; q++) acc[j] = fmaf(wv[j][q], xv[q], acc[j]);
     }
     for (; k < K; k++) {
-      const float xk = x[k * ACT_LD + lane];
+      const float xk = x[k * LD + lane];
 #pragma unroll
       for (int j = 0; j < ACT_NB; j++) acc[j] = fmaf(w[j][k], xk, acc[j]);
     }
@@ -116,7 +117,7 @@ __device__ __forceinline__ void actor_layer(const float* __restrict__ W, const f
       float v = acc[j];
       if (act == 1) v = tanhf(v);
       else if (act == 2) v = fmaxf(v, 0.0f);
-      if (o0 + j < Nout) y[(o0 + j) * ACT_LD + lane] = v;
+      if (o0 + j < Nout) y[(o0 + j) * LD + lane] = v;
     }
   }
 }

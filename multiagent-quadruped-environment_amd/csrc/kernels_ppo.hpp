@@ -1,0 +1,377 @@
+// kernels_ppo.hpp -- k_ppo_grad / k_ppo_reduce / k_ppo_norm / k_ppo_adam: the clipped-surrogate PPO loss of rsl_rl, its gradient with respect
+// to the engine's actor-critic parameters, and the Adam step on them (mqe_ppo_grad, mqe_ppo_adam; include/mqe_hip.h).
+//
+// THE LOSS.  A sample is a flat index s = t * R' + r into a trajectory in mqe_rollout's layout, 0 <= s < T * R': its observation is the D
+// floats at packed + t * row_stride + r * D; actions[s][3], logp_old[s], v_old = value[s] (the first T rows of the [T + 1][R'] array), adv[s],
+// ret[s].  A minibatch is M = count samples: index[first .. first + count) when an int32 index list is given (a slice of a device
+// permutation; a value outside [0, T R') is the caller's error -- the kernel clamps it, so that it cannot read outside the trajectory),
+// otherwise the contiguous range first .. first + count.  Per sample, all f32:
+//     mean = actor(obs), v = critic(obs)        the fmaf chains of k_actor (kernels_actor.hpp: actor_layer, unchanged)
+//     z_j  = (a_j - mean_j) * exp(-log_std_j)
+//     logp = sum_j (-0.5 z_j^2 - log_std_j) - 1.5 ln(2 pi)        (j ascending, from 0, as k_actor);   ratio = exp(logp - logp_old)
+//     L_pi = -min(ratio * adv, clamp(ratio, 1 - c, 1 + c) * adv)
+//     L_v  = (v - ret)^2;   with MQE_PPO_CLIP_VALUE:  max((v - ret)^2, (v_c - ret)^2),  v_c = v_old + clamp(v - v_old, -c_v, c_v)
+//     H    = sum_j log_std_j + 1.5 (1 + ln(2 pi))                   (state-independent)
+//     L    = mean(L_pi) + value_coef * mean(L_v) - entropy_coef * H
+// THE GRADIENT is what autograd gives away from the kinks; the kinks are decided by selects, never by products with a mask:
+//     dL/dlogp       = 0 when (adv > 0 and ratio > 1 + c) or (adv < 0 and ratio < 1 - c), otherwise -adv * ratio * (1 / M)
+//     dlogp/dmean_j  = z_j * exp(-log_std_j);    dlogp/dlog_std_j = z_j^2 - 1;    log_std_j additionally receives -entropy_coef
+//     dL/dv          = value_coef * (1 / M) * { 2 (v - ret) when the unclipped square is the larger one (ties: unclipped) or the flag is off;
+//                                               2 (v_c - ret) when |v - v_old| < c_v;  0 otherwise }
+//     hidden layers:   delta_in = (W^T delta_out) * (1 - y^2) (tanh, from the stored output y) or (y > 0 ? . : 0) (relu)
+// 1 / M is one f32 value, formed on the host as (float)(1.0 / M).
+//
+// LAYOUT.  A workgroup is 1024 threads = 16 wavefronts (k_actor's) and walks row tiles of RT samples: tile i of the minibatch is samples
+// i RT .. i RT + RT - 1; workgroup b of G = min(tiles, PPO_MAX_WG) takes tiles b, b + G, b + 2 G, ... in that order (a fixed grid: a function
+// of count, the tile height and PPO_MAX_WG alone).  LDS holds, as [k][row] with an odd row stride, the observation and EVERY layer output of
+// ONE network -- the backward pass needs them -- and the two networks run one after the other (actor forward, actor head, actor backward,
+// critic forward on the observation that is still there, critic head, critic backward).  No separate delta buffers: the delta of layer l - 1
+// overwrites the stored output of layer l - 1 IN PLACE, element by element by the thread that reads that element for the activation
+// derivative, after the weight gradient of layer l (the last reader of that output as an input) is done.  So the footprint is
+// (D + sum of hidden widths + 4) rows; RT = 64 (stride 65) when that fits 160 KiB -- every network up to 128 x 128 x 128, the 64 x 64 case
+// included -- else RT = 32 (stride 33: lanes 32 .. 63 repeat rows 0 .. 31 in the lane = row phases), which holds the widest accepted stack
+// (128 + 3 x 256 + 4 rows = 116 KiB).  A 16-row tile is never needed.
+// FORWARD: actor_layer, lane = row, weights wave-uniform.  BACKWARD-DATA (ppo_dx): lane = row as well; a wavefront owns four input neurons k
+// and runs  acc = 0; for o ascending: acc = fmaf(W[o][k], delta[o], acc)  -- one LDS read feeds four FMAs, weights wave-uniform again.
+// WEIGHT GRADIENT (ppo_dw): dW[o][k] = sum over rows of delta[o][row] x[k][row] is a reduction ACROSS the lanes of the other phases, so the
+// threads are mapped again: a thread owns a 4 x 4 block (o = 4 ob .. 4 ob + 3; k = kb, kb + nbk, kb + 2 nbk, kb + 3 nbk with nbk = ceil(K / 4), so that
+// consecutive lanes read consecutive LDS banks and store consecutive floats) and runs, per element, ONE fmaf chain over the rows in ascending
+// order:  acc = fmaf(delta[o][row], x[k][row], acc)  (db: acc += delta[o][row]).  The chain continues over all tiles of the workgroup: the
+// accumulators start at 0 on the workgroup's first tile and are otherwise read from, and written back to, the workgroup's partial
+// gradient in per-handle scratch by the thread that owns them (L2-resident; no atomics, the same thread every time).  8 LDS reads feed 16
+// FMAs.  WHY VALU AND NOT THE f32 MFMA: on this chip v_mfma_f32_32x32x2_f32 runs at 64 FLOP / clk / SIMD, exactly the f32 vector rate, so the
+// matrix cores buy no arithmetic; they would save LDS reads (2 per 32 x 32 x 2 step against 8 per 16 FMAs) at the price of operands padded
+// to 32 x 32 for widths such as 3, 7, 14 and 17 and of rows (the MFMA's k) fed from two LDS arrays through a lane layout that the lane = row
+// phases do not produce.  Per 64-row tile of a 64 x 64 layer: 2048 wave-level ds_read (4096 clk of the CU's LDS port) against 4096
+// wave-level FMAs (2048 clk over 4 SIMDs): the weight gradient is LDS-bound at about twice its arithmetic time, which is what DESIGN 3.5's
+// roofline carries.
+// REDUCTION (k_ppo_reduce, a second launch): grad[i] = (float) sum over workgroups b ascending of (double) partial[b][i]; the statistics
+// and the three log_std gradients are f64 per lane of wavefront 0 over the workgroup's tiles, added across lanes by the xor butterfly
+// 32, 16, ..., 1 (k_gae's), stored per workgroup and added in workgroup order.  No floating-point atomics anywhere: the same bits every run.
+// Rows past the end of the minibatch load the last sample (clamped) and carry delta = 0: they contribute +0 to every chain.
+//
+// ADAM (k_ppo_norm, k_ppo_adam).  norm = sqrt(sum g_i^2) in f64: thread t of ONE 1024-thread workgroup adds i = t, t + 1024, ... ascending
+// (fma), then a fixed LDS tree (stride 512, 256, ..., 1).  scale = min(1, max_grad_norm / ((float) norm + 1e-6f)) (f32; 1 when clipping is off).
+// Per element, f32:  g = grad * scale;  m = fmaf(b1, m, (1 - b1) * g);  v = fmaf(b2, v, ((1 - b2) * g) * g);
+//     p = p - (step_size * m) / (sqrtf(v) / bc2s + eps)     step_size = lr / (1 - b1^step), bc2s = sqrt(1 - b2^step), 1 - b1, 1 - b2: formed on the
+// host in f64 and passed as f32.
+#pragma once
+#include "mqe_common.hpp"
+#include "kernels_actor.hpp"
+
+#define PPO_MAX_WG 256                 // persistent workgroups of k_ppo_grad at most: the chip's 256 CUs, one 1024-thread workgroup each
+#define PPO_LDS_LIMIT (160 * 1024)
+#define PPO_PST 8                      // doubles per workgroup in the statistics scratch: L_pi, L_v, logp_old - logp, clipped, dlog_std[3], pad
+#define PPO_REDUCE_THREADS 256
+#define PPO_ADAM_THREADS 256
+#define PPO_NORM_THREADS 1024
+
+// rows of the LDS image: observation, every hidden output of the larger network, 4 output rows (mean 0 .. 2, value)
+static inline int ppo_lds_rows(const ActorNet& a, const ActorNet& c, int D) {
+  int ha = 0, hc = 0;
+  for (int l = 1; l < a.n_layers; l++) ha += a.dims[l];
+  for (int l = 1; l < c.n_layers; l++) hc += c.dims[l];
+  return D + (ha > hc ? ha : hc) + 4;
+}
+static inline size_t ppo_lds_bytes(int rows, int rt) { return ((size_t)rows * (rt + 1) + 2 + 2 * 64) * sizeof(float); }      // + the tile's sample indices (64-bit)
+
+// backward-data of one layer, in place: y (the stored output of the layer below, [K][LD]) becomes its delta
+template <int LD>
+__device__ __forceinline__ void ppo_dx(const float* __restrict__ W, int K, int Nout, const float* dY, float* y, int row, int wave, int relu) {
+  for (int k0 = wave * ACT_NB; k0 < K; k0 += ACT_WAVES * ACT_NB) {
+    int kk[ACT_NB];
+    float acc[ACT_NB];
+#pragma unroll
+    for (int j = 0; j < ACT_NB; j++) {
+      kk[j] = min(k0 + j, K - 1);      // a short last block recomputes the last neuron and does not store it
+      acc[j] = 0.0f;
+    }
+    int o = 0;
+    for (; o + 4 <= Nout; o += 4) {
+      float d[4], w[4][ACT_NB];
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        d[q] = dY[(o + q) * LD + row];
+#pragma unroll
+        for (int j = 0; j < ACT_NB; j++) w[q][j] = W[(size_t)(o + q) * K + kk[j]];
+      }
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int j = 0; j < ACT_NB; j++) acc[j] = fmaf(w[q][j], d[q], acc[j]);
+    }
+    for (; o < Nout; o++) {
+      const float d = dY[o * LD + row];
+#pragma unroll
+      for (int j = 0; j < ACT_NB; j++) acc[j] = fmaf(W[(size_t)o * K + kk[j]], d, acc[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < ACT_NB; j++) {
+      if (k0 + j < K) {
+        const float yv = y[(k0 + j) * LD + row];
+        y[(k0 + j) * LD + row] = relu ? (yv > 0.0f ? acc[j] : 0.0f) : acc[j] * fmaf(-yv, yv, 1.0f);
+      }
+    }
+  }
+}
+
+// weight and bias gradient of one layer: the workgroup's partial (gW [Nout][K], gB [Nout]) continues its per-element fmaf chain over the RT rows
+template <int LD, int RT>
+__device__ __forceinline__ void ppo_dw(const float* dY, const float* x, int K, int Nout, float* __restrict__ gW, float* __restrict__ gB, bool first,
+                                       int tid) {
+  const int nbk = (K + 3) >> 2, nbo = (Nout + 3) >> 2;
+  for (int blk = tid; blk < nbk * nbo; blk += ACT_THREADS) {
+    const int ob = blk / nbk, kb = blk - ob * nbk;
+    int oo[4], kk[4];
+    bool ov[4], kv[4];
+    float acc[4][4], accb[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      ov[j] = ob * 4 + j < Nout; oo[j] = ov[j] ? ob * 4 + j : Nout - 1;
+      kv[j] = kb + j * nbk < K;  kk[j] = kv[j] ? kb + j * nbk : K - 1;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      accb[j] = (!first && ov[j] && kb == 0) ? gB[oo[j]] : 0.0f;
+#pragma unroll
+      for (int q = 0; q < 4; q++) acc[j][q] = (!first && ov[j] && kv[q]) ? gW[(size_t)oo[j] * K + kk[q]] : 0.0f;
+    }
+#pragma unroll 4
+    for (int r = 0; r < RT; r++) {
+      float dy[4], xv[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) { dy[j] = dY[oo[j] * LD + r]; xv[j] = x[kk[j] * LD + r]; }
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        accb[j] += dy[j];
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[j][q] = fmaf(dy[j], xv[q], acc[j][q]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (ov[j] && kb == 0) gB[oo[j]] = accb[j];
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+        if (ov[j] && kv[q]) gW[(size_t)oo[j] * K + kk[q]] = acc[j][q];
+    }
+  }
+}
+
+struct PpoNets { ActorNet actor, critic; };      // read from device memory (wave-uniform loads at the layer loops): 20 words that need no registers
+
+// forward of one network with every layer output kept: observation at lds[0], hidden output l at hid + (sum of the widths below it) rows,
+// the last layer at `out`
+template <int LD>
+__device__ __forceinline__ void ppo_forward(const ActorNet& net, const float* __restrict__ params, float* lds, int D, float* out, int row, int wave,
+                                            int hidden_act) {
+  const float* x = lds;
+  float* y = lds + (size_t)D * LD;
+  for (int l = 0; l < net.n_layers; l++) {
+    const bool last = l + 1 == net.n_layers;
+    const int K = net.dims[l], Nout = net.dims[l + 1];
+    const float* W = params + net.w_off[l];
+    const float* b = W + (size_t)K * Nout;
+    float* dst = last ? out : y;
+    if (((K | net.w_off[l]) & 3) == 0) actor_layer<true, LD>(W, b, K, Nout, x, dst, row, wave, last ? 0 : hidden_act);
+    else actor_layer<false, LD>(W, b, K, Nout, x, dst, row, wave, last ? 0 : hidden_act);
+    __syncthreads();
+    x = y;
+    y += (size_t)Nout * LD;
+  }
+}
+
+// backward of one network: `out` holds the delta of the last layer; walks the layers down, weight gradient first, then the delta below in place
+template <int LD, int RT>
+__device__ __forceinline__ void ppo_backward(const ActorNet& net, const float* __restrict__ params, float* __restrict__ part, float* lds, int D,
+                                             float* out, int row, int wave, int tid, int relu, bool first) {
+  int below = 0;                       // rows under the input of layer l: D + hidden widths 1 .. l - 1, minus the input's own
+  for (int l = 1; l + 1 < net.n_layers; l++) below += net.dims[l];
+  // x of the last layer starts at row D + (sum of hidden widths but the last); for a single-layer network it is the observation
+  float* dY = out;
+  for (int l = net.n_layers - 1; l >= 0; l--) {
+    const int K = net.dims[l], Nout = net.dims[l + 1];
+    float* x = l == 0 ? lds : lds + (size_t)(D + below) * LD;
+    ppo_dw<LD, RT>(dY, x, K, Nout, part + net.w_off[l], part + net.w_off[l] + (size_t)K * Nout, first, tid);
+    __syncthreads();
+    if (l == 0) break;
+    ppo_dx<LD>(params + net.w_off[l], K, Nout, dY, x, row, wave, relu);
+    __syncthreads();
+    dY = x;
+    if (l >= 2) below -= net.dims[l - 1];
+  }
+}
+
+struct PpoLoss { float clip, value_coef, entropy_coef, value_clip, inv_m; int clip_value; };
+
+template <int RT>
+__global__ void __launch_bounds__(ACT_THREADS) k_ppo_grad(const float* __restrict__ params, const PpoNets* __restrict__ nets, int log_std_off, int n_params, int D, int rows_lds,
+                                                          int relu, const float* __restrict__ packed, long long stride, int rows, long long n_total,
+                                                          const float* __restrict__ actions, const float* __restrict__ logp_old,
+                                                          const float* __restrict__ value, const float* __restrict__ adv, const float* __restrict__ ret,
+                                                          const int32_t* __restrict__ index, long long first, long long count, PpoLoss ls,
+                                                          float* __restrict__ part_all, double* __restrict__ pst) {
+  constexpr int LD = RT + 1;
+  extern __shared__ __attribute__((aligned(16))) float ppo_lds[];
+  float* out = ppo_lds + (size_t)(rows_lds - 4) * LD;
+  long long* srow = reinterpret_cast<long long*>(ppo_lds + (size_t)rows_lds * LD + (((size_t)rows_lds * LD) & 1));      // 8-byte aligned
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int row = lane & (RT - 1);
+  const int hidden_act = relu ? 2 : 1;
+  float* part = part_all + (size_t)blockIdx.x * n_params;
+  const long long tiles = (count + RT - 1) / RT;
+  double sLpi = 0.0, sLv = 0.0, sKl = 0.0, sClip = 0.0, gls[3] = {0.0, 0.0, 0.0};
+  bool first_tile = true;
+  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    // the tile's samples: past the end of the minibatch the last one again
+    if (tid < RT) {
+      long long i = tile * RT + tid;
+      if (i > count - 1) i = count - 1;
+      long long s = first + i;
+      if (index != nullptr) {
+        s = index[first + i];
+        s = s < 0 ? 0 : (s > n_total - 1 ? n_total - 1 : s);
+      }
+      srow[tid] = s;
+    }
+    __syncthreads();
+    for (int e = tid; e < RT * D; e += ACT_THREADS) {
+      const int r = e / D, k = e - r * D;
+      const long long s = srow[r];
+      const long long t = s / rows, rr = s - t * rows;
+      ppo_lds[k * LD + r] = packed[(size_t)t * (size_t)stride + (size_t)rr * D + k];
+    }
+    __syncthreads();
+    const bool valid = tile * RT + lane < count && lane < RT;
+    // ---- actor ----
+    ppo_forward<LD>(nets->actor, params, ppo_lds, D, out, row, wave, hidden_act);
+    if (wave == 0) {
+      const long long s = srow[row];
+      const float lpo = logp_old[s], ad = adv[s];
+      float z[3], inv[3], lp = 0.0f;
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        const float lsj = params[log_std_off + j];
+        inv[j] = expf(-lsj);
+        z[j] = (actions[(size_t)s * 3 + j] - out[j * LD + row]) * inv[j];
+        lp += -0.5f * z[j] * z[j] - lsj;
+      }
+      lp -= 3.0f * 0.9189385332046727f;       // 3 x 0.5 ln(2 pi)
+      const float ratio = expf(lp - lpo);
+      const float lo = 1.0f - ls.clip, hi = 1.0f + ls.clip;
+      const float Lpi = -fminf(ratio * ad, fminf(fmaxf(ratio, lo), hi) * ad);
+      const bool gate = (ad > 0.0f && ratio > hi) || (ad < 0.0f && ratio < lo);
+      const float dlp = gate ? 0.0f : -ad * ratio * ls.inv_m;
+      if (lane < RT) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) out[j * LD + row] = valid ? dlp * z[j] * inv[j] : 0.0f;
+      }
+      if (valid) {
+        sLpi += (double)Lpi;
+        sKl += (double)(lpo - lp);
+        sClip += fabsf(ratio - 1.0f) > ls.clip ? 1.0 : 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; j++) gls[j] += (double)(dlp * (z[j] * z[j] - 1.0f));
+      }
+    }
+    __syncthreads();
+    ppo_backward<LD, RT>(nets->actor, params, part, ppo_lds, D, out, row, wave, tid, relu, first_tile);
+    // ---- critic: the observation is still in place ----
+    ppo_forward<LD>(nets->critic, params, ppo_lds, D, out + 3 * LD, row, wave, hidden_act);
+    if (wave == 0) {
+      const long long s = srow[row];
+      const float v = out[3 * LD + row], rt = ret[s];
+      const float d1 = v - rt, u = d1 * d1;
+      float Lv = u, dv = 2.0f * d1;
+      if (ls.clip_value) {
+        const float vo = value[s];
+        const float dvo = v - vo;
+        const float vc = vo + fminf(fmaxf(dvo, -ls.value_clip), ls.value_clip);
+        const float d2 = vc - rt, cl = d2 * d2;
+        Lv = fmaxf(u, cl);
+        dv = u >= cl ? 2.0f * d1 : (fabsf(dvo) < ls.value_clip ? 2.0f * d2 : 0.0f);
+      }
+      if (lane < RT) out[3 * LD + row] = valid ? ls.value_coef * ls.inv_m * dv : 0.0f;
+      if (valid) sLv += (double)Lv;
+    }
+    __syncthreads();
+    ppo_backward<LD, RT>(nets->critic, params, part, ppo_lds, D, out + 3 * LD, row, wave, tid, relu, first_tile);
+    first_tile = false;
+  }
+  if (wave != 0) return;
+  double v[7] = {sLpi, sLv, sKl, sClip, gls[0], gls[1], gls[2]};
+#pragma unroll
+  for (int q = 0; q < 7; q++) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v[q] += __shfl_xor(v[q], m);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < 7; q++) pst[(size_t)blockIdx.x * PPO_PST + q] = v[q];
+  }
+}
+
+// grad and the statistics from the G workgroups' partials, in workgroup order
+__global__ void __launch_bounds__(PPO_REDUCE_THREADS) k_ppo_reduce(const float* __restrict__ part, const double* __restrict__ pst, int G, int n_params,
+                                                                   int log_std_off, long long M, float value_coef, float entropy_coef,
+                                                                   const float* __restrict__ params, float* __restrict__ grad, float* __restrict__ stats) {
+  const int i = blockIdx.x * PPO_REDUCE_THREADS + threadIdx.x;
+  if (i < log_std_off) {
+    double a = 0.0;
+    for (int b = 0; b < G; b++) a += (double)part[(size_t)b * n_params + i];
+    grad[i] = (float)a;
+  } else if (i < n_params) {
+    double a = 0.0;
+    for (int b = 0; b < G; b++) a += pst[(size_t)b * PPO_PST + 4 + (i - log_std_off)];
+    grad[i] = (float)(a - (double)entropy_coef);
+  }
+  if (i == 0 && stats != nullptr) {
+    double S[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int b = 0; b < G; b++)
+      for (int q = 0; q < 4; q++) S[q] += pst[(size_t)b * PPO_PST + q];
+    const double n = (double)M;
+    double H = 1.5 * (1.0 + 1.8378770664093453);        // ln(2 pi)
+    for (int j = 0; j < 3; j++) H += (double)params[log_std_off + j];
+    const double Lpi = S[0] / n, Lv = S[1] / n;
+    stats[0] = (float)Lpi;
+    stats[1] = (float)Lv;
+    stats[2] = (float)H;
+    stats[3] = (float)(Lpi + (double)value_coef * Lv - (double)entropy_coef * H);
+    stats[4] = (float)(S[2] / n);
+    stats[5] = (float)(S[3] / n);
+  }
+}
+
+// the L2 norm of the gradient in f64, a fixed order: one workgroup
+__global__ void __launch_bounds__(PPO_NORM_THREADS) k_ppo_norm(const float* __restrict__ grad, int n, double* __restrict__ norm_out, float* __restrict__ norm_dev) {
+  __shared__ double red[PPO_NORM_THREADS];
+  double a = 0.0;
+  for (int i = threadIdx.x; i < n; i += PPO_NORM_THREADS) a = fma((double)grad[i], (double)grad[i], a);
+  red[threadIdx.x] = a;
+  __syncthreads();
+  for (int w = PPO_NORM_THREADS / 2; w >= 1; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double nn = sqrt(red[0]);
+    norm_out[0] = nn;
+    if (norm_dev != nullptr) norm_dev[0] = (float)nn;
+  }
+}
+
+struct PpoAdam { float b1, b2, omb1, omb2, step_size, bc2s, eps, max_norm; };
+
+__global__ void __launch_bounds__(PPO_ADAM_THREADS) k_ppo_adam(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ grad,
+                                                               int n, const double* __restrict__ norm, PpoAdam a) {
+  const int i = blockIdx.x * PPO_ADAM_THREADS + threadIdx.x;
+  if (i >= n) return;
+  float scale = 1.0f;
+  if (a.max_norm > 0.0f) scale = fminf(1.0f, a.max_norm / ((float)norm[0] + 1e-6f));
+  const float g = grad[i] * scale;
+  const float mi = fmaf(a.b1, m[i], a.omb1 * g);
+  const float vi = fmaf(a.b2, v[i], (a.omb2 * g) * g);
+  m[i] = mi;
+  v[i] = vi;
+  p[i] = p[i] - (a.step_size * mi) / (sqrtf(vi) / a.bc2s + a.eps);
+}

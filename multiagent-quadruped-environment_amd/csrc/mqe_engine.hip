@@ -21,6 +21,7 @@
 #include "kernels_view.hpp"
 #include "kernels_actor.hpp"
 #include "kernels_gae.hpp"
+#include "kernels_ppo.hpp"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, const char* a = "") {
@@ -132,6 +133,17 @@ struct mqe_sim {
   int to_rec_cap = 0;
   // mqe_gae: the (sum, sum of squares) pair of every k_gae workgroup, made by the first MQE_GAE_NORMALIZE call (kernels_gae.hpp)
   double* gae_part = nullptr;
+  // mqe_ppo_grad / mqe_ppo_adam (kernels_ppo.hpp): the workgroups' partial gradients [PPO_MAX_WG][n_params] and statistics, made by the first
+  // mqe_ppo_grad of an actor with the row tile its shapes allow; the two Adam moment buffers [2][n_params] and the f64 norm, made zeroed by the
+  // first mqe_ppo_optimizer / mqe_ppo_adam.  All four belong to the actor: mqe_actor_create drops them.  The trainer's, never in state_bufs
+  struct Ppo {
+    float* part = nullptr;
+    double* pst = nullptr;
+    int32_t* nets = nullptr;      // the two ActorNet shapes as k_ppo_grad reads them
+    int rt = 0, lds_rows = 0;
+    float* moments = nullptr;
+    double* norm = nullptr;
+  } ppo;
   // profiling
   bool prof = false, prof_now = false;   // prof_now: this call is one of the sampled ones
   int step_open = 0;                     // 0: no step in flight; 1: after mqe_step_head; 2: after mqe_step_tail / mqe_step_begin (mqe_step_end closes)
@@ -1499,13 +1511,14 @@ static int actor_net_shape(const char* who, int layers, const int32_t* dims, int
   return 0;
 }
 static void actor_release(mqe_sim* s) {
-  for (float* p : {s->act.params, s->act.stage}) {
+  for (void* p : {(void*)s->act.params, (void*)s->act.stage, (void*)s->ppo.part, (void*)s->ppo.pst, (void*)s->ppo.nets, (void*)s->ppo.moments, (void*)s->ppo.norm}) {
     if (!p) continue;
     for (size_t i = 0; i < s->allocs.size(); i++)
       if (s->allocs[i] == p) { s->allocs.erase(s->allocs.begin() + i); break; }
     hipFree(p);         // waits for the launches that still read it
   }
   s->act = mqe_sim::Actor();
+  s->ppo = mqe_sim::Ppo();
 }
 extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
   if (!s || !sh) return fail(-1, "mqe_actor_create: null argument");
@@ -1640,6 +1653,137 @@ extern "C" int mqe_gae(mqe_sim* s, int T, const float* packed_dev, long long row
     const int nb = (int)(want < 2048 ? want : 2048);
     hipLaunchKernelGGL(k_gae_normalize, dim3(nb), dim3(GAE_NORM_THREADS), 0, q, adv_dev, (long long)n, (const double*)part, nblk, stats_dev);
   }
+  return launched();
+}
+
+// ---- mqe_ppo_grad / mqe_ppo_optimizer / mqe_ppo_adam (include/mqe_hip.h; kernels_ppo.hpp) ------------------------------------------------------
+// the library is built without NaN / infinity semantics (-fno-honor-nans, -fno-honor-infinities): float arguments are ASSUMED finite and a
+// test on their value, or on bits copied from it, may be folded away -- so the arguments are classified from their bytes, read as volatile
+static uint32_t ppo_bits(const void* p) {
+  const volatile unsigned char* b = (const volatile unsigned char*)p;
+  return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+}
+static bool ppo_not_finite(const float* x) { return (ppo_bits(x) & 0x7f800000u) == 0x7f800000u; }
+static bool ppo_bad_coef(const float* x) {          // negative, NaN or infinite
+  const uint32_t u = ppo_bits(x);
+  return (u & 0x7f800000u) == 0x7f800000u || ((u >> 31) != 0 && (u << 1) != 0);
+}
+extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long long row_stride, const float* actions_dev, const float* logp_dev,
+                            const float* value_dev, const float* adv_dev, const float* ret_dev, const int32_t* index_dev, long long first,
+                            long long count, const mqe_ppo_loss* loss, int flags, float* grad_dev, float* stats_dev, void* stream) {
+  if (!s) return fail(-1, "null engine handle");
+  if (!packed_dev || !actions_dev || !logp_dev || !value_dev || !adv_dev || !ret_dev || !loss || !grad_dev)
+    return fail(-1, "mqe_ppo_grad: packed_dev, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, loss and grad_dev are required");
+  if (!s->act.on) return fail(-6, "mqe_ppo_grad: no actor (mqe_actor_create)");
+  if (s->act.critic.n_layers == 0) return fail(-6, "mqe_ppo_grad: the actor was created without a critic: the loss has a value term");
+  if (T <= 0 || T > MQE_ROLLOUT_MAX_STEPS) return fail(-6, "mqe_ppo_grad: T must be 1 .. MQE_ROLLOUT_MAX_STEPS (4096)");
+  const size_t pf = packed_floats(s);
+  if (row_stride < (long long)pf || row_stride % 4 != 0) return fail(-6, "mqe_ppo_grad: row_stride must be a multiple of 4 and at least the MQE_T_WRAPPER_PACKED length");
+  if (((uintptr_t)packed_dev & 15) || ((uintptr_t)actions_dev & 3) || ((uintptr_t)logp_dev & 3) || ((uintptr_t)value_dev & 3) || ((uintptr_t)adv_dev & 3) ||
+      ((uintptr_t)ret_dev & 3) || ((uintptr_t)index_dev & 3) || ((uintptr_t)grad_dev & 3) || ((uintptr_t)stats_dev & 3))
+    return fail(-6, "mqe_ppo_grad: misaligned pointer (packed_dev: 16 bytes, the others: 4)");
+  const size_t rows = (size_t)s->N * s->Aw, n = (size_t)T * rows;
+  if (count < 1) return fail(-6, "mqe_ppo_grad: count must be at least 1");
+  if (first < 0) return fail(-6, "mqe_ppo_grad: first must not be negative");
+  if (first > (1LL << 40) || count > (1LL << 40)) return fail(-6, "mqe_ppo_grad: first / count beyond any trajectory");
+  if (!index_dev && first + count > (long long)n) return fail(-6, "mqe_ppo_grad: first + count exceeds the T x R' samples of the trajectory");
+  if (ppo_bad_coef(&loss->clip_ratio)) return fail(-6, "mqe_ppo_grad: clip_ratio must be finite and not negative");
+  if (ppo_bad_coef(&loss->value_coef)) return fail(-6, "mqe_ppo_grad: value_coef must be finite and not negative");
+  if (ppo_bad_coef(&loss->entropy_coef)) return fail(-6, "mqe_ppo_grad: entropy_coef must be finite and not negative");
+  if (ppo_bad_coef(&loss->value_clip)) return fail(-6, "mqe_ppo_grad: value_clip must be finite and not negative");
+  if (flags & ~MQE_PPO_CLIP_VALUE) return fail(-6, "mqe_ppo_grad: unknown bits in flags (MQE_PPO_CLIP_VALUE is the only one)");
+  const mqe_sim::Actor& a = s->act;
+  const struct { const void* p; size_t bytes; } in[8] = {{packed_dev, ((size_t)T * row_stride + pf) * 4}, {actions_dev, n * 12}, {logp_dev, n * 4},
+      {value_dev, (n + rows) * 4}, {adv_dev, n * 4}, {ret_dev, n * 4}, {index_dev, (size_t)(first + count) * 4}, {a.params, (size_t)a.n_params * 4}};
+  const struct { const void* p; size_t bytes; const char* name; } out[2] = {{grad_dev, (size_t)a.n_params * 4, "grad_dev"}, {stats_dev, MQE_PPO_STATS * 4, "stats_dev"}};
+  for (int o = 0; o < 2; o++)
+    for (int i = 0; i < 8; i++)
+      if (gae_overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes)) return fail(-6, "mqe_ppo_grad: %s overlaps an input range or the parameter buffer", out[o].name);
+  if (gae_overlap(grad_dev, (size_t)a.n_params * 4, stats_dev, MQE_PPO_STATS * 4)) return fail(-6, "mqe_ppo_grad: %s overlaps grad_dev", "stats_dev");
+  if (!s->ppo.part) {                  // once per actor: the row tile of its shapes, the scratch (hipMalloc synchronises)
+    mqe_sim::Ppo& p = s->ppo;
+    p.lds_rows = ppo_lds_rows(a.actor, a.critic, s->D);
+    p.rt = ppo_lds_bytes(p.lds_rows, 64) <= PPO_LDS_LIMIT ? 64 : 32;
+    const int lds = (int)ppo_lds_bytes(p.lds_rows, p.rt);
+    if (lds > PPO_LDS_LIMIT) return fail(-5, "mqe_ppo_grad: the layer outputs of one network do not fit the LDS even at 32 rows");
+    const hipError_t e = p.rt == 64 ? hipFuncSetAttribute((const void*)k_ppo_grad<64>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)
+                                    : hipFuncSetAttribute((const void*)k_ppo_grad<32>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (lds > 48 * 1024 && e != hipSuccess) return fail(-5, "mqe_ppo_grad: cannot reserve LDS for k_ppo_grad");
+    PpoNets nets; nets.actor = a.actor; nets.critic = a.critic;
+    if (dalloc(s, &p.pst, (size_t)PPO_MAX_WG * PPO_PST) || dalloc(s, &p.nets, sizeof nets / 4) ||
+        hipMemcpy(p.nets, &nets, sizeof nets, hipMemcpyHostToDevice) != hipSuccess || dalloc(s, &p.part, (size_t)PPO_MAX_WG * a.n_params, 0)) {
+      p.part = nullptr;                // the next call tries again; what was allocated is released with the handle
+      return fail(-5, "device alloc failed (mqe_ppo_grad scratch)");
+    }
+  }
+  hipStream_t q = (hipStream_t)stream;
+  const int rt = s->ppo.rt;
+  const long long tiles = (count + rt - 1) / rt;
+  const int G = (int)(tiles < PPO_MAX_WG ? tiles : PPO_MAX_WG);
+  const PpoNets* nets = reinterpret_cast<const PpoNets*>(s->ppo.nets);
+  PpoLoss ls;
+  ls.clip = loss->clip_ratio; ls.value_coef = loss->value_coef; ls.entropy_coef = loss->entropy_coef; ls.value_clip = loss->value_clip;
+  ls.inv_m = (float)(1.0 / (double)count); ls.clip_value = (flags & MQE_PPO_CLIP_VALUE) ? 1 : 0;
+  const size_t lds = ppo_lds_bytes(s->ppo.lds_rows, rt);
+  if (rt == 64)
+    hipLaunchKernelGGL(k_ppo_grad<64>, dim3(G), dim3(ACT_THREADS), lds, q, (const float*)a.params, nets, a.log_std_off, a.n_params, s->D, s->ppo.lds_rows, a.relu,
+                       packed_dev, row_stride, (int)rows, (long long)n, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, index_dev, first, count, ls, s->ppo.part, s->ppo.pst);
+  else
+    hipLaunchKernelGGL(k_ppo_grad<32>, dim3(G), dim3(ACT_THREADS), lds, q, (const float*)a.params, nets, a.log_std_off, a.n_params, s->D, s->ppo.lds_rows, a.relu,
+                       packed_dev, row_stride, (int)rows, (long long)n, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, index_dev, first, count, ls, s->ppo.part, s->ppo.pst);
+  hipLaunchKernelGGL(k_ppo_reduce, dim3((a.n_params + PPO_REDUCE_THREADS - 1) / PPO_REDUCE_THREADS), dim3(PPO_REDUCE_THREADS), 0, q, (const float*)s->ppo.part,
+                     (const double*)s->ppo.pst, G, a.n_params, a.log_std_off, count, ls.value_coef, ls.entropy_coef, (const float*)a.params, grad_dev, stats_dev);
+  return launched();
+}
+
+// the moment buffers [2][n_params] and the norm, zeroed, on first use
+static int ppo_moments(mqe_sim* s) {
+  if (s->ppo.moments) return 0;
+  if (dalloc(s, &s->ppo.norm, 1) || dalloc(s, &s->ppo.moments, (size_t)2 * s->act.n_params)) { s->ppo.moments = nullptr; return fail(-5, "device alloc failed (Adam moments)"); }
+  return 0;
+}
+extern "C" int mqe_ppo_optimizer(mqe_sim* s, mqe_tensor_view* m_out, mqe_tensor_view* v_out) {
+  if (!s || !m_out || !v_out) return fail(-1, "mqe_ppo_optimizer: null argument");
+  if (!s->act.on) return fail(-6, "mqe_ppo_optimizer: no actor (mqe_actor_create)");
+  if (int rc = ppo_moments(s)) return rc;
+  mqe_tensor_view* v[2] = {m_out, v_out};
+  for (int i = 0; i < 2; i++) {
+    v[i]->ptr = s->ppo.moments + (size_t)i * s->act.n_params; v[i]->ndim = 1; v[i]->shape[0] = s->act.n_params;
+    v[i]->shape[1] = v[i]->shape[2] = v[i]->shape[3] = 0; v[i]->dtype = 0;
+  }
+  return 0;
+}
+extern "C" int mqe_ppo_adam(mqe_sim* s, const float* grad_dev, long long step, float lr, float beta1, float beta2, float eps, float max_grad_norm,
+                            float* norm_dev, void* stream) {
+  if (!s) return fail(-1, "null engine handle");
+  if (!grad_dev) return fail(-1, "mqe_ppo_adam: grad_dev is required");
+  if (!s->act.on) return fail(-6, "mqe_ppo_adam: no actor (mqe_actor_create)");
+  if (step < 1) return fail(-6, "mqe_ppo_adam: step counts from 1");
+  if (((uintptr_t)grad_dev & 3) || ((uintptr_t)norm_dev & 3)) return fail(-6, "mqe_ppo_adam: misaligned pointer (grad_dev, norm_dev: 4 bytes)");
+  if (ppo_not_finite(&lr)) return fail(-6, "mqe_ppo_adam: lr is not finite");
+  if (ppo_bad_coef(&beta1) || beta1 >= 1.0f) return fail(-6, "mqe_ppo_adam: beta1 must lie in [0, 1)");
+  if (ppo_bad_coef(&beta2) || beta2 >= 1.0f) return fail(-6, "mqe_ppo_adam: beta2 must lie in [0, 1)");
+  if (ppo_bad_coef(&eps)) return fail(-6, "mqe_ppo_adam: eps must be finite and not negative");
+  if (ppo_not_finite(&max_grad_norm)) return fail(-6, "mqe_ppo_adam: max_grad_norm is not finite (0 or below: no clipping)");
+  if (int rc = ppo_moments(s)) return rc;
+  const size_t nb = (size_t)s->act.n_params * 4;
+  const struct { const void* p; size_t bytes; } mine[3] = {{s->act.params, nb}, {s->ppo.moments, 2 * nb}, {s->ppo.norm, 8}};
+  for (int i = 0; i < 3; i++) {
+    if (gae_overlap(grad_dev, nb, mine[i].p, mine[i].bytes)) return fail(-6, "mqe_ppo_adam: %s overlaps the parameter or moment buffers", "grad_dev");
+    if (gae_overlap(norm_dev, 4, mine[i].p, mine[i].bytes)) return fail(-6, "mqe_ppo_adam: %s overlaps the parameter or moment buffers", "norm_dev");
+  }
+  if (gae_overlap(norm_dev, 4, grad_dev, nb)) return fail(-6, "mqe_ppo_adam: %s overlaps grad_dev", "norm_dev");
+  hipStream_t q = (hipStream_t)stream;
+  const int n = s->act.n_params;
+  const bool clip = max_grad_norm > 0.0f;
+  if (clip || norm_dev) hipLaunchKernelGGL(k_ppo_norm, dim3(1), dim3(PPO_NORM_THREADS), 0, q, grad_dev, n, s->ppo.norm, norm_dev);
+  PpoAdam k;
+  k.b1 = beta1; k.b2 = beta2; k.omb1 = (float)(1.0 - (double)beta1); k.omb2 = (float)(1.0 - (double)beta2);
+  k.step_size = (float)((double)lr / (1.0 - std::pow((double)beta1, (double)step)));
+  k.bc2s = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
+  k.eps = eps; k.max_norm = clip ? max_grad_norm : 0.0f;
+  hipLaunchKernelGGL(k_ppo_adam, dim3((n + PPO_ADAM_THREADS - 1) / PPO_ADAM_THREADS), dim3(PPO_ADAM_THREADS), 0, q, s->act.params, s->ppo.moments,
+                     s->ppo.moments + n, grad_dev, n, (const double*)s->ppo.norm, k);
   return launched();
 }
 

@@ -115,12 +115,18 @@ ACTOR_MAX_LAYERS, ACTOR_MAX_HIDDEN, ACTOR_MAX_OBS = 4, 256, 128
 ACTOR_TANH, ACTOR_RELU = 0, 1
 ROLLOUT_MAX_STEPS, ROLLOUT_DETERMINISTIC = 4096, 1
 GAE_NORMALIZE = 1            # mqe_gae flags bit 0
+PPO_CLIP_VALUE, PPO_STATS = 1, 6      # mqe_ppo_grad: flags bit 0; floats of stats_dev (mean L_pi, mean L_v, H, L, approximate KL, clip share)
 RNG_ACTOR = 0x70000000           # csrc/mqe_common.hpp MQE_RNG_ACTOR: `count` of the actor's draws = RNG_ACTOR + post-physics steps so far
 
 
 class ActorShape(C.Structure):
     _fields_ = [("obs_dim", i32), ("act_dim", i32), ("actor_layers", i32), ("actor_dims", i32 * (ACTOR_MAX_LAYERS + 1)),
                 ("critic_layers", i32), ("critic_dims", i32 * (ACTOR_MAX_LAYERS + 1)), ("activation", i32), ("action_gain", f32)]
+
+
+class PpoLoss(C.Structure):
+    """mqe_ppo_loss"""
+    _fields_ = [("clip_ratio", f32), ("value_coef", f32), ("entropy_coef", f32), ("value_clip", f32)]
 
 
 def actor_param_layout(actor_dims, critic_dims=None):

@@ -177,6 +177,7 @@ class HipEngine(EngineBase):
             raise RuntimeError(f"mqe_actor_create failed ({rc}): {self.lib.mqe_last_error().decode()}")
         self._actor = dict(actor_dims=actor_dims, critic_dims=critic_dims or None, activation=activation, action_gain=float(action_gain))
         self._actor_views = None
+        self.ppo_step = 0            # the library dropped Adam's moments with the old actor
 
     def actor_params(self):
         """{name: zero-copy view} of the engine's parameter buffer (abi.actor_param_layout: actor.0.weight, actor.0.bias, ..., critic.0.weight,
@@ -300,6 +301,118 @@ class HipEngine(EngineBase):
             raise RuntimeError(f"mqe_gae failed ({rc}): {self.lib.mqe_last_error().decode()}")
         traj.advantages, traj.returns, traj.adv_stats = adv, ret, (stats if normalize else None)
         return traj
+
+    # ---- the PPO update on the engine's own parameters (mqe_ppo_grad / mqe_ppo_optimizer / mqe_ppo_adam; csrc/kernels_ppo.hpp) ---------------
+    def ppo_grad(self, traj, index=None, first=0, count=None, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=None, out=None):
+        """Gradient of rsl_rl's clipped-surrogate PPO loss over one minibatch of a Rollout that HipEngine.gae has filled, with respect to the
+        engine's actor-critic parameters (mqe_ppo_grad; csrc/kernels_ppo.hpp states the loss): two launches, no synchronisation (the first
+        call after create_actor allocates its scratch and synchronises once), the same bits on every run.  The minibatch is
+        index[first:first + count] (an int32 device tensor of flat sample numbers t * N * A' + row, e.g. a slice of torch.randperm) or, without
+        an index, the samples first .. first + count; count=None: everything from `first` on.  value_clip: None (plain squared error) or the
+        clamp c_v of the clipped value loss.  out: (grad, stats) tensors to write instead of fresh ones.  -> (grad, stats): grad float32
+        [n_params] in actor_params()["flat"]'s layout, stats float32 [6]: mean L_pi, mean L_v, entropy H, L, approximate KL, clip share."""
+        if getattr(self, "_actor", None) is None:
+            raise RuntimeError("no actor: call create_actor first")
+        if self._actor["critic_dims"] is None:
+            raise ValueError("ppo_grad: the loss has a value term and the actor was created without a critic")
+        for name in ("value", "logp", "advantages", "returns"):
+            if getattr(traj, name) is None:
+                raise ValueError(f"ppo_grad: traj.{name} is None (rollout with a critic, then gae)")
+        T = int(traj.T)
+        N, Aw, D = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
+        dev = self.torch_device
+        ok = lambda t, shp: t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shp
+        for name, shp in (("actions", (T, N, Aw, 3)), ("logp", (T, N, Aw)), ("value", (T + 1, N, Aw)), ("advantages", (T, N, Aw)), ("returns", (T, N, Aw))):
+            if not ok(getattr(traj, name), shp):
+                raise ValueError(f"traj.{name} must be a contiguous float32 device tensor of shape {shp}")
+        if traj.packed.dtype != torch.float32 or not traj.packed.is_cuda or traj.packed.stride(1) != 1:
+            raise ValueError("traj.packed must be a float32 device tensor (T + 1, row_stride) with unit stride along a row")
+        n_params = self.actor_params()["flat"].numel()
+        total = T * N * Aw
+        if index is not None:
+            if not (index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.dim() == 1):
+                raise ValueError("index must be a contiguous one-dimensional int32 device tensor")
+            total = int(index.numel())
+        first = int(first)
+        count = total - first if count is None else int(count)
+        if index is not None and (first < 0 or count < 1 or first + count > total):
+            raise ValueError(f"index holds {total} samples: first={first}, count={count} reach outside it")
+        grad, stats = out if out is not None else (None, None)
+        if grad is not None and not ok(grad, (n_params,)):
+            raise ValueError(f"out[0] (grad) must be a contiguous float32 device tensor of shape {(n_params,)}")
+        if stats is not None and not ok(stats, (abi.PPO_STATS,)):
+            raise ValueError(f"out[1] (stats) must be a contiguous float32 device tensor of shape {(abi.PPO_STATS,)}")
+        grad = grad if grad is not None else torch.empty(n_params, dtype=torch.float32, device=dev)
+        stats = stats if stats is not None else torch.empty(abi.PPO_STATS, dtype=torch.float32, device=dev)
+        loss = abi.PpoLoss(float(clip), float(value_coef), float(entropy_coef), float(value_clip) if value_clip is not None else 0.0)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+        f = self.lib.mqe_ppo_grad
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong] + [C.c_void_p] * 6 + [C.c_longlong, C.c_longlong, C.POINTER(abi.PpoLoss), C.c_int,
+                                                                                          C.c_void_p, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        rc = f(self.h, T, ptr(traj.packed), int(traj.packed.stride(0)), ptr(traj.actions), ptr(traj.logp), ptr(traj.value), ptr(traj.advantages),
+               ptr(traj.returns), ptr(index), first, count, C.byref(loss), abi.PPO_CLIP_VALUE if value_clip is not None else 0, ptr(grad), ptr(stats),
+               self._stream())
+        if rc != 0:
+            raise RuntimeError(f"mqe_ppo_grad failed ({rc}): {self.lib.mqe_last_error().decode()}")
+        return grad, stats
+
+    def optimizer_state(self):
+        """{"exp_avg", "exp_avg_sq"}: zero-copy views of Adam's two moment buffers (mqe_ppo_optimizer), float32 [n_params] in the layout of
+        actor_params()["flat"], zero until the first adam_step; a new create_actor drops them.  With actor_params()["flat"] and the step count
+        (HipEngine.ppo_step) they are the whole optimiser checkpoint."""
+        if getattr(self, "_actor", None) is None:
+            raise RuntimeError("no actor: call create_actor first")
+        m, v = abi.TensorView(), abi.TensorView()
+        f = self.lib.mqe_ppo_optimizer
+        f.argtypes, f.restype = [C.c_void_p, C.POINTER(abi.TensorView), C.POINTER(abi.TensorView)], C.c_int
+        self._check(f(self.h, C.byref(m), C.byref(v)))
+        return {"exp_avg": self._wrap(m.ptr, [int(m.shape[0])], m.dtype), "exp_avg_sq": self._wrap(v.ptr, [int(v.shape[0])], v.dtype)}
+
+    def adam_step(self, grad, step, lr, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, norm_out=None):
+        """One torch.optim.Adam step (no weight decay, no amsgrad) on the engine's parameters, in place, ordered on the stream (mqe_ppo_adam).
+        step >= 1 is the caller's count.  max_grad_norm: clip_grad_norm_ over all parameters first (None: off); norm_out: a float32 [1] device
+        tensor that receives the unscaled gradient norm."""
+        n_params = self.actor_params()["flat"].numel()
+        if not (grad.is_cuda and grad.dtype == torch.float32 and grad.is_contiguous() and grad.numel() == n_params):
+            raise ValueError(f"grad must be a contiguous float32 device tensor of {n_params} elements")
+        if norm_out is not None and not (norm_out.is_cuda and norm_out.dtype == torch.float32 and norm_out.numel() >= 1):
+            raise ValueError("norm_out must be a float32 device tensor")
+        f = self.lib.mqe_ppo_adam
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        rc = f(self.h, C.c_void_p(grad.data_ptr()), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+               float(max_grad_norm) if max_grad_norm is not None else 0.0, C.c_void_p(norm_out.data_ptr() if norm_out is not None else None), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"mqe_ppo_adam failed ({rc}): {self.lib.mqe_last_error().decode()}")
+
+    def ppo_update(self, traj, epochs, minibatches, lr, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=None, betas=(0.9, 0.999), eps=1e-8,
+                   max_grad_norm=None, generator=None):
+        """The PPO update of one trajectory inside the engine: per epoch one device permutation of the T x N x A' samples
+        (torch.randperm(..., device=..., generator=generator)), cut into `minibatches` equal slices (the last takes the remainder), and per
+        slice ppo_grad + adam_step -- 2 to 4 launches, no synchronisation, no copy.  The step count lives on this object (ppo_step) and carries
+        over between calls.  -> the (epochs, minibatches, 6) statistics tensor (ppo_grad's, before each step).  Afterwards the engine's buffer
+        is the master copy of the parameters."""
+        epochs, minibatches = int(epochs), int(minibatches)
+        T = int(traj.T)
+        N, Aw, _ = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
+        total = T * N * Aw
+        if epochs < 1 or minibatches < 1 or minibatches > total:
+            raise ValueError(f"ppo_update: epochs >= 1 and 1 <= minibatches <= {total} samples")
+        dev = self.torch_device
+        stats = torch.empty(epochs, minibatches, abi.PPO_STATS, dtype=torch.float32, device=dev)
+        grad = torch.empty(self.actor_params()["flat"].numel(), dtype=torch.float32, device=dev)
+        per = total // minibatches
+        for e in range(epochs):
+            perm = torch.randperm(total, device=dev, generator=generator).to(torch.int32)
+            for b in range(minibatches):
+                first = b * per
+                count = per if b + 1 < minibatches else total - first
+                self.ppo_grad(traj, index=perm, first=first, count=count, clip=clip, value_coef=value_coef, entropy_coef=entropy_coef,
+                              value_clip=value_clip, out=(grad, stats[e, b]))
+                self.ppo_step = getattr(self, "ppo_step", 0) + 1
+                self.adam_step(grad, self.ppo_step, lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm)
+        return stats
 
     def defender_command(self, out):
         self._call("defender_command", C.c_void_p(out.data_ptr()), self._stream())

@@ -177,6 +177,36 @@ class FusedTaskWrapper(EmptyWrapper):
             else:
                 views["log_std"].copy_(torch.as_tensor(log_std).detach().reshape(3).to(torch.float32), non_blocking=True)
 
+    def pull_actor(self):
+        """the reverse of sync_actor(): the engine's parameter buffer -> the torch modules and log_std given to set_actor, device to device
+        when they live on the engine's device, no synchronisation.  After ppo_update() the ENGINE holds the master copy of the parameters:
+        pull_actor() brings the modules up to date, and a sync_actor() before it would overwrite the update with the modules' old values"""
+        eng = self._rollout_engine("pull_actor")
+        if getattr(self, "_actor_src", None) is None:
+            raise RuntimeError("pull_actor: no actor (set_actor first)")
+        a_lin, c_lin, log_std = self._actor_src
+        views = eng.actor_params()
+        with torch.no_grad():
+            for who, lin in (("actor", a_lin), ("critic", c_lin)):
+                for l, layer in enumerate(lin):
+                    layer.weight.copy_(views[f"{who}.{l}.weight"], non_blocking=True)
+                    layer.bias.copy_(views[f"{who}.{l}.bias"], non_blocking=True)
+            if isinstance(log_std, torch.Tensor):
+                log_std.copy_(views["log_std"].reshape(log_std.shape), non_blocking=True)
+
+    def ppo_update(self, traj, **kw):
+        """The PPO update of a trajectory of rollout(gamma=...) inside the engine (HipEngine.ppo_update: epochs, minibatches, lr, clip,
+        value_coef, entropy_coef, value_clip, betas, eps, max_grad_norm, generator): per minibatch the clipped-surrogate gradient and one Adam
+        step on the engine's own parameter buffer, no copy and no synchronisation; -> the (epochs, minibatches, 6) statistics tensor.
+        Afterwards the engine holds the master copy: the following rollout() uses it as it is, pull_actor() copies it into the torch
+        modules, and sync_actor() would overwrite it with the modules' values."""
+        eng = self._rollout_engine("ppo_update")
+        if getattr(self, "_actor_src", None) is None:
+            raise RuntimeError("ppo_update: no actor (set_actor first)")
+        if not self._actor_src[1]:
+            raise ValueError("ppo_update: the loss has a value term, and the actor was set without a critic (set_actor(actor, critic))")
+        return eng.ppo_update(traj, **kw)
+
     def rollout(self, T, deterministic=False, gamma=None, lam=0.95, normalize_advantages=False):
         """T steps with the engine's own actor (set_actor) in one call: a Rollout (mqe.engine.hip_engine) whose tensors -- obs (T+1, N, A', D),
         reward (T, N, A'), done (T, N) bool, actions (T, N, A', 3) unclipped, logp (T, N, A'), value (T+1, N, A') or None -- are fresh memory

@@ -56,6 +56,12 @@ class mqe_openrl_wrapper(Wrapper):
         gamma / lam / normalize_advantages: FusedTaskWrapper.rollout's -- time_outs, advantages, returns and adv_stats from the engine (mqe_gae)"""
         return self.env.rollout(T, deterministic=deterministic, gamma=gamma, lam=lam, normalize_advantages=normalize_advantages)
 
+    def ppo_update_torch(self, traj, **kw):
+        """FusedTaskWrapper.ppo_update on a trajectory of rollout_torch(gamma=...): the PPO epochs run inside the engine on its own parameters
+        (mqe_ppo_grad / mqe_ppo_adam); -> the (epochs, minibatches, 6) statistics tensor.  pull_actor() of the wrapped env brings the result back
+        into the torch modules"""
+        return self.env.ppo_update(traj, **kw)
+
     def step_dlpack(self, actions):
         """Device-resident hand-off for trainers that do not speak torch (replaces the numpy round trip of
         openrl_ws/utils.py:53-67): `actions` is any object with `__dlpack__` living on the env's device; returns objects with
