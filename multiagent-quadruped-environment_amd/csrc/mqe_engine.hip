@@ -24,8 +24,8 @@
 #include "kernels_ppo.hpp"
 
 static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, const char* a = "") {
-  snprintf(g_err, sizeof g_err, fmt, a);
+static int fail(int code, const char* fmt, const char* a = "", const char* b = "", const char* c = "") {      // fmt: up to three %s
+  snprintf(g_err, sizeof g_err, fmt, a, b, c);
   return code;
 }
 #define HIPCHK(x)                                                        \
@@ -1492,6 +1492,48 @@ extern "C" int mqe_step_end(mqe_sim* s, void* stream) {
   return run_substeps_and_post(s, (hipStream_t)stream);
 }
 
+// ---- host checks the training entry points share (mqe_actor_create, mqe_rollout, mqe_gae, mqe_ppo_grad, mqe_ppo_adam): each stated once; `fn`
+// is the entry point, the prefix of its refusals.  First: (T, row_stride) of a trajectory in mqe_rollout's layout against the handle
+struct TrajShape { size_t rows, n, packed_floats; };      // R' = N x A'; T x R' samples; floats of one packed row
+static int traj_shape(const mqe_sim* s, const char* fn, int T, long long row_stride, TrajShape* t) {
+  if (T <= 0 || T > MQE_ROLLOUT_MAX_STEPS) return fail(-6, "%s: T must be 1 .. MQE_ROLLOUT_MAX_STEPS (4096)", fn);
+  t->packed_floats = packed_floats(s);
+  if (row_stride < (long long)t->packed_floats || row_stride % 4 != 0) return fail(-6, "%s: row_stride must be a multiple of 4 and at least the MQE_T_WRAPPER_PACKED length", fn);
+  t->rows = (size_t)s->N * s->Aw; t->n = (size_t)T * t->rows;
+  return 0;
+}
+struct Aligned { const void* p; unsigned bytes; };
+static int check_aligned(const char* fn, std::initializer_list<Aligned> ptrs, const char* rule) {
+  for (const Aligned& a : ptrs)
+    if ((uintptr_t)a.p & (a.bytes - 1)) return fail(-6, "%s: misaligned pointer (%s)", fn, rule);
+  return 0;
+}
+// the first n_out of `r` are what the call writes: none of them may overlap a range behind it in the list (a null pointer is no range)
+struct Range { const void* p; size_t bytes; const char* name; };
+static int check_disjoint(const char* fn, std::initializer_list<Range> r, int n_out) {
+  for (const Range* o = r.begin(); o < r.begin() + n_out; o++)
+    for (const Range* x = o + 1; x < r.end(); x++) {
+      const uintptr_t a = (uintptr_t)o->p, b = (uintptr_t)x->p;
+      if (o->p && x->p && a < b + x->bytes && b < a + o->bytes) return fail(-6, "%s: %s overlaps %s", fn, o->name, x->name);
+    }
+  return 0;
+}
+// the library is built without NaN / infinity semantics (-fno-honor-nans, -fno-honor-infinities): float arguments are ASSUMED finite and a
+// test on their value, or on bits copied from it, may be folded away -- so the arguments are classified from their bytes, read as volatile
+static uint32_t float_bits(const void* p) {
+  const volatile unsigned char* b = (const volatile unsigned char*)p;
+  return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+}
+static bool not_finite(const float* x) { return (float_bits(x) & 0x7f800000u) == 0x7f800000u; }
+static bool negative_or_not_finite(const float* x) {
+  const uint32_t u = float_bits(x);
+  return (u & 0x7f800000u) == 0x7f800000u || ((u >> 31) != 0 && (u << 1) != 0);
+}
+static bool outside_unit_interval(const float* x) { return negative_or_not_finite(x) || *x > 1.0f; }      // the comparison sees a finite value
+static void view_1d_f32(mqe_tensor_view* v, float* p, int n) {
+  v->ptr = p; v->ndim = 1; v->shape[0] = n; v->shape[1] = v->shape[2] = v->shape[3] = 0; v->dtype = 0;
+}
+
 // ---- on-device rollouts: mqe_actor_create / mqe_actor_params / mqe_rollout (include/mqe_hip.h) ---------------------------------
 // one network's dims[] against the limits; fills its offsets into the flat parameter buffer from *off on
 static int actor_net_shape(const char* who, int layers, const int32_t* dims, int in, int out, ActorNet* net, int* off, int* ldh) {
@@ -1530,7 +1572,7 @@ extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
   if (sh->obs_dim > MQE_ACTOR_MAX_OBS) return fail(-6, "mqe_actor_create: obs_dim above MQE_ACTOR_MAX_OBS (128)");
   if (sh->act_dim != 3) return fail(-6, "mqe_actor_create: act_dim must be 3");
   if (sh->activation != MQE_ACTOR_TANH && sh->activation != MQE_ACTOR_RELU) return fail(-6, "mqe_actor_create: activation must be MQE_ACTOR_TANH or MQE_ACTOR_RELU");
-  if (!(std::fabs(sh->action_gain) < 1e30f)) return fail(-6, "mqe_actor_create: action_gain is not finite");
+  if (not_finite(&sh->action_gain) || std::fabs(sh->action_gain) >= 1e30f) return fail(-6, "mqe_actor_create: action_gain is not finite");
   mqe_sim::Actor a;
   int off = 0, ldh = 0;
   memset(&a.actor, 0, sizeof a.actor); memset(&a.critic, 0, sizeof a.critic);
@@ -1550,7 +1592,7 @@ extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
 extern "C" int mqe_actor_params(mqe_sim* s, mqe_tensor_view* v) {
   if (!s || !v) return fail(-1, "mqe_actor_params: null argument");
   if (!s->act.on) return fail(-6, "mqe_actor_params: no actor (mqe_actor_create)");
-  v->ptr = s->act.params; v->ndim = 1; v->shape[0] = s->act.n_params; v->shape[1] = v->shape[2] = v->shape[3] = 0; v->dtype = 0;
+  view_1d_f32(v, s->act.params, s->act.n_params);
   return 0;
 }
 // value_only: the launch behind the last step (no draw, nothing but value written)
@@ -1569,15 +1611,13 @@ extern "C" int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* pack
   if (!packed_dev || !actions_dev) return fail(-1, "mqe_rollout: packed_dev and actions_dev are required");
   if (!s->act.on) return fail(-6, "mqe_rollout: no actor (mqe_actor_create)");
   if (s->step_open) return fail(-8, "mqe_rollout inside an open step (mqe_step_begin / _head without mqe_step_end)");
-  if (T <= 0 || T > MQE_ROLLOUT_MAX_STEPS) return fail(-6, "mqe_rollout: T must be 1 .. MQE_ROLLOUT_MAX_STEPS (4096)");
-  const size_t pf = packed_floats(s);
-  if (row_stride < (long long)pf || row_stride % 4 != 0) return fail(-6, "mqe_rollout: row_stride must be a multiple of 4 and at least the MQE_T_WRAPPER_PACKED length");
-  if (((uintptr_t)packed_dev & 15) || ((uintptr_t)obs0_dev & 3) || ((uintptr_t)actions_dev & 3) || ((uintptr_t)logp_dev & 3) || ((uintptr_t)value_dev & 3))
-    return fail(-6, "mqe_rollout: misaligned pointer (packed_dev: 16 bytes, the others: 4)");
+  TrajShape ts;
+  if (int rc = traj_shape(s, "mqe_rollout", T, row_stride, &ts)) return rc;
+  if (int rc = check_aligned("mqe_rollout", {{packed_dev, 16}, {obs0_dev, 4}, {actions_dev, 4}, {logp_dev, 4}, {value_dev, 4}}, "packed_dev: 16 bytes, the others: 4")) return rc;
   if (value_dev && s->act.critic.n_layers == 0) return fail(-6, "mqe_rollout: value_dev given, but the actor was created without a critic");
   if (s->to_rec && T > s->to_rec_cap) return fail(-6, "mqe_rollout: T exceeds capacity_steps of the registered time-out record (mqe_rollout_time_outs)");
   hipStream_t q = (hipStream_t)stream;
-  const size_t rows = (size_t)s->N * s->Aw, nobs = rows * s->D;
+  const size_t rows = ts.rows, nobs = rows * s->D;
   // row 0: the starting observation, reward and done bytes zeroed
   HIPCHK(hipMemcpyAsync(packed_dev, obs0_dev ? obs0_dev : (const float*)s->tens[MQE_T_WRAPPER_OBS], nobs * 4, hipMemcpyDeviceToDevice, q));
   HIPCHK(hipMemsetAsync(packed_dev + nobs, 0, rows * 4 + (size_t)s->N, q));
@@ -1608,34 +1648,22 @@ extern "C" int mqe_rollout_time_outs(mqe_sim* s, uint8_t* time_outs_dev, int cap
 }
 
 // ---- mqe_gae (include/mqe_hip.h; kernels_gae.hpp) ---------------------------------------------------------------------------------------
-static bool gae_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a && b && x < y + nb && y < x + na;
-}
 extern "C" int mqe_gae(mqe_sim* s, int T, const float* packed_dev, long long row_stride, const float* value_dev, const uint8_t* time_outs_dev,
                        float gamma, float lam, int flags, float* adv_dev, float* ret_dev, float* stats_dev, void* stream) {
   if (!s) return fail(-1, "null engine handle");
   if (!packed_dev || !value_dev || !adv_dev || !ret_dev) return fail(-1, "mqe_gae: packed_dev, value_dev, adv_dev and ret_dev are required");
-  if (T <= 0 || T > MQE_ROLLOUT_MAX_STEPS) return fail(-6, "mqe_gae: T must be 1 .. MQE_ROLLOUT_MAX_STEPS (4096)");
-  const size_t pf = packed_floats(s);
-  if (row_stride < (long long)pf || row_stride % 4 != 0) return fail(-6, "mqe_gae: row_stride must be a multiple of 4 and at least the MQE_T_WRAPPER_PACKED length");
-  if (((uintptr_t)packed_dev & 3) || ((uintptr_t)value_dev & 3) || ((uintptr_t)adv_dev & 3) || ((uintptr_t)ret_dev & 3) || ((uintptr_t)stats_dev & 3))
-    return fail(-6, "mqe_gae: misaligned pointer (packed_dev, value_dev, adv_dev, ret_dev, stats_dev: 4 bytes)");
-  if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(-6, "mqe_gae: gamma must lie in [0, 1]");
-  if (!(lam >= 0.0f && lam <= 1.0f)) return fail(-6, "mqe_gae: lam must lie in [0, 1]");
+  TrajShape ts;
+  if (int rc = traj_shape(s, "mqe_gae", T, row_stride, &ts)) return rc;
+  if (int rc = check_aligned("mqe_gae", {{packed_dev, 4}, {value_dev, 4}, {adv_dev, 4}, {ret_dev, 4}, {stats_dev, 4}}, "packed_dev, value_dev, adv_dev, ret_dev, stats_dev: 4 bytes")) return rc;
+  if (outside_unit_interval(&gamma)) return fail(-6, "mqe_gae: gamma must lie in [0, 1]");
+  if (outside_unit_interval(&lam)) return fail(-6, "mqe_gae: lam must lie in [0, 1]");
   if (flags & ~MQE_GAE_NORMALIZE) return fail(-6, "mqe_gae: unknown bits in flags (MQE_GAE_NORMALIZE is the only one)");
-  const size_t rows = (size_t)s->N * s->Aw, n = (size_t)T * rows;
+  const size_t rows = ts.rows, n = ts.n, pf = ts.packed_floats;
   const bool norm = (flags & MQE_GAE_NORMALIZE) != 0;
   if (norm && n < 2) return fail(-6, "mqe_gae: MQE_GAE_NORMALIZE needs T x R' >= 2 values (the unbiased std of one value does not exist)");
-  const struct { const void* p; size_t bytes; const char* name; } in[3] = {{packed_dev, ((size_t)T * row_stride + pf) * 4, "packed_dev"},
-      {value_dev, (n + rows) * 4, "value_dev"}, {time_outs_dev, (size_t)T * s->N, "time_outs_dev"}},
-    out[3] = {{adv_dev, n * 4, "adv_dev"}, {ret_dev, n * 4, "ret_dev"}, {stats_dev, 8, "stats_dev"}};
-  for (int o = 0; o < 3; o++) {
-    for (int i = 0; i < 3; i++)
-      if (gae_overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes)) return fail(-6, "mqe_gae: %s overlaps an input range", out[o].name);
-    for (int o2 = o + 1; o2 < 3; o2++)
-      if (gae_overlap(out[o].p, out[o].bytes, out[o2].p, out[o2].bytes)) return fail(-6, "mqe_gae: %s overlaps another output range", out[o].name);
-  }
+  if (int rc = check_disjoint("mqe_gae", {{adv_dev, n * 4, "adv_dev"}, {ret_dev, n * 4, "ret_dev"}, {stats_dev, 8, "stats_dev"},
+                                          {packed_dev, ((size_t)T * row_stride + pf) * 4, "packed_dev"}, {value_dev, (n + rows) * 4, "value_dev"},
+                                          {time_outs_dev, (size_t)T * s->N, "time_outs_dev"}}, 3)) return rc;
   const int nblk = (int)((rows + GAE_THREADS - 1) / GAE_THREADS);
   if (norm && !s->gae_part) {          // once per handle: dalloc's memset synchronises
     if (dalloc(s, &s->gae_part, (size_t)2 * nblk)) return fail(-5, "device alloc failed (mqe_gae scratch)");
@@ -1643,10 +1671,7 @@ extern "C" int mqe_gae(mqe_sim* s, int T, const float* packed_dev, long long row
   hipStream_t q = (hipStream_t)stream;
   const long long rew_off = (long long)rows * s->D;
   double* part = norm ? s->gae_part : nullptr;
-  if (time_outs_dev)
-    hipLaunchKernelGGL(k_gae<true>, dim3(nblk), dim3(GAE_THREADS), 0, q, packed_dev, row_stride, rew_off, value_dev, time_outs_dev, gamma, lam, T, (int)rows, s->N, s->Aw, adv_dev, ret_dev, part);
-  else
-    hipLaunchKernelGGL(k_gae<false>, dim3(nblk), dim3(GAE_THREADS), 0, q, packed_dev, row_stride, rew_off, value_dev, time_outs_dev, gamma, lam, T, (int)rows, s->N, s->Aw, adv_dev, ret_dev, part);
+  hipLaunchKernelGGL(time_outs_dev ? k_gae<true> : k_gae<false>, dim3(nblk), dim3(GAE_THREADS), 0, q, packed_dev, row_stride, rew_off, value_dev, time_outs_dev, gamma, lam, T, (int)rows, s->N, s->Aw, adv_dev, ret_dev, part);
   if (norm) {
     const long long per = (long long)GAE_NORM_THREADS * 8;       // ~8 values per thread
     const long long want = ((long long)n + per - 1) / per;
@@ -1657,17 +1682,6 @@ extern "C" int mqe_gae(mqe_sim* s, int T, const float* packed_dev, long long row
 }
 
 // ---- mqe_ppo_grad / mqe_ppo_optimizer / mqe_ppo_adam (include/mqe_hip.h; kernels_ppo.hpp) ------------------------------------------------------
-// the library is built without NaN / infinity semantics (-fno-honor-nans, -fno-honor-infinities): float arguments are ASSUMED finite and a
-// test on their value, or on bits copied from it, may be folded away -- so the arguments are classified from their bytes, read as volatile
-static uint32_t ppo_bits(const void* p) {
-  const volatile unsigned char* b = (const volatile unsigned char*)p;
-  return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
-}
-static bool ppo_not_finite(const float* x) { return (ppo_bits(x) & 0x7f800000u) == 0x7f800000u; }
-static bool ppo_bad_coef(const float* x) {          // negative, NaN or infinite
-  const uint32_t u = ppo_bits(x);
-  return (u & 0x7f800000u) == 0x7f800000u || ((u >> 31) != 0 && (u << 1) != 0);
-}
 extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long long row_stride, const float* actions_dev, const float* logp_dev,
                             const float* value_dev, const float* adv_dev, const float* ret_dev, const int32_t* index_dev, long long first,
                             long long count, const mqe_ppo_loss* loss, int flags, float* grad_dev, float* stats_dev, void* stream) {
@@ -1676,38 +1690,33 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
     return fail(-1, "mqe_ppo_grad: packed_dev, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, loss and grad_dev are required");
   if (!s->act.on) return fail(-6, "mqe_ppo_grad: no actor (mqe_actor_create)");
   if (s->act.critic.n_layers == 0) return fail(-6, "mqe_ppo_grad: the actor was created without a critic: the loss has a value term");
-  if (T <= 0 || T > MQE_ROLLOUT_MAX_STEPS) return fail(-6, "mqe_ppo_grad: T must be 1 .. MQE_ROLLOUT_MAX_STEPS (4096)");
-  const size_t pf = packed_floats(s);
-  if (row_stride < (long long)pf || row_stride % 4 != 0) return fail(-6, "mqe_ppo_grad: row_stride must be a multiple of 4 and at least the MQE_T_WRAPPER_PACKED length");
-  if (((uintptr_t)packed_dev & 15) || ((uintptr_t)actions_dev & 3) || ((uintptr_t)logp_dev & 3) || ((uintptr_t)value_dev & 3) || ((uintptr_t)adv_dev & 3) ||
-      ((uintptr_t)ret_dev & 3) || ((uintptr_t)index_dev & 3) || ((uintptr_t)grad_dev & 3) || ((uintptr_t)stats_dev & 3))
-    return fail(-6, "mqe_ppo_grad: misaligned pointer (packed_dev: 16 bytes, the others: 4)");
-  const size_t rows = (size_t)s->N * s->Aw, n = (size_t)T * rows;
+  TrajShape ts;
+  if (int rc = traj_shape(s, "mqe_ppo_grad", T, row_stride, &ts)) return rc;
+  if (int rc = check_aligned("mqe_ppo_grad", {{packed_dev, 16}, {actions_dev, 4}, {logp_dev, 4}, {value_dev, 4}, {adv_dev, 4}, {ret_dev, 4}, {index_dev, 4},
+                                              {grad_dev, 4}, {stats_dev, 4}}, "packed_dev: 16 bytes, the others: 4")) return rc;
+  const size_t rows = ts.rows, n = ts.n, pf = ts.packed_floats;
   if (count < 1) return fail(-6, "mqe_ppo_grad: count must be at least 1");
   if (first < 0) return fail(-6, "mqe_ppo_grad: first must not be negative");
   if (first > (1LL << 40) || count > (1LL << 40)) return fail(-6, "mqe_ppo_grad: first / count beyond any trajectory");
   if (!index_dev && first + count > (long long)n) return fail(-6, "mqe_ppo_grad: first + count exceeds the T x R' samples of the trajectory");
-  if (ppo_bad_coef(&loss->clip_ratio)) return fail(-6, "mqe_ppo_grad: clip_ratio must be finite and not negative");
-  if (ppo_bad_coef(&loss->value_coef)) return fail(-6, "mqe_ppo_grad: value_coef must be finite and not negative");
-  if (ppo_bad_coef(&loss->entropy_coef)) return fail(-6, "mqe_ppo_grad: entropy_coef must be finite and not negative");
-  if (ppo_bad_coef(&loss->value_clip)) return fail(-6, "mqe_ppo_grad: value_clip must be finite and not negative");
+  if (negative_or_not_finite(&loss->clip_ratio)) return fail(-6, "mqe_ppo_grad: clip_ratio must be finite and not negative");
+  if (negative_or_not_finite(&loss->value_coef)) return fail(-6, "mqe_ppo_grad: value_coef must be finite and not negative");
+  if (negative_or_not_finite(&loss->entropy_coef)) return fail(-6, "mqe_ppo_grad: entropy_coef must be finite and not negative");
+  if (negative_or_not_finite(&loss->value_clip)) return fail(-6, "mqe_ppo_grad: value_clip must be finite and not negative");
   if (flags & ~MQE_PPO_CLIP_VALUE) return fail(-6, "mqe_ppo_grad: unknown bits in flags (MQE_PPO_CLIP_VALUE is the only one)");
   const mqe_sim::Actor& a = s->act;
-  const struct { const void* p; size_t bytes; } in[8] = {{packed_dev, ((size_t)T * row_stride + pf) * 4}, {actions_dev, n * 12}, {logp_dev, n * 4},
-      {value_dev, (n + rows) * 4}, {adv_dev, n * 4}, {ret_dev, n * 4}, {index_dev, (size_t)(first + count) * 4}, {a.params, (size_t)a.n_params * 4}};
-  const struct { const void* p; size_t bytes; const char* name; } out[2] = {{grad_dev, (size_t)a.n_params * 4, "grad_dev"}, {stats_dev, MQE_PPO_STATS * 4, "stats_dev"}};
-  for (int o = 0; o < 2; o++)
-    for (int i = 0; i < 8; i++)
-      if (gae_overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes)) return fail(-6, "mqe_ppo_grad: %s overlaps an input range or the parameter buffer", out[o].name);
-  if (gae_overlap(grad_dev, (size_t)a.n_params * 4, stats_dev, MQE_PPO_STATS * 4)) return fail(-6, "mqe_ppo_grad: %s overlaps grad_dev", "stats_dev");
+  if (int rc = check_disjoint("mqe_ppo_grad", {{stats_dev, MQE_PPO_STATS * 4, "stats_dev"}, {grad_dev, (size_t)a.n_params * 4, "grad_dev"},
+                                               {packed_dev, ((size_t)T * row_stride + pf) * 4, "packed_dev"}, {actions_dev, n * 12, "actions_dev"},
+                                               {logp_dev, n * 4, "logp_dev"}, {value_dev, (n + rows) * 4, "value_dev"}, {adv_dev, n * 4, "adv_dev"},
+                                               {ret_dev, n * 4, "ret_dev"}, {index_dev, (size_t)(first + count) * 4, "index_dev"},
+                                               {a.params, (size_t)a.n_params * 4, "the parameter buffer"}}, 2)) return rc;
   if (!s->ppo.part) {                  // once per actor: the row tile of its shapes, the scratch (hipMalloc synchronises)
     mqe_sim::Ppo& p = s->ppo;
     p.lds_rows = ppo_lds_rows(a.actor, a.critic, s->D);
     p.rt = ppo_lds_bytes(p.lds_rows, 64) <= PPO_LDS_LIMIT ? 64 : 32;
     const int lds = (int)ppo_lds_bytes(p.lds_rows, p.rt);
     if (lds > PPO_LDS_LIMIT) return fail(-5, "mqe_ppo_grad: the layer outputs of one network do not fit the LDS even at 32 rows");
-    const hipError_t e = p.rt == 64 ? hipFuncSetAttribute((const void*)k_ppo_grad<64>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)
-                                    : hipFuncSetAttribute((const void*)k_ppo_grad<32>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    const hipError_t e = hipFuncSetAttribute((const void*)(p.rt == 64 ? k_ppo_grad<64> : k_ppo_grad<32>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (lds > 48 * 1024 && e != hipSuccess) return fail(-5, "mqe_ppo_grad: cannot reserve LDS for k_ppo_grad");
     PpoNets nets; nets.actor = a.actor; nets.critic = a.critic;
     if (dalloc(s, &p.pst, (size_t)PPO_MAX_WG * PPO_PST) || dalloc(s, &p.nets, sizeof nets / 4) ||
@@ -1725,12 +1734,8 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   ls.clip = loss->clip_ratio; ls.value_coef = loss->value_coef; ls.entropy_coef = loss->entropy_coef; ls.value_clip = loss->value_clip;
   ls.inv_m = (float)(1.0 / (double)count); ls.clip_value = (flags & MQE_PPO_CLIP_VALUE) ? 1 : 0;
   const size_t lds = ppo_lds_bytes(s->ppo.lds_rows, rt);
-  if (rt == 64)
-    hipLaunchKernelGGL(k_ppo_grad<64>, dim3(G), dim3(ACT_THREADS), lds, q, (const float*)a.params, nets, a.log_std_off, a.n_params, s->D, s->ppo.lds_rows, a.relu,
-                       packed_dev, row_stride, (int)rows, (long long)n, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, index_dev, first, count, ls, s->ppo.part, s->ppo.pst);
-  else
-    hipLaunchKernelGGL(k_ppo_grad<32>, dim3(G), dim3(ACT_THREADS), lds, q, (const float*)a.params, nets, a.log_std_off, a.n_params, s->D, s->ppo.lds_rows, a.relu,
-                       packed_dev, row_stride, (int)rows, (long long)n, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, index_dev, first, count, ls, s->ppo.part, s->ppo.pst);
+  hipLaunchKernelGGL(rt == 64 ? k_ppo_grad<64> : k_ppo_grad<32>, dim3(G), dim3(ACT_THREADS), lds, q, (const float*)a.params, nets, a.log_std_off, a.n_params, s->D, s->ppo.lds_rows, a.relu,
+                     packed_dev, row_stride, (int)rows, (long long)n, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, index_dev, first, count, ls, s->ppo.part, s->ppo.pst);
   hipLaunchKernelGGL(k_ppo_reduce, dim3((a.n_params + PPO_REDUCE_THREADS - 1) / PPO_REDUCE_THREADS), dim3(PPO_REDUCE_THREADS), 0, q, (const float*)s->ppo.part,
                      (const double*)s->ppo.pst, G, a.n_params, a.log_std_off, count, ls.value_coef, ls.entropy_coef, (const float*)a.params, grad_dev, stats_dev);
   return launched();
@@ -1746,11 +1751,8 @@ extern "C" int mqe_ppo_optimizer(mqe_sim* s, mqe_tensor_view* m_out, mqe_tensor_
   if (!s || !m_out || !v_out) return fail(-1, "mqe_ppo_optimizer: null argument");
   if (!s->act.on) return fail(-6, "mqe_ppo_optimizer: no actor (mqe_actor_create)");
   if (int rc = ppo_moments(s)) return rc;
-  mqe_tensor_view* v[2] = {m_out, v_out};
-  for (int i = 0; i < 2; i++) {
-    v[i]->ptr = s->ppo.moments + (size_t)i * s->act.n_params; v[i]->ndim = 1; v[i]->shape[0] = s->act.n_params;
-    v[i]->shape[1] = v[i]->shape[2] = v[i]->shape[3] = 0; v[i]->dtype = 0;
-  }
+  view_1d_f32(m_out, s->ppo.moments, s->act.n_params);
+  view_1d_f32(v_out, s->ppo.moments + s->act.n_params, s->act.n_params);
   return 0;
 }
 extern "C" int mqe_ppo_adam(mqe_sim* s, const float* grad_dev, long long step, float lr, float beta1, float beta2, float eps, float max_grad_norm,
@@ -1759,20 +1761,16 @@ extern "C" int mqe_ppo_adam(mqe_sim* s, const float* grad_dev, long long step, f
   if (!grad_dev) return fail(-1, "mqe_ppo_adam: grad_dev is required");
   if (!s->act.on) return fail(-6, "mqe_ppo_adam: no actor (mqe_actor_create)");
   if (step < 1) return fail(-6, "mqe_ppo_adam: step counts from 1");
-  if (((uintptr_t)grad_dev & 3) || ((uintptr_t)norm_dev & 3)) return fail(-6, "mqe_ppo_adam: misaligned pointer (grad_dev, norm_dev: 4 bytes)");
-  if (ppo_not_finite(&lr)) return fail(-6, "mqe_ppo_adam: lr is not finite");
-  if (ppo_bad_coef(&beta1) || beta1 >= 1.0f) return fail(-6, "mqe_ppo_adam: beta1 must lie in [0, 1)");
-  if (ppo_bad_coef(&beta2) || beta2 >= 1.0f) return fail(-6, "mqe_ppo_adam: beta2 must lie in [0, 1)");
-  if (ppo_bad_coef(&eps)) return fail(-6, "mqe_ppo_adam: eps must be finite and not negative");
-  if (ppo_not_finite(&max_grad_norm)) return fail(-6, "mqe_ppo_adam: max_grad_norm is not finite (0 or below: no clipping)");
+  if (int rc = check_aligned("mqe_ppo_adam", {{grad_dev, 4}, {norm_dev, 4}}, "grad_dev, norm_dev: 4 bytes")) return rc;
+  if (not_finite(&lr)) return fail(-6, "mqe_ppo_adam: lr is not finite");
+  if (negative_or_not_finite(&beta1) || beta1 >= 1.0f) return fail(-6, "mqe_ppo_adam: beta1 must lie in [0, 1)");
+  if (negative_or_not_finite(&beta2) || beta2 >= 1.0f) return fail(-6, "mqe_ppo_adam: beta2 must lie in [0, 1)");
+  if (negative_or_not_finite(&eps)) return fail(-6, "mqe_ppo_adam: eps must be finite and not negative");
+  if (not_finite(&max_grad_norm)) return fail(-6, "mqe_ppo_adam: max_grad_norm is not finite (0 or below: no clipping)");
   if (int rc = ppo_moments(s)) return rc;
   const size_t nb = (size_t)s->act.n_params * 4;
-  const struct { const void* p; size_t bytes; } mine[3] = {{s->act.params, nb}, {s->ppo.moments, 2 * nb}, {s->ppo.norm, 8}};
-  for (int i = 0; i < 3; i++) {
-    if (gae_overlap(grad_dev, nb, mine[i].p, mine[i].bytes)) return fail(-6, "mqe_ppo_adam: %s overlaps the parameter or moment buffers", "grad_dev");
-    if (gae_overlap(norm_dev, 4, mine[i].p, mine[i].bytes)) return fail(-6, "mqe_ppo_adam: %s overlaps the parameter or moment buffers", "norm_dev");
-  }
-  if (gae_overlap(norm_dev, 4, grad_dev, nb)) return fail(-6, "mqe_ppo_adam: %s overlaps grad_dev", "norm_dev");
+  if (int rc = check_disjoint("mqe_ppo_adam", {{norm_dev, 4, "norm_dev"}, {grad_dev, nb, "grad_dev"}, {s->act.params, nb, "the parameter buffer"},
+                                               {s->ppo.moments, 2 * nb, "the moment buffers"}, {s->ppo.norm, 8, "the engine's norm scratch"}}, 2)) return rc;
   hipStream_t q = (hipStream_t)stream;
   const int n = s->act.n_params;
   const bool clip = max_grad_norm > 0.0f;

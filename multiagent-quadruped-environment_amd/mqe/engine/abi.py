@@ -1,4 +1,5 @@
-"""ctypes mirror of include/mqe_hip.h (keep in sync; tests/test_abi.py checks sizes against the built library)."""
+"""ctypes mirror of include/mqe_hip.h: constants, structs and SIGNATURES, the signature of every function the header declares
+(tests/test_abi.py holds the struct sizes against the built library and SIGNATURES against the header's prototypes)."""
 import ctypes as C
 
 ABI_VERSION = 17
@@ -153,17 +154,57 @@ class TensorView(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("ndim", i32), ("shape", C.c_int64 * 4), ("dtype", i32)]
 
 
-def bind(lib, prefix):
-    """Declare argtypes/restypes of the entry points of include/mqe_hip.h for a loaded library."""
-    H = C.c_void_p
+# The signature of EVERY function include/mqe_hip.h declares, {name: (restype, argtypes)}, stated here and nowhere else: load_library()
+# applies the table to the CDLL once and no caller assigns argtypes / restype.  One type rule (tests/test_abi.py holds every entry to the
+# header's prototype under it): int / long long / float -> c_int / c_longlong / c_float; mqe_sim* -> c_void_p, mqe_sim** -> POINTER(c_void_p);
+# a pointer to mqe_sim_desc / mqe_tensor_view / mqe_actor_shape / mqe_ppo_loss -> POINTER of its mirror; every other pointer (device or host
+# data, the stream) -> c_void_p, which takes None, an integer address, a ctypes array and byref(...).
+_H = _P = _STREAM = C.c_void_p            # the handle; a data pointer; the hipStream_t
+_I, _L, _F = C.c_int, C.c_longlong, C.c_float
+_VIEW = C.POINTER(TensorView)
 
-    def fn(name, *args, res=C.c_int):
+
+def _sig(*argtypes, res=C.c_int):
+    return res, argtypes
+
+
+SIGNATURES = {
+    "mqe_last_error": _sig(res=C.c_char_p),
+    "mqe_abi_limits": _sig(_P, _I),
+    "mqe_sim_create": _sig(C.POINTER(SimDesc), C.POINTER(_H)),
+    "mqe_sim_destroy": _sig(_H),
+    "mqe_sim_tensor": _sig(_H, _I, _VIEW),
+    "mqe_actor_create": _sig(_H, C.POINTER(ActorShape)),
+    "mqe_actor_params": _sig(_H, _VIEW),
+    "mqe_rollout": _sig(_H, _I, _P, _P, _L, _P, _P, _P, _I, _STREAM),
+    "mqe_rollout_time_outs": _sig(_H, _P, _I),
+    "mqe_gae": _sig(_H, _I, _P, _L, _P, _P, _F, _F, _I, _P, _P, _P, _STREAM),
+    "mqe_ppo_grad": _sig(_H, _I, _P, _L, _P, _P, _P, _P, _P, _P, _L, _L, C.POINTER(PpoLoss), _I, _P, _P, _STREAM),
+    "mqe_ppo_optimizer": _sig(_H, _VIEW, _VIEW),
+    "mqe_ppo_adam": _sig(_H, _P, _L, _F, _F, _F, _F, _F, _P, _STREAM),
+    "mqe_render_depth": _sig(_H, _P, _I, _I, _F, _P, _P, _F, _STREAM),
+    "mqe_render_view": _sig(_H, _I, _P, _P, _P, _I, _I, _F, _P, _P, _F, _STREAM),
+    "mqe_measure_heights": _sig(_H, _P, _P, _I, _I, _STREAM),
+    "mqe_set_height_refresh": _sig(_H, _P, _P, _I, _I),
+    "mqe_debug_dynamics": _sig(_H, _I, _I, _P, _P, _P),
+    "mqe_debug_times": _sig(_P),
+    "mqe_state_size": _sig(_H, res=_L),
+    "mqe_profile_read": _sig(_H, _P, _I, _P),
+}
+for _names, _s in (("abi_version sizeof_desc", _sig()),          # the families that share a signature
+                   ("compute_torques simulate post_physics_step reset_all step_end step_tail refresh_rigid_body_state history_sync", _sig(_H, _STREAM)),
+                   ("policy_step defender_command step step_begin step_head step_command step_joint state_save state_load", _sig(_H, _P, _STREAM)),
+                   ("post_decimation_step post_physics_stage wrapper_eval", _sig(_H, _I, _STREAM)),
+                   ("set_actor_root_state_indexed set_dof_state_indexed", _sig(_H, _P, _I, _STREAM)),
+                   ("set_rigid_body_refresh debug_stop_phase profile_enable", _sig(_H, _I)),
+                   ("set_return_buffer debug_wave_times debug_tail_times debug_phase_times debug_epilogue_times", _sig(_H, _P))):
+    SIGNATURES.update({"mqe_" + _n: _s for _n in _names.split()})
+SHARED = ("last_error", "sim_create", "sim_destroy", "sim_tensor")      # what the CPU oracle exports as well (mqo_*), with these signatures
+
+
+def bind(lib, prefix="mqe_", names=None):
+    """Puts SIGNATURES on the functions of a loaded library, where it is loaded: all of them (libmqe_hip.so), or the `names` (without prefix)
+    that a library exporting part of the ABI under another prefix shares (the oracle: SHARED as mqo_*)."""
+    for name in names or [n[4:] for n in SIGNATURES]:
         f = getattr(lib, prefix + name)
-        f.argtypes, f.restype = list(args), res
-        return f
-    api = {}
-    api["last_error"] = fn("last_error", res=C.c_char_p)
-    api["sim_create"] = fn("sim_create", C.POINTER(SimDesc), C.POINTER(H))
-    api["sim_destroy"] = fn("sim_destroy", H)
-    api["sim_tensor"] = fn("sim_tensor", H, C.c_int, C.POINTER(TensorView))
-    return api
+        f.restype, f.argtypes = SIGNATURES["mqe_" + name]

@@ -23,7 +23,7 @@ class EngineBase:
 
     def __init__(self, lib, desc, keepalive):
         self.lib, self.desc, self._keep = lib, desc, keepalive
-        self.api = abi.bind(lib, self.prefix)
+        self.api = {name: getattr(lib, self.prefix + name) for name in abi.SHARED}      # bound where the library was loaded
         h = C.c_void_p()
         self._check(self.api["sim_create"](C.byref(desc), C.byref(h)))
         self.h = h

@@ -14,18 +14,38 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.
 
 
 def load_library():
+    """the process-wide CDLL, every function of include/mqe_hip.h bound to its abi.SIGNATURES entry (once, here: no caller sets a signature)"""
     global _LIB
     if _LIB is None:
         path = os.environ.get("MQE_HIP_LIB", LIB_PATH)       # experiments: an alternative build of the same ABI
         if path != LIB_PATH:
             import sys
             print(f"mqe: override in effect: MQE_HIP_LIB={path} (not the in-tree build)", file=sys.stderr)      # never silent
-            _LIB = C.CDLL(path)
-            return _LIB
-        if not os.path.isfile(LIB_PATH):
+        elif not os.path.isfile(LIB_PATH):
             raise RuntimeError(f"HIP engine not built: {LIB_PATH} missing (run `python -c 'import __graft_entry__ as g; g.build()'`)")
-        _LIB = C.CDLL(LIB_PATH)
+        lib = C.CDLL(path)
+        abi.bind(lib)
+        _LIB = lib
     return _LIB
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _need_f32(what, t, shape):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+        raise ValueError(f"{what} must be a contiguous float32 device tensor of shape {shape}")
+
+
+def _need_flags(what, t, shape):
+    if not (t.is_cuda and t.dtype in (torch.bool, torch.uint8) and t.is_contiguous() and tuple(t.shape) == shape):
+        raise ValueError(f"{what} must be a contiguous bool or uint8 device tensor of shape {shape}")
+
+
+def _need_packed(traj):
+    if traj.packed.dtype != torch.float32 or not traj.packed.is_cuda or traj.packed.stride(1) != 1:
+        raise ValueError("traj.packed must be a float32 device tensor (T + 1, row_stride) with unit stride along a row")
 
 
 class Rollout:
@@ -57,22 +77,19 @@ class HipEngine(EngineBase):
         self.torch_device = torch.device(device)
         torch.cuda.set_device(self.torch_device)
         super().__init__(load_library(), desc, keepalive)
-        lib = self.lib
-        vp = C.c_void_p
-        for name, args in (("policy_step", [vp, vp, vp]), ("compute_torques", [vp, vp]), ("simulate", [vp, vp]),
-                           ("post_decimation_step", [vp, C.c_int, vp]), ("post_physics_step", [vp, vp]), ("post_physics_stage", [vp, C.c_int, vp]),
-                           ("reset_all", [vp, vp]), ("step", [vp, vp, vp]), ("step_begin", [vp, vp, vp]), ("step_end", [vp, vp]), ("step_head", [vp, vp, vp]), ("step_tail", [vp, vp]), ("set_return_buffer", [vp, vp]), ("step_joint", [vp, vp, vp]), ("step_command", [vp, vp, vp]), ("defender_command", [vp, vp, vp]),
-                           ("wrapper_eval", [vp, C.c_int, vp]),
-                           ("debug_dynamics", [vp, C.c_int, C.c_int, vp, C.POINTER(C.c_int), vp]),
-                           ("debug_stop_phase", [vp, C.c_int]),
-                           ("debug_wave_times", [vp, vp]), ("debug_tail_times", [vp, vp]),
-                           ("debug_phase_times", [vp, vp]), ("debug_epilogue_times", [vp, vp]),
-                           ("history_sync", [vp, vp]), ("refresh_rigid_body_state", [vp, vp]), ("set_rigid_body_refresh", [vp, C.c_int]),
-                           ("state_save", [vp, vp, vp]), ("state_load", [vp, vp, vp]),
-                           ("profile_enable", [vp, C.c_int]),
-                           ("profile_read", [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)])):
-            f = getattr(lib, "mqe_" + name)
-            f.argtypes, f.restype = args, C.c_int
+        self._actor = self._actor_views = self._height_live = None
+        self._n_policy = 0          # policy steps so far: the slot of T_HISTORY's ring (history())
+        self.ppo_step = 0           # Adam steps taken by ppo_update
+
+    def _invoke(self, name, *args):
+        """mqe_<name>(handle, *args) for the entry points whose refusals callers tell apart by name and code"""
+        rc = getattr(self.lib, "mqe_" + name)(self.h, *args)
+        if rc != 0:
+            raise RuntimeError(f"mqe_{name} failed ({rc}): {self.lib.mqe_last_error().decode()}")
+
+    def _need_actor(self):
+        if self._actor is None:
+            raise RuntimeError("no actor: call create_actor first")
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.torch_device).cuda_stream)
@@ -84,7 +101,7 @@ class HipEngine(EngineBase):
     def policy_step(self, command):
         assert command.is_cuda and command.dtype == torch.float32 and command.is_contiguous()
         self._call("policy_step", C.c_void_p(command.data_ptr()), self._stream())
-        self._n_policy = getattr(self, "_n_policy", 0) + 1
+        self._n_policy += 1
 
     def compute_torques(self):
         self._call("compute_torques", self._stream())
@@ -109,7 +126,7 @@ class HipEngine(EngineBase):
         """Fused Go1.step for control type C (mqe_step_command): (R, num_command_dims) per-robot command rows on the device."""
         assert command.is_cuda and command.dtype == torch.float32 and command.is_contiguous()
         self._call("step_command", C.c_void_p(command.data_ptr()), self._stream())
-        self._n_policy = getattr(self, "_n_policy", 0) + 1
+        self._n_policy += 1
 
     def step_joint(self, actions12):
         """Fused step for control types P / V / T: (R, 12) joint-space actions on the device."""
@@ -140,7 +157,7 @@ class HipEngine(EngineBase):
                 between()
             finally:
                 self._call("step_end", self._stream())
-        self._n_policy = getattr(self, "_n_policy", 0) + 1
+        self._n_policy += 1
 
     def set_return_buffer(self, packed):
         """mqe_set_return_buffer: the following launches write obs | reward | done into `packed` (None: the engine's own buffer)"""
@@ -170,11 +187,7 @@ class HipEngine(EngineBase):
             sh.critic_dims[i] = v
         sh.activation = abi.ACTOR_RELU if activation == "relu" else abi.ACTOR_TANH
         sh.action_gain = float(action_gain)
-        f = self.lib.mqe_actor_create
-        f.argtypes, f.restype = [C.c_void_p, C.POINTER(abi.ActorShape)], C.c_int
-        rc = f(self.h, C.byref(sh))
-        if rc != 0:
-            raise RuntimeError(f"mqe_actor_create failed ({rc}): {self.lib.mqe_last_error().decode()}")
+        self._invoke("actor_create", C.byref(sh))
         self._actor = dict(actor_dims=actor_dims, critic_dims=critic_dims or None, activation=activation, action_gain=float(action_gain))
         self._actor_views = None
         self.ppo_step = 0            # the library dropped Adam's moments with the old actor
@@ -182,13 +195,10 @@ class HipEngine(EngineBase):
     def actor_params(self):
         """{name: zero-copy view} of the engine's parameter buffer (abi.actor_param_layout: actor.0.weight, actor.0.bias, ..., critic.0.weight,
         ..., log_std) + "flat", the whole buffer.  Live device memory: copy_ into the views; later launches on the stream see the values."""
-        if getattr(self, "_actor", None) is None:
-            raise RuntimeError("no actor: call create_actor first")
+        self._need_actor()
         if self._actor_views is None:
             v = abi.TensorView()
-            f = self.lib.mqe_actor_params
-            f.argtypes, f.restype = [C.c_void_p, C.POINTER(abi.TensorView)], C.c_int
-            self._check(f(self.h, C.byref(v)))
+            self._call("actor_params", C.byref(v))
             flat = self._wrap(v.ptr, [int(v.shape[0])], v.dtype)
             views = {n: flat[o:o + int(np.prod(shp))].view(shp) for n, (o, shp) in abi.actor_param_layout(self._actor["actor_dims"], self._actor["critic_dims"]).items()}
             views["flat"] = flat
@@ -207,8 +217,7 @@ class HipEngine(EngineBase):
         (T, N, A', 3), logp (T, N, A'), value (T+1, N, A') or None without a critic.  time_outs=True: the call also records T_TIME_OUT_BUF as
         every step left it (mqe_rollout_time_outs: one N-byte device copy per step) into Rollout.time_outs, (T, N) bool -- a fresh tensor,
         or out.time_outs; without it the call enqueues what it always did and Rollout.time_outs stays as it was (None on a fresh one)."""
-        if getattr(self, "_actor", None) is None:
-            raise RuntimeError("no actor: call create_actor first")
+        self._need_actor()
         T = int(T)
         N, Aw, D = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
         dev = self.torch_device
@@ -224,38 +233,25 @@ class HipEngine(EngineBase):
             if out.packed.stride(1) != 1 or out.packed.stride(0) < out.packed.shape[1]:
                 raise ValueError("out.packed must be (T + 1, row_stride) with unit stride along a row")
             for name, t, shape in (("actions", out.actions, (T, N, Aw, 3)), ("logp", out.logp, (T, N, Aw)), ("value", out.value, (T + 1, N, Aw))):
-                if t is None:
-                    continue
-                if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
-                    raise ValueError(f"out.{name} must be a contiguous float32 device tensor of shape {shape}")
+                if t is not None:
+                    _need_f32(f"out.{name}", t, shape)
             if out.actions is None or out.packed.dtype != torch.float32 or not out.packed.is_cuda:
                 raise ValueError("out.packed and out.actions must be float32 device tensors")
         if time_outs:
             if out.time_outs is None:
                 out.time_outs = torch.zeros(max(T, 0), N, dtype=torch.uint8, device=dev).view(torch.bool)
-            rec = out.time_outs
-            if not (rec.is_cuda and rec.dtype in (torch.bool, torch.uint8) and rec.is_contiguous() and tuple(rec.shape) == (T, N)):
-                raise ValueError(f"out.time_outs must be a contiguous bool or uint8 device tensor of shape {(T, N)}")
+            _need_flags("out.time_outs", out.time_outs, (T, N))
         if obs0 is not None:
             assert obs0.is_cuda and obs0.dtype == torch.float32 and obs0.is_contiguous() and tuple(obs0.shape) == (N, Aw, D)
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
-        f = self.lib.mqe_rollout
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        f.restype = C.c_int
-        reg = self.lib.mqe_rollout_time_outs
-        reg.argtypes, reg.restype = [C.c_void_p, C.c_void_p, C.c_int], C.c_int
         if time_outs:
-            self._check(reg(self.h, ptr(out.time_outs), max(T, 1)))       # T <= 0: mqe_rollout itself refuses
+            self._call("rollout_time_outs", _ptr(out.time_outs), max(T, 1))       # T <= 0: mqe_rollout itself refuses
         try:
-            rc = f(self.h, T, ptr(obs0), ptr(out.packed), int(out.packed.stride(0)), ptr(out.actions), ptr(out.logp), ptr(out.value),
-                   abi.ROLLOUT_DETERMINISTIC if deterministic else 0, self._stream())
-            msg = self.lib.mqe_last_error().decode() if rc != 0 else ""
+            self._invoke("rollout", T, _ptr(obs0), _ptr(out.packed), int(out.packed.stride(0)), _ptr(out.actions), _ptr(out.logp), _ptr(out.value),
+                         abi.ROLLOUT_DETERMINISTIC if deterministic else 0, self._stream())
         finally:
             if time_outs:
-                reg(self.h, None, 0)         # the record belongs to this call alone, refused or not
-        if rc != 0:
-            raise RuntimeError(f"mqe_rollout failed ({rc}): {msg}")
-        self._n_policy = getattr(self, "_n_policy", 0) + T
+                self.lib.mqe_rollout_time_outs(self.h, None, 0)         # the record belongs to this call alone, refused or not
+        self._n_policy += T
         return out
 
     def gae(self, traj, gamma, lam=0.95, normalize=False, out=None):
@@ -272,33 +268,21 @@ class HipEngine(EngineBase):
         N, Aw, D = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
         dev = self.torch_device
         shape = (T, N, Aw)
-        ok = lambda t, shp: t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shp
-        if not ok(traj.value, (T + 1, N, Aw)):
-            raise ValueError(f"traj.value must be a contiguous float32 device tensor of shape {(T + 1, N, Aw)}")
-        if traj.packed.dtype != torch.float32 or not traj.packed.is_cuda or traj.packed.stride(1) != 1:
-            raise ValueError("traj.packed must be a float32 device tensor (T + 1, row_stride) with unit stride along a row")
+        _need_f32("traj.value", traj.value, (T + 1, N, Aw))
+        _need_packed(traj)
         rec = traj.time_outs
-        if rec is not None and not (rec.is_cuda and rec.dtype in (torch.bool, torch.uint8) and rec.is_contiguous() and tuple(rec.shape) == (T, N)):
-            raise ValueError(f"traj.time_outs must be a contiguous bool or uint8 device tensor of shape {(T, N)}")
+        if rec is not None:
+            _need_flags("traj.time_outs", rec, (T, N))
         adv, ret, stats = (out.advantages, out.returns, out.adv_stats) if out is not None else (None, None, None)
-        for name, t in (("advantages", adv), ("returns", ret)):
-            if t is not None and not ok(t, shape):
-                raise ValueError(f"out.{name} must be a contiguous float32 device tensor of shape {shape}")
-        if stats is not None and not ok(stats, (2,)):
-            raise ValueError("out.adv_stats must be a contiguous float32 device tensor of shape (2,)")
+        for name, t, shp in (("advantages", adv, shape), ("returns", ret, shape), ("adv_stats", stats, (2,))):
+            if t is not None:
+                _need_f32(f"out.{name}", t, shp)
         adv = adv if adv is not None else torch.empty(shape, dtype=torch.float32, device=dev)
         ret = ret if ret is not None else torch.empty(shape, dtype=torch.float32, device=dev)
         if normalize and stats is None:
             stats = torch.empty(2, dtype=torch.float32, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
-        f = self.lib.mqe_gae
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
-                      C.c_void_p, C.c_void_p]
-        f.restype = C.c_int
-        rc = f(self.h, T, ptr(traj.packed), int(traj.packed.stride(0)), ptr(traj.value), ptr(rec), float(gamma), float(lam),
-               abi.GAE_NORMALIZE if normalize else 0, ptr(adv), ptr(ret), ptr(stats if normalize else None), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mqe_gae failed ({rc}): {self.lib.mqe_last_error().decode()}")
+        self._invoke("gae", T, _ptr(traj.packed), int(traj.packed.stride(0)), _ptr(traj.value), _ptr(rec), float(gamma), float(lam),
+                     abi.GAE_NORMALIZE if normalize else 0, _ptr(adv), _ptr(ret), _ptr(stats if normalize else None), self._stream())
         traj.advantages, traj.returns, traj.adv_stats = adv, ret, (stats if normalize else None)
         return traj
 
@@ -311,8 +295,7 @@ class HipEngine(EngineBase):
         an index, the samples first .. first + count; count=None: everything from `first` on.  value_clip: None (plain squared error) or the
         clamp c_v of the clipped value loss.  out: (grad, stats) tensors to write instead of fresh ones.  -> (grad, stats): grad float32
         [n_params] in actor_params()["flat"]'s layout, stats float32 [6]: mean L_pi, mean L_v, entropy H, L, approximate KL, clip share."""
-        if getattr(self, "_actor", None) is None:
-            raise RuntimeError("no actor: call create_actor first")
+        self._need_actor()
         if self._actor["critic_dims"] is None:
             raise ValueError("ppo_grad: the loss has a value term and the actor was created without a critic")
         for name in ("value", "logp", "advantages", "returns"):
@@ -321,12 +304,9 @@ class HipEngine(EngineBase):
         T = int(traj.T)
         N, Aw, D = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
         dev = self.torch_device
-        ok = lambda t, shp: t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shp
         for name, shp in (("actions", (T, N, Aw, 3)), ("logp", (T, N, Aw)), ("value", (T + 1, N, Aw)), ("advantages", (T, N, Aw)), ("returns", (T, N, Aw))):
-            if not ok(getattr(traj, name), shp):
-                raise ValueError(f"traj.{name} must be a contiguous float32 device tensor of shape {shp}")
-        if traj.packed.dtype != torch.float32 or not traj.packed.is_cuda or traj.packed.stride(1) != 1:
-            raise ValueError("traj.packed must be a float32 device tensor (T + 1, row_stride) with unit stride along a row")
+            _need_f32(f"traj.{name}", getattr(traj, name), shp)
+        _need_packed(traj)
         n_params = self.actor_params()["flat"].numel()
         total = T * N * Aw
         if index is not None:
@@ -338,35 +318,24 @@ class HipEngine(EngineBase):
         if index is not None and (first < 0 or count < 1 or first + count > total):
             raise ValueError(f"index holds {total} samples: first={first}, count={count} reach outside it")
         grad, stats = out if out is not None else (None, None)
-        if grad is not None and not ok(grad, (n_params,)):
-            raise ValueError(f"out[0] (grad) must be a contiguous float32 device tensor of shape {(n_params,)}")
-        if stats is not None and not ok(stats, (abi.PPO_STATS,)):
-            raise ValueError(f"out[1] (stats) must be a contiguous float32 device tensor of shape {(abi.PPO_STATS,)}")
+        for what, t, shp in (("out[0] (grad)", grad, (n_params,)), ("out[1] (stats)", stats, (abi.PPO_STATS,))):
+            if t is not None:
+                _need_f32(what, t, shp)
         grad = grad if grad is not None else torch.empty(n_params, dtype=torch.float32, device=dev)
         stats = stats if stats is not None else torch.empty(abi.PPO_STATS, dtype=torch.float32, device=dev)
         loss = abi.PpoLoss(float(clip), float(value_coef), float(entropy_coef), float(value_clip) if value_clip is not None else 0.0)
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
-        f = self.lib.mqe_ppo_grad
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong] + [C.c_void_p] * 6 + [C.c_longlong, C.c_longlong, C.POINTER(abi.PpoLoss), C.c_int,
-                                                                                          C.c_void_p, C.c_void_p, C.c_void_p]
-        f.restype = C.c_int
-        rc = f(self.h, T, ptr(traj.packed), int(traj.packed.stride(0)), ptr(traj.actions), ptr(traj.logp), ptr(traj.value), ptr(traj.advantages),
-               ptr(traj.returns), ptr(index), first, count, C.byref(loss), abi.PPO_CLIP_VALUE if value_clip is not None else 0, ptr(grad), ptr(stats),
-               self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mqe_ppo_grad failed ({rc}): {self.lib.mqe_last_error().decode()}")
+        self._invoke("ppo_grad", T, _ptr(traj.packed), int(traj.packed.stride(0)), _ptr(traj.actions), _ptr(traj.logp), _ptr(traj.value),
+                     _ptr(traj.advantages), _ptr(traj.returns), _ptr(index), first, count, C.byref(loss),
+                     abi.PPO_CLIP_VALUE if value_clip is not None else 0, _ptr(grad), _ptr(stats), self._stream())
         return grad, stats
 
     def optimizer_state(self):
         """{"exp_avg", "exp_avg_sq"}: zero-copy views of Adam's two moment buffers (mqe_ppo_optimizer), float32 [n_params] in the layout of
         actor_params()["flat"], zero until the first adam_step; a new create_actor drops them.  With actor_params()["flat"] and the step count
         (HipEngine.ppo_step) they are the whole optimiser checkpoint."""
-        if getattr(self, "_actor", None) is None:
-            raise RuntimeError("no actor: call create_actor first")
+        self._need_actor()
         m, v = abi.TensorView(), abi.TensorView()
-        f = self.lib.mqe_ppo_optimizer
-        f.argtypes, f.restype = [C.c_void_p, C.POINTER(abi.TensorView), C.POINTER(abi.TensorView)], C.c_int
-        self._check(f(self.h, C.byref(m), C.byref(v)))
+        self._call("ppo_optimizer", C.byref(m), C.byref(v))
         return {"exp_avg": self._wrap(m.ptr, [int(m.shape[0])], m.dtype), "exp_avg_sq": self._wrap(v.ptr, [int(v.shape[0])], v.dtype)}
 
     def adam_step(self, grad, step, lr, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, norm_out=None):
@@ -378,13 +347,8 @@ class HipEngine(EngineBase):
             raise ValueError(f"grad must be a contiguous float32 device tensor of {n_params} elements")
         if norm_out is not None and not (norm_out.is_cuda and norm_out.dtype == torch.float32 and norm_out.numel() >= 1):
             raise ValueError("norm_out must be a float32 device tensor")
-        f = self.lib.mqe_ppo_adam
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
-        f.restype = C.c_int
-        rc = f(self.h, C.c_void_p(grad.data_ptr()), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-               float(max_grad_norm) if max_grad_norm is not None else 0.0, C.c_void_p(norm_out.data_ptr() if norm_out is not None else None), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mqe_ppo_adam failed ({rc}): {self.lib.mqe_last_error().decode()}")
+        self._invoke("ppo_adam", grad.data_ptr(), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                     float(max_grad_norm) if max_grad_norm is not None else 0.0, _ptr(norm_out), self._stream())
 
     def ppo_update(self, traj, epochs, minibatches, lr, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=None, betas=(0.9, 0.999), eps=1e-8,
                    max_grad_norm=None, generator=None):
@@ -410,7 +374,7 @@ class HipEngine(EngineBase):
                 count = per if b + 1 < minibatches else total - first
                 self.ppo_grad(traj, index=perm, first=first, count=count, clip=clip, value_coef=value_coef, entropy_coef=entropy_coef,
                               value_clip=value_clip, out=(grad, stats[e, b]))
-                self.ppo_step = getattr(self, "ppo_step", 0) + 1
+                self.ppo_step += 1
                 self.adam_step(grad, self.ppo_step, lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm)
         return stats
 
@@ -423,15 +387,13 @@ class HipEngine(EngineBase):
     def save_state(self):
         """Checkpoint: every state buffer of the handle + its ring positions as one host blob (numpy uint8); see mqe_state_save.
         Not part of it: a caller-owned return buffer (mqe_set_return_buffer) and the wrappers' host-side counters."""
-        self.lib.mqe_state_size.argtypes, self.lib.mqe_state_size.restype = [C.c_void_p], C.c_longlong
         blob = np.empty(int(self.lib.mqe_state_size(self.h)) + 8, np.uint8)
         self._call("state_save", C.c_void_p(blob.ctypes.data), self._stream())
-        blob[-8:] = np.frombuffer(np.int64(getattr(self, "_n_policy", 0)).tobytes(), np.uint8)      # host-side frame counter of history()
+        blob[-8:] = np.frombuffer(np.int64(self._n_policy).tobytes(), np.uint8)      # host-side frame counter of history()
         return blob
 
     def load_state(self, blob):
         blob = np.ascontiguousarray(blob, np.uint8)
-        self.lib.mqe_state_size.argtypes, self.lib.mqe_state_size.restype = [C.c_void_p], C.c_longlong
         want = int(self.lib.mqe_state_size(self.h)) + 8
         if blob.nbytes != want:     # the C side checks the header against the handle, not the length of the caller's buffer
             raise ValueError(f"checkpoint blob has {blob.nbytes} bytes, this handle's state takes {want} (truncated file or another scene shape)")
@@ -444,13 +406,8 @@ class HipEngine(EngineBase):
         R = self.desc.num_envs * self.desc.num_agents
         if out is None:
             out = torch.empty(R, int(height), int(width), dtype=torch.float32, device=self.torch_device)
-        f = self.lib.mqe_render_depth
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_void_p]
-        f.restype = C.c_int
         p3, r3 = (C.c_float * 3)(*[float(x) for x in pos]), (C.c_float * 3)(*[float(x) for x in rpy])
-        rc = f(self.h, C.c_void_p(out.data_ptr()), int(height), int(width), float(hfov_deg), p3, r3, float(far), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mqe_render_depth failed ({rc}): {self.lib.mqe_last_error().decode()}")
+        self._invoke("render_depth", out.data_ptr(), int(height), int(width), float(hfov_deg), p3, r3, float(far), self._stream())
         return out
 
     def render_view(self, env, height, width, hfov_deg, eye, lookat, far=60.0, rgba=None, geom=False, ids=False):
@@ -467,15 +424,8 @@ class HipEngine(EngineBase):
         assert rgba.is_cuda and rgba.dtype == torch.uint8 and rgba.is_contiguous() and rgba.numel() == H * W * 4
         g = torch.empty(H, W, 4, dtype=torch.float32, device=dev) if geom else None
         i = torch.empty(H, W, dtype=torch.int32, device=dev) if ids else None
-        f = self.lib.mqe_render_view
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
-                      C.c_float, C.c_void_p]
-        f.restype = C.c_int
         e3, l3 = (C.c_float * 3)(*[float(x) for x in eye]), (C.c_float * 3)(*[float(x) for x in lookat])
-        rc = f(self.h, int(env), C.c_void_p(rgba.data_ptr()), C.c_void_p(g.data_ptr() if geom else None), C.c_void_p(i.data_ptr() if ids else None),
-               H, W, float(hfov_deg), e3, l3, float(far), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mqe_render_view failed ({rc}): {self.lib.mqe_last_error().decode()}")
+        self._invoke("render_view", int(env), rgba.data_ptr(), _ptr(g), _ptr(i), H, W, float(hfov_deg), e3, l3, float(far), self._stream())
         out = (rgba,) + ((g,) if geom else ()) + ((i,) if ids else ())
         return out if len(out) > 1 else rgba
 
@@ -498,13 +448,8 @@ class HipEngine(EngineBase):
         return pts
 
     def _height_call(self, name, out, pts, scenery, *tail):
-        f = getattr(self.lib, "mqe_" + name)
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * len(tail)
-        f.restype = C.c_int
-        rc = f(self.h, C.c_void_p(out.data_ptr() if out is not None else None), C.c_void_p(pts.ctypes.data if pts is not None else None),
-               int(pts.shape[0]) if pts is not None else 0, abi.HSCAN_SCENERY if scenery else 0, *tail)
-        if rc != 0:
-            raise RuntimeError(f"mqe_{name} failed ({rc}): {self.lib.mqe_last_error().decode()}")
+        self._invoke(name, _ptr(out), pts.ctypes.data if pts is not None else None, int(pts.shape[0]) if pts is not None else 0,
+                     abi.HSCAN_SCENERY if scenery else 0, *tail)
 
     def measure_heights(self, points_xy, out=None, scenery=False):
         """(R, P) device tensor: the height of the static surface under the yaw-aligned grid `points_xy` ((P, 2) base-frame offsets) around
@@ -527,7 +472,7 @@ class HipEngine(EngineBase):
             return None
         pts = self._height_grid(points_xy)
         R = self.desc.num_envs * self.desc.num_agents
-        live = getattr(self, "_height_live", None)
+        live = self._height_live
         if live is None or live.shape != (R, pts.shape[0]):
             live = torch.zeros(R, pts.shape[0], dtype=torch.float32, device=self.torch_device)
         self._height_call("set_height_refresh", live, pts, scenery)
@@ -541,7 +486,7 @@ class HipEngine(EngineBase):
     def history(self):
         """(R, 2100) time-ordered locomotion history gathered from the ring (host-side bookkeeping of the slot)."""
         h = self.tensor(abi.T_HISTORY)
-        pos = getattr(self, "_n_policy", 0) % abi.HIST
+        pos = self._n_policy % abi.HIST
         idx = (torch.arange(abi.HIST, device=h.device) + pos) % abi.HIST
         return h[:, idx, :70].reshape(h.shape[0], -1)
 

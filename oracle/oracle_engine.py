@@ -51,6 +51,7 @@ def load_library(f64=False):
         if not os.path.isfile(path):
             build()
         _LIBS[name] = C.CDLL(path)
+        abi.bind(_LIBS[name], "mqo_", abi.SHARED)       # the four functions both libraries export with one signature; the rest: OracleEngine
         if not os.environ.get("OMP_NUM_THREADS"):       # one OpenMP runtime per process: the setting holds for every build of the checker loaded afterwards
             _LIBS[name].mqo_set_num_threads(usable_cpus())
     return _LIBS[name]
@@ -63,10 +64,12 @@ class OracleEngine(EngineBase):
     def __init__(self, desc, keepalive, f64=False, device="cpu"):
         self.torch_device = torch.device("cpu")
         super().__init__(load_library(f64), desc, keepalive)
-        vp = C.c_void_p
+        vp, ci, cf = C.c_void_p, C.c_int, C.c_float
         for name, args in (("policy_step", [vp, vp]), ("compute_torques", [vp]), ("simulate", [vp]),
-                           ("post_decimation_step", [vp, C.c_int]), ("post_physics_step", [vp]), ("post_physics_stage", [vp, C.c_int]),
-                           ("reset_all", [vp]), ("step", [vp, vp]), ("step_joint", [vp, vp]), ("hist_pos", [vp]), ("wrapper_eval", [vp, C.c_int])):
+                           ("post_decimation_step", [vp, ci]), ("post_physics_step", [vp]), ("post_physics_stage", [vp, ci]),
+                           ("reset_all", [vp]), ("step", [vp, vp]), ("step_joint", [vp, vp]), ("hist_pos", [vp]), ("wrapper_eval", [vp, ci]),
+                           ("defender_command", [vp, vp]), ("debug_dynamics", [vp, ci, ci, vp, vp, vp, vp]),
+                           ("render_depth", [vp, vp, ci, ci, cf, vp, vp, cf]), ("history", [vp, vp])):
             f = getattr(self.lib, "mqo_" + name)
             f.argtypes, f.restype = args, C.c_int
 
@@ -122,7 +125,6 @@ class OracleEngine(EngineBase):
 
     def defender_command(self, out):
         o = np.zeros((self.desc.num_envs, 3), np.float32)
-        self.lib.mqo_defender_command.argtypes = [C.c_void_p, C.c_void_p]
         self.lib.mqo_defender_command(self.h, C.c_void_p(o.ctypes.data))
         out.copy_(torch.from_numpy(o))
 
@@ -131,9 +133,7 @@ class OracleEngine(EngineBase):
         minv = np.zeros((18, 18), np.float32)
         nc = C.c_int(0)
         con = np.zeros((64, 8), np.float32)
-        f = self.lib.mqo_debug_dynamics
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
-        f(self.h, int(env), int(robot), C.c_void_p(M.ctypes.data), C.c_void_p(minv.ctypes.data), C.byref(nc), C.c_void_p(con.ctypes.data))
+        self.lib.mqo_debug_dynamics(self.h, int(env), int(robot), C.c_void_p(M.ctypes.data), C.c_void_p(minv.ctypes.data), C.byref(nc), C.c_void_p(con.ctypes.data))
         return M, minv, con[:nc.value]
 
     def history_sync(self):
@@ -144,11 +144,8 @@ class OracleEngine(EngineBase):
         negative depth along the optical axis, -inf = nothing within `far` -- what the HIP kernel is compared with (tests/test_camera_gpu.py)"""
         R = self.desc.num_envs * self.desc.num_agents
         img = np.zeros((R, int(height), int(width)), np.float32)
-        f = self.lib.mqo_render_depth
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float]
-        f.restype = C.c_int
         p3, r3 = (C.c_float * 3)(*[float(x) for x in pos]), (C.c_float * 3)(*[float(x) for x in rpy])
-        rc = f(self.h, C.c_void_p(img.ctypes.data), int(height), int(width), float(hfov_deg), p3, r3, float(far))
+        rc = self.lib.mqo_render_depth(self.h, C.c_void_p(img.ctypes.data), int(height), int(width), float(hfov_deg), p3, r3, float(far))
         if rc != 0:
             raise RuntimeError(f"mqo_render_depth failed ({rc}): {self.lib.mqo_last_error().decode()}")
         return torch.from_numpy(img)
@@ -156,6 +153,5 @@ class OracleEngine(EngineBase):
     def history(self):
         R = self.desc.num_envs * self.desc.num_agents
         out = np.zeros((R, 2100), np.float32)
-        self.lib.mqo_history.argtypes = [C.c_void_p, C.c_void_p]
         self.lib.mqo_history(self.h, C.c_void_p(out.ctypes.data))
         return torch.from_numpy(out)

@@ -25,6 +25,51 @@ def test_header_symbols_exported():
         assert hasattr(lib, s), f"{s} declared in include/mqe_hip.h but not exported by libmqe_hip.so"
 
 
+def prototypes():
+    """{name: (return type, [parameter declarations])} of every function the header declares"""
+    h = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mqe_hip.h")).read(), flags=re.S)
+    found = re.findall(r"^(const char\*|int|long long)\s+(mqe_\w+)\s*\((.*?)\);", h, re.M | re.S)
+    return {name: (ret, [] if args.strip() == "void" else [" ".join(a.split()) for a in args.split(",")]) for ret, name, args in found}
+
+
+def ctype_of(decl):
+    """the one type rule of abi.SIGNATURES: a parameter declaration of the header -> its ctypes type"""
+    base, stars = re.fullmatch(r"(?:const )?(.+?) ?(\**) ?\w+", decl).groups()      # [const] type [*[*]] name
+    t = base + stars
+    mirrors = {"mqe_sim_desc*": abi.SimDesc, "mqe_tensor_view*": abi.TensorView, "mqe_actor_shape*": abi.ActorShape, "mqe_ppo_loss*": abi.PpoLoss}
+    if t in mirrors:
+        return C.POINTER(mirrors[t])
+    if t == "mqe_sim**":
+        return C.POINTER(C.c_void_p)
+    if t in ("mqe_sim*", "float*", "int32_t*", "uint8_t*", "int*", "long long*", "void*"):
+        return C.c_void_p
+    return {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float}[t]
+
+
+def test_signature_table_is_the_header_and_is_what_the_library_carries():
+    """abi.SIGNATURES states the ctypes signature of every prototype of include/mqe_hip.h, each derived from the header by one rule, and
+    load_library() has put exactly these on the functions of the process-wide CDLL: no call site states a signature of its own."""
+    protos = prototypes()
+    assert len(protos) == 53 and set(protos) == set(declared_symbols()) == set(abi.SIGNATURES)
+    returns = {"int": C.c_int, "long long": C.c_longlong, "const char*": C.c_char_p}
+    for name, (ret, params) in protos.items():
+        restype, argtypes = abi.SIGNATURES[name]
+        assert restype is returns[ret], name
+        assert len(argtypes) == len(params), (name, params)
+        for i, (decl, have) in enumerate(zip(params, argtypes)):
+            assert have is ctype_of(decl), (name, i, decl, have)
+    from mqe.engine.hip_engine import load_library
+    lib = load_library()
+    for name, (restype, argtypes) in abi.SIGNATURES.items():
+        f = getattr(lib, name)
+        assert f.restype is restype and tuple(f.argtypes) == tuple(argtypes), name
+
+
+def test_the_engine_binding_states_no_signature():
+    src = open(os.path.join(ROOT, "multiagent-quadruped-environment_amd", "mqe", "engine", "hip_engine.py")).read()
+    assert "argtypes" not in src and "restype" not in src
+
+
 def test_struct_mirror_size():
     lib = C.CDLL(LIB_PATH)
     assert lib.mqe_abi_version() == abi.ABI_VERSION

@@ -27,14 +27,6 @@ def handle(N):
     return _HANDLES[N]
 
 
-def raw_gae(eng):
-    f = eng.lib.mqe_gae
-    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
-                  C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
-    return f
-
-
 def synth(shape):
     """the shared synthetic trajectory of a shape (host side: made once, never changed)"""
     if shape not in _SYNTH:
@@ -55,7 +47,7 @@ def call(eng, s, t, gamma, lam, with_to, flags=0, want_stats=False, **kw):
              to=t["time_outs"].data_ptr() if with_to else None, gamma=gamma, lam=lam, flags=flags, adv=t["adv"].data_ptr(), ret=t["ret"].data_ptr(),
              stats=t["stats"].data_ptr() if want_stats else None)
     a.update(kw)
-    return raw_gae(eng)(a["h"], a["T"], a["packed"], a["stride"], a["value"], a["to"], a["gamma"], a["lam"], a["flags"], a["adv"], a["ret"], a["stats"],
+    return eng.lib.mqe_gae(a["h"], a["T"], a["packed"], a["stride"], a["value"], a["to"], a["gamma"], a["lam"], a["flags"], a["adv"], a["ret"], a["stats"],
                         eng._stream())
 
 
@@ -276,19 +268,18 @@ def test_normalize_needs_two_values():
 
 
 def test_refusals_of_the_time_out_record():
-    from test_rollout_gpu import _buffers, _is_sent, _raw_rollout
+    from test_rollout_gpu import _buffers, _is_sent
     N, T = 3, 4
     eng = engine("go1gate", N)
     install(eng, "tanh7", True, pseed=1)
     eng.reset_all()
     reg = eng.lib.mqe_rollout_time_outs
-    reg.argtypes, reg.restype = [C.c_void_p, C.c_void_p, C.c_int], C.c_int
     rec = torch.full((T * N + 64,), 0x5A, dtype=torch.uint8, device=eng.torch_device)
     assert reg(None, rec.data_ptr(), T) == -1 and eng.lib.mqe_last_error().decode()
     for cap in (0, -1):
         assert reg(eng.h, rec.data_ptr(), cap) == -6 and "capacity_steps" in eng.lib.mqe_last_error().decode()
     assert reg(eng.h, rec.data_ptr(), T - 1) == 0
-    f = _raw_rollout(eng)
+    f = eng.lib.mqe_rollout
     r, flat = _buffers(eng, T)
     p = lambda x: C.c_void_p(x.data_ptr())
     args = (eng.h, T, None, p(r.packed), int(r.packed.stride(0)), p(r.actions), p(r.logp), p(r.value), 0)

@@ -144,10 +144,7 @@ def test_roots_far_outside_the_map_read_the_clamped_edge():
 def test_refusals_launch_nothing(small):
     d, e, info = small
     R = 3 * d.num_agents
-    f = e.lib.mqe_measure_heights
-    f.argtypes, f.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p], C.c_int
-    g = e.lib.mqe_set_height_refresh
-    g.argtypes, g.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int], C.c_int
+    f, g = e.lib.mqe_measure_heights, e.lib.mqe_set_height_refresh
     pts = np.zeros((1025, 2), np.float32)
     out = torch.full((R * 1025,), -777.0, device="cuda")
     o, p = C.c_void_p(out.data_ptr()), C.c_void_p(pts.ctypes.data)

@@ -53,14 +53,6 @@ def upload(s, dev):
     return t
 
 
-def raw_grad(eng):
-    f = eng.lib.mqe_ppo_grad
-    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong] + [C.c_void_p] * 6 + [C.c_longlong, C.c_longlong, C.POINTER(abi.PpoLoss), C.c_int,
-                                                                                      C.c_void_p, C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
-    return f
-
-
 def call(eng, s, t, first, count, use_index, cfg=CFG, want_stats=True, **kw):
     loss = abi.PpoLoss(cfg["clip"], cfg["value_coef"], cfg["entropy_coef"], cfg["value_clip"] if cfg["value_clip"] is not None else 0.0)
     a = dict(h=eng.h, T=s["T"], packed=t["packed"].data_ptr(), stride=s["stride"], actions=t["actions"].data_ptr(), logp=t["logp_old"].data_ptr(),
@@ -68,7 +60,7 @@ def call(eng, s, t, first, count, use_index, cfg=CFG, want_stats=True, **kw):
              first=first, count=count, loss=C.byref(loss), flags=abi.PPO_CLIP_VALUE if cfg["value_clip"] is not None else 0,
              grad=t["grad"].data_ptr(), stats=t["stats"].data_ptr() if want_stats else None)
     a.update(kw)
-    return raw_grad(eng)(a["h"], a["T"], a["packed"], a["stride"], a["actions"], a["logp"], a["value"], a["adv"], a["ret"], a["index"], a["first"],
+    return eng.lib.mqe_ppo_grad(a["h"], a["T"], a["packed"], a["stride"], a["actions"], a["logp"], a["value"], a["adv"], a["ret"], a["index"], a["first"],
                          a["count"], a["loss"], a["flags"], a["grad"], a["stats"], eng._stream())
 
 
@@ -207,13 +199,6 @@ def test_row_weighted_mean_of_two_shards_is_the_whole_batch():
 
 
 # ---- 5. Adam -----------------------------------------------------------------------------------------------------------------------------------
-def raw_adam(eng):
-    f = eng.lib.mqe_ppo_adam
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
-    f.restype = C.c_int
-    return f
-
-
 @pytest.mark.parametrize("max_norm", [None, 0.5], ids=["noclip", "clip"])
 @pytest.mark.parametrize("net", ["tanh64x64", "tanh256x3"])
 def test_adam_steps_against_float64(net, max_norm):
@@ -328,7 +313,7 @@ def test_refusals_of_mqe_ppo_adam():
     g = torch.full((n + 8,), 0.25, device=dev)
     norm = torch.full((2,), 7.0, device=dev)
     before = [x.clone() for x in (views["flat"], opt["exp_avg"], opt["exp_avg_sq"])]
-    f = raw_adam(eng)
+    f = eng.lib.mqe_ppo_adam
 
     def refused(code, word, **kw):
         a = dict(h=eng.h, grad=g.data_ptr(), step=1, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, max_norm=0.5, norm=norm.data_ptr())

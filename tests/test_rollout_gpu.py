@@ -351,18 +351,11 @@ def test_no_side_effects_and_live_parameters():
 
 
 # ---- 8. refusals ---------------------------------------------------------------------------------------------------------------------------
-def _raw_rollout(eng):
-    f = eng.lib.mqe_rollout
-    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    f.restype = C.c_int
-    return f
-
-
 def test_refusals():
     N, T = 3, 2
     eng = engine("go1gate", N)
     eng.reset_all()
-    f = _raw_rollout(eng)
+    f = eng.lib.mqe_rollout
     r, flat = _buffers(eng, T)
     p = lambda t, off=0: C.c_void_p((t.data_ptr() + off) if t is not None else None)
     stride = int(r.packed.stride(0))
@@ -413,9 +406,7 @@ def test_refusals():
     sh = abi.ActorShape(obs_dim=16, act_dim=3, actor_layers=5, activation=0, action_gain=1.0)      # the same through the C entry point itself
     for i, v in enumerate([16, 8, 8, 8, 8]):
         sh.actor_dims[i] = v
-    fc = eng.lib.mqe_actor_create
-    fc.argtypes, fc.restype = [C.c_void_p, C.POINTER(abi.ActorShape)], C.c_int
-    assert fc(eng.h, C.byref(sh)) == -6 and "Linear layers" in eng.lib.mqe_last_error().decode()
+    assert eng.lib.mqe_actor_create(eng.h, C.byref(sh)) == -6 and "Linear layers" in eng.lib.mqe_last_error().decode()
     stub = engine("go1football-1vs1", 2)
     assert "no task observation" in create_refused(stub, [int(stub.tensor(abi.T_WRAPPER_OBS).shape[-1]), 8, 3])
     stub.close()

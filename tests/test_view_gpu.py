@@ -52,9 +52,6 @@ def view(e, env, h, w, fov, eye, lookat, far=60.0):
 def raw_view(e, env, rgba, geom, ids, h, w, fov, eye, lookat, far):
     """mqe_render_view itself, with the caller's pointers (None = null): its return code"""
     f = e.lib.mqe_render_view
-    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
-                  C.c_float, C.c_void_p]
-    f.restype = C.c_int
     ptr = lambda t: C.c_void_p(t if isinstance(t, int) else t.data_ptr()) if t is not None else C.c_void_p(None)
     v3 = lambda v: (C.c_float * 3)(*[float(x) for x in v]) if v is not None else None
     return f(e.h, int(env), ptr(rgba), ptr(geom), ptr(ids), int(h), int(w), float(fov), v3(eye), v3(lookat), float(far), e._stream())
