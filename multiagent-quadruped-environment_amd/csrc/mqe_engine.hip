@@ -674,8 +674,10 @@ static int stage_policy(mqe_sim* s) {
   if (ad.dims[0] != 2100 || bd.dims[0] != 2102 || bd.dims[bd.n_layers] != 12 || ad.dims[ad.n_layers] != 2)
     return fail(-6, "policy I/O must be adaptation 2100->2, body 2102->12 (go1.py:395,404,29)");
   s->ada_h0 = ad.dims[1]; s->body_h0 = bd.dims[1];
-  if (s->ada_h0 % GB_N || s->body_h0 % GB_N) return fail(-6, "first hidden sizes must be multiples of 64");
-  std::vector<int> krow(2100);
+  // The body's columns of the fused layer 0 start at ada_h0, so that width keeps whole 64-column tiles.  The body's own first width is free:
+  // l0.Npad rounds ada_h0 + body_h0 up to 64 with zero weights and zero bias, the next layer's K (rounded up to 16, never past Npad) reads
+  // those columns as the zeros they are, and k_body_l0_finish touches the real ones only.
+  if (s->ada_h0 % GB_N) return fail(-6, "the adaptation module's first hidden size must be a multiple of 64");  std::vector<int> krow(2100);
   for (int k = 0; k < 2100; k++) krow[k] = (k / 70) * MQE_FRAME + (k % 70);
   // the split-f16 operand has its own K order: compact frames of MQE_H2_FRAME columns (mqe_common.hpp): the twelve constant gait
   // parameters of a frame folded onto its presence-flag column, its last_two_locomotion_action onto the previous frame's
