@@ -38,7 +38,8 @@ extern "C" {
  * mqe_actor_params and mqe_rollout (new exports), mqe_actor_shape, MQE_ACTOR_*, MQE_ROLLOUT_*; mqe_rollout_time_outs and mqe_gae (new exports),
  * MQE_GAE_NORMALIZE; mqe_ppo_grad, mqe_ppo_optimizer and mqe_ppo_adam (new exports), mqe_ppo_loss, MQE_PPO_*; value normalisation: no export
  * and no prototype changes -- MQE_ACTOR_VALUE_NORM (a bit of mqe_actor_shape.activation above the kind byte), MQE_VALUE_NORM_STATE,
- * MQE_GAE_VALUE_NORM, MQE_PPO_VALUE_NORM and MQE_PPO_VALUE_NORM_UPDATE (flag bits that were refused as unknown before). */
+ * MQE_GAE_VALUE_NORM, MQE_PPO_VALUE_NORM and MQE_PPO_VALUE_NORM_UPDATE (flag bits that were refused as unknown before); layer normalisation:
+ * likewise -- MQE_ACTOR_LAYER_NORM and MQE_ACTOR_FEATURE_NORM (bits 2 and 4 of the kind byte of mqe_actor_shape.activation, refused before). */
 #define MQE_ABI_VERSION 17
 #define MQE_MAX_SPHERES 64    /* feature points of one robot (the capsule model has 32, the exact one 60) */
 #define MQE_MAX_PRIMS 20      /* collision primitives of one robot (Go1: 18) */
@@ -448,7 +449,7 @@ typedef struct {
   int32_t actor_dims[MQE_ACTOR_MAX_LAYERS + 1];   /* obs_dim, hidden ..., 3 */
   int32_t critic_layers;                          /* 0 = no critic */
   int32_t critic_dims[MQE_ACTOR_MAX_LAYERS + 1];  /* obs_dim, hidden ..., 1 */
-  int32_t activation;                             /* MQE_ACTOR_TANH / MQE_ACTOR_RELU on every hidden layer of both networks */
+  int32_t activation;                             /* MQE_ACTOR_TANH / MQE_ACTOR_RELU on every hidden layer of both networks (+ the bits of the value- and layer-normalisation sections) */
   float action_gain;                              /* 1 for the task wrappers, 0.5 for the OpenRL adapter (which feeds 0.5 * a) */
 } mqe_actor_shape;
 /* Allocates the engine-owned parameter buffer (zeroed) and the action staging buffer; a second call replaces the first.  Refused with
@@ -589,6 +590,31 @@ int mqe_ppo_adam(mqe_sim* s, const float* grad_dev, long long step, float lr, fl
  * The scratch is allocated by the first flagged call and grown when T grows; such a call synchronises once, as the other first calls do, and the
  * scratch is released with the actor.  Refused (-6, naming flags; nothing enqueued or written, state untouched): a flag on a handle without an
  * actor created with MQE_ACTOR_VALUE_NORM.  Bits 2 and 4 of both flag words stay unknown. */
+
+/* ---- Layer normalisation in the actor-critic, forward and backward (csrc/kernels_ln.hpp: k_actor_ln, k_ln_grad) ------------------------------
+ * v17, additive: no prototype, no struct and no #define of this header changes.  OpenRL's PPONet keeps MAPPO's MLP base: a LayerNorm on the
+ * observation and one behind every hidden activation.  The operator is torch.nn.LayerNorm(n, eps = 1e-5, elementwise_affine = True) over the n
+ * features of one row: u = gamma * xhat + beta, xhat = (a - mean(a)) / sqrt(mean((a - mean(a))^2) + eps) (biased variance), all f32, two-pass
+ * and centred; the summation order is stated in csrc/kernels_ln.hpp and restated on the host by tests/layer_norm_ref.py.
+ * THE TWO CONSTANTS BELOW ARE NOT #DEFINED BY THIS HEADER (tests/test_rollout.py pins the exact set of MQE_ACTOR_* defines).  Their values are
+ * stated here, defined under these names in csrc/kernels_ln.hpp (which the engine compiles) and mirrored in mqe/engine/abi.py;
+ * tests/test_layer_norm.py holds the three statements together.  A C caller passes the numbers.
+ *   MQE_ACTOR_LAYER_NORM = 2   MQE_ACTOR_FEATURE_NORM = 4
+ * Both are bits of the KIND BYTE of mqe_actor_shape.activation, or-ed with MQE_ACTOR_TANH / MQE_ACTOR_RELU (and with MQE_ACTOR_VALUE_NORM above
+ * the byte or not); every other bit of the byte is refused as before (-6), and so is bit 512.  They apply to both networks of the handle:
+ * MQE_ACTOR_LAYER_NORM    the hidden norm: a LayerNorm behind the activation of EVERY hidden layer (a = tanh / relu (W x + b), the next layer
+ *   reads u); never behind the output layer; a network of one Linear layer has none.
+ * MQE_ACTOR_FEATURE_NORM  the feature norm: a LayerNorm on the D observation floats in front of layer 0; each network has its own gamma, beta.
+ * Parameter buffer, per network and in this order: [norm_in.weight (D), norm_in.bias (D)] with the feature norm; per layer l weight, bias, and
+ *   for a hidden layer under the hidden norm [norm.weight (n), norm.bias (n)]; then the critic likewise, log_std[3] and the value-normalisation
+ *   state as before.  With both bits clear the layout is the plain one, bit for bit.  mqe_actor_create sets every gamma to 1 (the buffer is
+ *   otherwise zeroed).  n_params, grad_dev, the Adam moments and the gradient clip cover gamma and beta like any weight or bias.
+ * mqe_rollout, mqe_gae, mqe_ppo_grad, mqe_ppo_optimizer and mqe_ppo_adam are called as before.  A handle created with either bit launches
+ * k_actor_ln and k_ln_grad instead of k_actor and k_ppo_grad; a handle created without them launches what it always did.  The gradient of a
+ * normalised layer (du = the gradient with respect to u):  dgamma = sum over the samples of du * xhat;  dbeta = sum of du;
+ *   dxhat = du * gamma;  da = rstd * (dxhat - mean(dxhat) - xhat * mean(dxhat * xhat));  then the activation's derivative.
+ * No atomics: the same bits on every run.  Every shape mqe_actor_create accepts without the bits it accepts with them (D up to 128 included);
+ * k_ln_grad's LDS rule (csrc/kernels_ln.hpp) takes 32-row tiles earlier than k_ppo_grad's. */
 
 /* The onboard forward depth camera of LeggedRobotField (legged_robot_field.py:23-93: create_camera_sensor + attach_camera_to_body on the
  * base link, :196-223: get_camera_image_gpu_tensor(IMAGE_DEPTH)) for every robot, from the CURRENT state: out_dev [R][height][width]

@@ -150,6 +150,34 @@ __device__ __forceinline__ void actor_net(const ActorNet& net, const float* __re
   }
 }
 
+// wavefront 0, behind the networks: the draw, the log-probability and every global store of the kernel (behind the last weight load)
+__device__ __forceinline__ void actor_finish(const ActorArgs& a, const float* out, bool sample, bool critic, int row0, int lane) {
+  const int row = row0 + lane;
+  float ls[3], act[3], lp = 0.0f;
+  if (sample) {
+    const int e = row / a.Aw, ag = row - e * a.Aw;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      ls[j] = a.params[a.log_std_off + j];
+      const float z = a.deterministic ? 0.0f : mqe_randn_key(a.seed, a.genv0 + (uint32_t)e, a.count, (uint32_t)(ag * 3 + j));
+      act[j] = fmaf(expf(ls[j]), z, out[j * ACT_LD + lane]);
+      lp += -0.5f * z * z - ls[j];
+    }
+    lp -= 3.0f * 0.9189385332046727f;       // 3 x 0.5 ln(2 pi)
+  }
+  const float v = critic ? out[3 * ACT_LD + lane] : 0.0f;
+  if (row >= a.rows) return;
+  if (sample) {
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      a.actions[(size_t)row * 3 + j] = act[j];
+      a.stage[(size_t)row * 3 + j] = a.gain * act[j];
+    }
+    if (a.logp) a.logp[row] = lp;
+  }
+  if (critic) a.value[row] = v;
+}
+
 __global__ void __launch_bounds__(ACT_THREADS) k_actor(ActorArgs a) {
   extern __shared__ __attribute__((aligned(16))) float act_lds[];
   float* bufA = act_lds;
@@ -171,29 +199,5 @@ __global__ void __launch_bounds__(ACT_THREADS) k_actor(ActorArgs a) {
     actor_net(a.critic, a.params, bufA, bufB, out + 3 * ACT_LD, lane, wave, hidden_act);
   }
   if (wave != 0) return;
-  const int row = row0 + lane;
-  float ls[3], act[3], lp = 0.0f;
-  if (sample) {
-    const int e = row / a.Aw, ag = row - e * a.Aw;
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      ls[j] = a.params[a.log_std_off + j];
-      const float z = a.deterministic ? 0.0f : mqe_randn_key(a.seed, a.genv0 + (uint32_t)e, a.count, (uint32_t)(ag * 3 + j));
-      act[j] = fmaf(expf(ls[j]), z, out[j * ACT_LD + lane]);
-      lp += -0.5f * z * z - ls[j];
-    }
-    lp -= 3.0f * 0.9189385332046727f;       // 3 x 0.5 ln(2 pi)
-  }
-  const float v = critic ? out[3 * ACT_LD + lane] : 0.0f;
-  // every global store of the kernel: behind the last weight load
-  if (row >= a.rows) return;
-  if (sample) {
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      a.actions[(size_t)row * 3 + j] = act[j];
-      a.stage[(size_t)row * 3 + j] = a.gain * act[j];
-    }
-    if (a.logp) a.logp[row] = lp;
-  }
-  if (critic) a.value[row] = v;
+  actor_finish(a, out, sample, critic, row0, lane);
 }

@@ -75,8 +75,9 @@ static inline int ppo_lds_rows(const ActorNet& a, const ActorNet& c, int D) {
 }
 static inline size_t ppo_lds_bytes(int rows, int rt) { return ((size_t)rows * (rt + 1) + 2 + 2 * 64) * sizeof(float); }      // + the tile's sample indices (64-bit)
 
-// backward-data of one layer, in place: y (the stored output of the layer below, [K][LD]) becomes its delta
-template <int LD>
+// backward-data of one layer, in place: y (the stored output of the layer below, [K][LD]) becomes its delta.  RAW (kernels_ln.hpp): W^T delta alone
+// into y, no activation derivative -- what a layer norm between the two layers receives
+template <int LD, bool RAW = false>
 __device__ __forceinline__ void ppo_dx(const float* __restrict__ W, int K, int Nout, const float* dY, float* y, int row, int wave, int relu) {
   for (int k0 = wave * ACT_NB; k0 < K; k0 += ACT_WAVES * ACT_NB) {
     int kk[ACT_NB];
@@ -108,6 +109,7 @@ __device__ __forceinline__ void ppo_dx(const float* __restrict__ W, int K, int N
 #pragma unroll
     for (int j = 0; j < ACT_NB; j++) {
       if (k0 + j < K) {
+        if (RAW) { y[(k0 + j) * LD + row] = acc[j]; continue; }
         const float yv = y[(k0 + j) * LD + row];
         y[(k0 + j) * LD + row] = relu ? (yv > 0.0f ? acc[j] : 0.0f) : acc[j] * fmaf(-yv, yv, 1.0f);
       }
@@ -203,6 +205,99 @@ __device__ __forceinline__ void ppo_backward(const ActorNet& net, const float* _
 }
 
 struct PpoLoss { float clip, value_coef, entropy_coef, value_clip, inv_m; int clip_value; };
+struct PpoSums { double Lpi = 0.0, Lv = 0.0, Kl = 0.0, Clip = 0.0, gls[3] = {0.0, 0.0, 0.0}; };      // f64 per lane of wavefront 0 over the workgroup's tiles
+
+// the samples of tile `tile` (past the end of the minibatch the last one again) and their observations -> LDS [k][row]
+template <int LD, int RT>
+__device__ __forceinline__ void ppo_load_tile(float* lds, long long* srow, const float* __restrict__ packed, long long stride, int rows, long long n_total,
+                                              const int32_t* __restrict__ index, long long first, long long count, long long tile, int D, int tid) {
+  if (tid < RT) {
+    long long i = tile * RT + tid;
+    if (i > count - 1) i = count - 1;
+    long long s = first + i;
+    if (index != nullptr) {
+      s = index[first + i];
+      s = s < 0 ? 0 : (s > n_total - 1 ? n_total - 1 : s);
+    }
+    srow[tid] = s;
+  }
+  __syncthreads();
+  for (int e = tid; e < RT * D; e += ACT_THREADS) {
+    const int r = e / D, k = e - r * D;
+    const long long s = srow[r];
+    const long long t = s / rows, rr = s - t * rows;
+    lds[k * LD + r] = packed[(size_t)t * (size_t)stride + (size_t)rr * D + k];
+  }
+  __syncthreads();
+}
+
+// wavefront 0, behind the actor's forward: out[0 .. 2] (the mean) becomes the delta of the last layer; the policy statistics
+template <int LD, int RT>
+__device__ __forceinline__ void ppo_actor_head(const float* __restrict__ params, int log_std_off, float* out, const long long* srow, int row, int lane, bool valid,
+                                               const float* __restrict__ actions, const float* __restrict__ logp_old, const float* __restrict__ adv,
+                                               const PpoLoss& ls, PpoSums& S) {
+  const long long s = srow[row];
+  const float lpo = logp_old[s], ad = adv[s];
+  float z[3], inv[3], lp = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const float lsj = params[log_std_off + j];
+    inv[j] = expf(-lsj);
+    z[j] = (actions[(size_t)s * 3 + j] - out[j * LD + row]) * inv[j];
+    lp += -0.5f * z[j] * z[j] - lsj;
+  }
+  lp -= 3.0f * 0.9189385332046727f;       // 3 x 0.5 ln(2 pi)
+  const float ratio = expf(lp - lpo);
+  const float lo = 1.0f - ls.clip, hi = 1.0f + ls.clip;
+  const float Lpi = -fminf(ratio * ad, fminf(fmaxf(ratio, lo), hi) * ad);
+  const bool gate = (ad > 0.0f && ratio > hi) || (ad < 0.0f && ratio < lo);
+  const float dlp = gate ? 0.0f : -ad * ratio * ls.inv_m;
+  if (lane < RT) {
+#pragma unroll
+    for (int j = 0; j < 3; j++) out[j * LD + row] = valid ? dlp * z[j] * inv[j] : 0.0f;
+  }
+  if (valid) {
+    S.Lpi += (double)Lpi;
+    S.Kl += (double)(lpo - lp);
+    S.Clip += fabsf(ratio - 1.0f) > ls.clip ? 1.0 : 0.0;
+#pragma unroll
+    for (int j = 0; j < 3; j++) S.gls[j] += (double)(dlp * (z[j] * z[j] - 1.0f));
+  }
+}
+
+// wavefront 0, behind the critic's forward: out[3] (the value) becomes the delta of the last layer; the value statistic
+template <int LD, int RT>
+__device__ __forceinline__ void ppo_critic_head(float* out, const long long* srow, int row, int lane, bool valid, const float* __restrict__ value,
+                                                const float* __restrict__ ret, const PpoLoss& ls, PpoSums& S) {
+  const long long s = srow[row];
+  const float v = out[3 * LD + row], rt = ret[s];
+  const float d1 = v - rt, u = d1 * d1;
+  float Lv = u, dv = 2.0f * d1;
+  if (ls.clip_value) {
+    const float vo = value[s];
+    const float dvo = v - vo;
+    const float vc = vo + fminf(fmaxf(dvo, -ls.value_clip), ls.value_clip);
+    const float d2 = vc - rt, cl = d2 * d2;
+    Lv = fmaxf(u, cl);
+    dv = u >= cl ? 2.0f * d1 : (fabsf(dvo) < ls.value_clip ? 2.0f * d2 : 0.0f);
+  }
+  if (lane < RT) out[3 * LD + row] = valid ? ls.value_coef * ls.inv_m * dv : 0.0f;
+  if (valid) S.Lv += (double)Lv;
+}
+
+// wavefront 0, at the end: the seven sums across the lanes (xor butterfly 32, 16, ..., 1) -> the workgroup's statistics slot
+__device__ __forceinline__ void ppo_store_sums(const PpoSums& S, int lane, double* __restrict__ pst) {
+  double v[7] = {S.Lpi, S.Lv, S.Kl, S.Clip, S.gls[0], S.gls[1], S.gls[2]};
+#pragma unroll
+  for (int q = 0; q < 7; q++) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v[q] += __shfl_xor(v[q], m);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < 7; q++) pst[q] = v[q];
+  }
+}
 
 template <int RT>
 __global__ void __launch_bounds__(ACT_THREADS) k_ppo_grad(const float* __restrict__ params, const PpoNets* __restrict__ nets, int log_std_off, int n_params, int D, int rows_lds,
@@ -220,95 +315,25 @@ __global__ void __launch_bounds__(ACT_THREADS) k_ppo_grad(const float* __restric
   const int hidden_act = relu ? 2 : 1;
   float* part = part_all + (size_t)blockIdx.x * n_params;
   const long long tiles = (count + RT - 1) / RT;
-  double sLpi = 0.0, sLv = 0.0, sKl = 0.0, sClip = 0.0, gls[3] = {0.0, 0.0, 0.0};
+  PpoSums S;
   bool first_tile = true;
   for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    // the tile's samples: past the end of the minibatch the last one again
-    if (tid < RT) {
-      long long i = tile * RT + tid;
-      if (i > count - 1) i = count - 1;
-      long long s = first + i;
-      if (index != nullptr) {
-        s = index[first + i];
-        s = s < 0 ? 0 : (s > n_total - 1 ? n_total - 1 : s);
-      }
-      srow[tid] = s;
-    }
-    __syncthreads();
-    for (int e = tid; e < RT * D; e += ACT_THREADS) {
-      const int r = e / D, k = e - r * D;
-      const long long s = srow[r];
-      const long long t = s / rows, rr = s - t * rows;
-      ppo_lds[k * LD + r] = packed[(size_t)t * (size_t)stride + (size_t)rr * D + k];
-    }
-    __syncthreads();
+    ppo_load_tile<LD, RT>(ppo_lds, srow, packed, stride, rows, n_total, index, first, count, tile, D, tid);
     const bool valid = tile * RT + lane < count && lane < RT;
     // ---- actor ----
     ppo_forward<LD>(nets->actor, params, ppo_lds, D, out, row, wave, hidden_act);
-    if (wave == 0) {
-      const long long s = srow[row];
-      const float lpo = logp_old[s], ad = adv[s];
-      float z[3], inv[3], lp = 0.0f;
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const float lsj = params[log_std_off + j];
-        inv[j] = expf(-lsj);
-        z[j] = (actions[(size_t)s * 3 + j] - out[j * LD + row]) * inv[j];
-        lp += -0.5f * z[j] * z[j] - lsj;
-      }
-      lp -= 3.0f * 0.9189385332046727f;       // 3 x 0.5 ln(2 pi)
-      const float ratio = expf(lp - lpo);
-      const float lo = 1.0f - ls.clip, hi = 1.0f + ls.clip;
-      const float Lpi = -fminf(ratio * ad, fminf(fmaxf(ratio, lo), hi) * ad);
-      const bool gate = (ad > 0.0f && ratio > hi) || (ad < 0.0f && ratio < lo);
-      const float dlp = gate ? 0.0f : -ad * ratio * ls.inv_m;
-      if (lane < RT) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) out[j * LD + row] = valid ? dlp * z[j] * inv[j] : 0.0f;
-      }
-      if (valid) {
-        sLpi += (double)Lpi;
-        sKl += (double)(lpo - lp);
-        sClip += fabsf(ratio - 1.0f) > ls.clip ? 1.0 : 0.0;
-#pragma unroll
-        for (int j = 0; j < 3; j++) gls[j] += (double)(dlp * (z[j] * z[j] - 1.0f));
-      }
-    }
+    if (wave == 0) ppo_actor_head<LD, RT>(params, log_std_off, out, srow, row, lane, valid, actions, logp_old, adv, ls, S);
     __syncthreads();
     ppo_backward<LD, RT>(nets->actor, params, part, ppo_lds, D, out, row, wave, tid, relu, first_tile);
     // ---- critic: the observation is still in place ----
     ppo_forward<LD>(nets->critic, params, ppo_lds, D, out + 3 * LD, row, wave, hidden_act);
-    if (wave == 0) {
-      const long long s = srow[row];
-      const float v = out[3 * LD + row], rt = ret[s];
-      const float d1 = v - rt, u = d1 * d1;
-      float Lv = u, dv = 2.0f * d1;
-      if (ls.clip_value) {
-        const float vo = value[s];
-        const float dvo = v - vo;
-        const float vc = vo + fminf(fmaxf(dvo, -ls.value_clip), ls.value_clip);
-        const float d2 = vc - rt, cl = d2 * d2;
-        Lv = fmaxf(u, cl);
-        dv = u >= cl ? 2.0f * d1 : (fabsf(dvo) < ls.value_clip ? 2.0f * d2 : 0.0f);
-      }
-      if (lane < RT) out[3 * LD + row] = valid ? ls.value_coef * ls.inv_m * dv : 0.0f;
-      if (valid) sLv += (double)Lv;
-    }
+    if (wave == 0) ppo_critic_head<LD, RT>(out, srow, row, lane, valid, value, ret, ls, S);
     __syncthreads();
     ppo_backward<LD, RT>(nets->critic, params, part, ppo_lds, D, out + 3 * LD, row, wave, tid, relu, first_tile);
     first_tile = false;
   }
   if (wave != 0) return;
-  double v[7] = {sLpi, sLv, sKl, sClip, gls[0], gls[1], gls[2]};
-#pragma unroll
-  for (int q = 0; q < 7; q++) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v[q] += __shfl_xor(v[q], m);
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < 7; q++) pst[(size_t)blockIdx.x * PPO_PST + q] = v[q];
-  }
+  ppo_store_sums(S, lane, pst + (size_t)blockIdx.x * PPO_PST);
 }
 
 // grad and the statistics from the G workgroups' partials, in workgroup order

@@ -23,6 +23,7 @@
 #include "kernels_gae.hpp"
 #include "kernels_ppo.hpp"
 #include "kernels_vn.hpp"
+#include "kernels_ln.hpp"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, const char* a = "", const char* b = "", const char* c = "") {      // fmt: up to three %s
@@ -127,6 +128,8 @@ struct mqe_sim {
     int log_std_off = 0, n_params = 0, ldh = 0, relu = 0;
     float gain = 1.0f;
     bool vnorm = false;           // MQE_ACTOR_VALUE_NORM: MQE_VALUE_NORM_STATE floats behind the n_params trainable ones
+    bool ln_hidden = false, ln_feat = false;      // MQE_ACTOR_LAYER_NORM / MQE_ACTOR_FEATURE_NORM: either one selects k_actor_ln and k_ln_grad (kernels_ln.hpp)
+    float inv_actor[MQE_ACTOR_MAX_LAYERS] = {}, inv_critic[MQE_ACTOR_MAX_LAYERS] = {};      // (float)(1.0 / dims[l]): the norms' 1 / n
     float* params = nullptr;      // [n_params (+ MQE_VALUE_NORM_STATE)]
     float* stage = nullptr;       // [N, A', 3]
   } act;
@@ -148,8 +151,8 @@ struct mqe_sim {
   struct Ppo {
     float* part = nullptr;
     double* pst = nullptr;
-    int32_t* nets = nullptr;      // the two ActorNet shapes as k_ppo_grad reads them
-    int rt = 0, lds_rows = 0;
+    int32_t* nets = nullptr;      // the two ActorNet shapes as k_ppo_grad reads them (PpoNets; LnNets for k_ln_grad)
+    int rt = 0, lds_rows = 0, uw = 0;      // uw: rows of k_ln_grad's shared buffer of normalised inputs
     float* moments = nullptr;
     double* norm = nullptr;
   } ppo;
@@ -1552,7 +1555,8 @@ static void view_1d_f32(mqe_tensor_view* v, float* p, int n) {
 
 // ---- on-device rollouts: mqe_actor_create / mqe_actor_params / mqe_rollout (include/mqe_hip.h) ---------------------------------
 // one network's dims[] against the limits; fills its offsets into the flat parameter buffer from *off on
-static int actor_net_shape(const char* who, int layers, const int32_t* dims, int in, int out, ActorNet* net, int* off, int* ldh) {
+static int actor_net_shape(const char* who, int layers, const int32_t* dims, int in, int out, bool ln_hidden, bool ln_feat, ActorNet* net, float* inv_n,
+                           int* off, int* ldh) {
   if (layers < 1 || layers > MQE_ACTOR_MAX_LAYERS) return fail(-6, "mqe_actor_create: %s: 1 .. 4 Linear layers (MQE_ACTOR_MAX_LAYERS)", who);
   if (dims[0] != in) return fail(-6, "mqe_actor_create: %s: dims[0] must be obs_dim", who);
   if (dims[layers] != out) return fail(-6, "mqe_actor_create: %s: the last width must be 3 for the actor (the mean) and 1 for the critic", who);
@@ -1562,9 +1566,12 @@ static int actor_net_shape(const char* who, int layers, const int32_t* dims, int
     net->dims[l] = dims[l];
     if (l < layers && dims[l] > *ldh) *ldh = dims[l];
   }
+  if (ln_feat) *off += 2 * dims[0];                       // norm_in.weight, norm_in.bias
   for (int l = 0; l < layers; l++) {
     net->w_off[l] = *off;
     *off += dims[l] * dims[l + 1] + dims[l + 1];
+    if (ln_hidden && l + 1 < layers) *off += 2 * dims[l + 1];      // norm.weight, norm.bias behind a hidden layer
+    inv_n[l] = (float)(1.0 / (double)dims[l]);
   }
   return 0;
 }
@@ -1600,21 +1607,25 @@ extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
   if (sh->obs_dim != s->D) return fail(-6, "mqe_actor_create: obs_dim differs from the width of this scene's MQE_T_WRAPPER_OBS");
   if (sh->obs_dim > MQE_ACTOR_MAX_OBS) return fail(-6, "mqe_actor_create: obs_dim above MQE_ACTOR_MAX_OBS (128)");
   if (sh->act_dim != 3) return fail(-6, "mqe_actor_create: act_dim must be 3");
-  const int kind = sh->activation & ~MQE_ACTOR_VALUE_NORM;
   const bool vnorm = (sh->activation & MQE_ACTOR_VALUE_NORM) != 0;
-  if (kind != MQE_ACTOR_TANH && kind != MQE_ACTOR_RELU) return fail(-6, "mqe_actor_create: activation must be MQE_ACTOR_TANH or MQE_ACTOR_RELU (or-ed with MQE_ACTOR_VALUE_NORM or not)");
+  const bool ln_hidden = (sh->activation & MQE_ACTOR_LAYER_NORM) != 0, ln_feat = (sh->activation & MQE_ACTOR_FEATURE_NORM) != 0;
+  const int kind = sh->activation & ~(MQE_ACTOR_VALUE_NORM | MQE_ACTOR_LAYER_NORM | MQE_ACTOR_FEATURE_NORM);
+  if (kind != MQE_ACTOR_TANH && kind != MQE_ACTOR_RELU)
+    return fail(-6, "mqe_actor_create: activation must be MQE_ACTOR_TANH or MQE_ACTOR_RELU (or-ed with MQE_ACTOR_LAYER_NORM, MQE_ACTOR_FEATURE_NORM, MQE_ACTOR_VALUE_NORM or not)");
   if (vnorm && sh->critic_layers == 0) return fail(-6, "mqe_actor_create: activation: MQE_ACTOR_VALUE_NORM needs a critic (the statistics are those of its targets)");
   if (not_finite(&sh->action_gain) || std::fabs(sh->action_gain) >= 1e30f) return fail(-6, "mqe_actor_create: action_gain is not finite");
   mqe_sim::Actor a;
   int off = 0, ldh = 0;
   memset(&a.actor, 0, sizeof a.actor); memset(&a.critic, 0, sizeof a.critic);
-  if (int rc = actor_net_shape("actor", sh->actor_layers, sh->actor_dims, sh->obs_dim, 3, &a.actor, &off, &ldh)) return rc;
+  if (int rc = actor_net_shape("actor", sh->actor_layers, sh->actor_dims, sh->obs_dim, 3, ln_hidden, ln_feat, &a.actor, a.inv_actor, &off, &ldh)) return rc;
   if (sh->critic_layers != 0)
-    if (int rc = actor_net_shape("critic", sh->critic_layers, sh->critic_dims, sh->obs_dim, 1, &a.critic, &off, &ldh)) return rc;
+    if (int rc = actor_net_shape("critic", sh->critic_layers, sh->critic_dims, sh->obs_dim, 1, ln_hidden, ln_feat, &a.critic, a.inv_critic, &off, &ldh)) return rc;
   a.log_std_off = off; a.n_params = off + 3; a.ldh = ldh; a.relu = kind == MQE_ACTOR_RELU; a.gain = sh->action_gain; a.vnorm = vnorm;
-  const size_t lds = actor_lds_bytes(ldh);
-  if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)k_actor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(-5, "mqe_actor_create: cannot reserve LDS for k_actor");
+  a.ln_hidden = ln_hidden; a.ln_feat = ln_feat;
+  const bool ln = ln_hidden || ln_feat;
+  const size_t lds = ln ? actor_ln_lds_bytes(ldh) : actor_lds_bytes(ldh);
+  if (lds > 48 * 1024 && hipFuncSetAttribute(ln ? (const void*)k_actor_ln : (const void*)k_actor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(-5, ln ? "mqe_actor_create: cannot reserve LDS for k_actor_ln" : "mqe_actor_create: cannot reserve LDS for k_actor");
   actor_release(s);
   if (dalloc(s, &a.params, (size_t)a.n_params + (vnorm ? MQE_VALUE_NORM_STATE : 0)) || dalloc(s, &a.stage, (size_t)s->N * s->Aw * 3)) {
     dfree(s, a.params);
@@ -1626,6 +1637,18 @@ extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
     if (hipMemcpy(a.params + a.n_params, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess) {
       dfree(s, a.params); dfree(s, a.stage);
       return fail(-5, "mqe_actor_create: cannot write the value-normalisation state");
+    }
+  }
+  if (ln) {                            // every gamma starts at 1 (torch.nn.LayerNorm's own start); the rest of the buffer stays zero
+    std::vector<float> ones(MQE_ACTOR_MAX_HIDDEN > MQE_ACTOR_MAX_OBS ? MQE_ACTOR_MAX_HIDDEN : MQE_ACTOR_MAX_OBS, 1.0f);
+    bool ok = true;
+    for (const ActorNet* net : {&a.actor, &a.critic})
+      for (int l = 0; l < net->n_layers; l++)
+        if (l == 0 ? ln_feat : ln_hidden)
+          ok = ok && hipMemcpy(a.params + ln_gamma_off(*net, l), ones.data(), (size_t)net->dims[l] * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+      dfree(s, a.params); dfree(s, a.stage);
+      return fail(-5, "mqe_actor_create: cannot write the layer norms' weights");
     }
   }
   a.on = true;
@@ -1646,7 +1669,15 @@ static void launch_actor(mqe_sim* s, const float* obs, float* actions, float* lo
   k.actor = a.actor; k.critic = a.critic; k.log_std_off = a.log_std_off;
   k.rows = s->N * s->Aw; k.D = s->D; k.Aw = s->Aw; k.ldh = a.ldh; k.relu = a.relu; k.deterministic = (flags & MQE_ROLLOUT_DETERMINISTIC) ? 1 : 0;
   k.gain = a.gain; k.seed = (uint32_t)s->d.seed; k.genv0 = (uint32_t)s->d.env_id_offset; k.count = MQE_RNG_ACTOR + (uint32_t)s->n_post_steps;
-  hipLaunchKernelGGL(k_actor, dim3((k.rows + ACT_ROWS - 1) / ACT_ROWS), dim3(ACT_THREADS), actor_lds_bytes(a.ldh), q, k);
+  const dim3 grid((k.rows + ACT_ROWS - 1) / ACT_ROWS);
+  if (!a.ln_hidden && !a.ln_feat) {
+    hipLaunchKernelGGL(k_actor, grid, dim3(ACT_THREADS), actor_lds_bytes(a.ldh), q, k);
+    return;
+  }
+  ActorLnArgs kl;
+  kl.a = k; kl.hidden = a.ln_hidden; kl.feat = a.ln_feat;
+  memcpy(kl.inv_actor, a.inv_actor, sizeof kl.inv_actor); memcpy(kl.inv_critic, a.inv_critic, sizeof kl.inv_critic);
+  hipLaunchKernelGGL(k_actor_ln, grid, dim3(ACT_THREADS), actor_ln_lds_bytes(a.ldh), q, kl);
 }
 extern "C" int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* packed_dev, long long row_stride, float* actions_dev, float* logp_dev,
                            float* value_dev, int flags, void* stream) {
@@ -1773,17 +1804,37 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
                                                {vn_state, MQE_VALUE_NORM_STATE * 4, "the value-normalisation state"}}, 2)) return rc;
   if (vn && (vn_scratch(s, &s->vn.tgt, &s->vn.tgt_cap, n) || (!s->vn.part && dalloc(s, &s->vn.part, (size_t)VN_PART))))
     return fail(-5, "device alloc failed (mqe_ppo_grad value-normalisation scratch)");
+  const bool ln = a.ln_hidden || a.ln_feat;
   if (!s->ppo.part) {                  // once per actor: the row tile of its shapes, the scratch (hipMalloc synchronises)
     mqe_sim::Ppo& p = s->ppo;
-    p.lds_rows = ppo_lds_rows(a.actor, a.critic, s->D);
+    p.lds_rows = ln ? ln_lds_rows(a.actor, a.critic, s->D, a.ln_hidden, a.ln_feat) : ppo_lds_rows(a.actor, a.critic, s->D);
+    p.uw = ln ? p.lds_rows - ppo_lds_rows(a.actor, a.critic, s->D) - LN_STAT - LN_PART : 0;
     p.rt = ppo_lds_bytes(p.lds_rows, 64) <= PPO_LDS_LIMIT ? 64 : 32;
     const int lds = (int)ppo_lds_bytes(p.lds_rows, p.rt);
-    if (lds > PPO_LDS_LIMIT) return fail(-5, "mqe_ppo_grad: the layer outputs of one network do not fit the LDS even at 32 rows");
-    const hipError_t e = hipFuncSetAttribute((const void*)(p.rt == 64 ? k_ppo_grad<64> : k_ppo_grad<32>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (lds > 48 * 1024 && e != hipSuccess) return fail(-5, "mqe_ppo_grad: cannot reserve LDS for k_ppo_grad");
-    PpoNets nets; nets.actor = a.actor; nets.critic = a.critic;
-    if (dalloc(s, &p.pst, (size_t)PPO_MAX_WG * PPO_PST) || dalloc(s, &p.nets, sizeof nets / 4) ||
-        hipMemcpy(p.nets, &nets, sizeof nets, hipMemcpyHostToDevice) != hipSuccess || dalloc(s, &p.part, (size_t)PPO_MAX_WG * a.n_params, 0)) {
+    // the shapes as the selected kernel reads them: LnNets (with the norms' 1 / n and the two switches) for k_ln_grad, PpoNets for k_ppo_grad
+    LnNets with_norms;
+    PpoNets plain;
+    const void* kern;
+    const void* image;
+    size_t image_bytes;
+    if (ln) {
+      if (lds > PPO_LDS_LIMIT)
+        return fail(-5, "mqe_ppo_grad: the layer outputs of one network, the widest norm's input and k_ln_grad's statistics do not fit the LDS even at 32 rows");
+      kern = p.rt == 64 ? (const void*)k_ln_grad<64> : (const void*)k_ln_grad<32>;
+      memset(&with_norms, 0, sizeof with_norms);
+      with_norms.actor.net = a.actor; with_norms.critic.net = a.critic; with_norms.hidden = a.ln_hidden; with_norms.feat = a.ln_feat;
+      memcpy(with_norms.actor.inv_n, a.inv_actor, sizeof a.inv_actor); memcpy(with_norms.critic.inv_n, a.inv_critic, sizeof a.inv_critic);
+      image = &with_norms; image_bytes = sizeof with_norms;
+    } else {
+      if (lds > PPO_LDS_LIMIT) return fail(-5, "mqe_ppo_grad: the layer outputs of one network do not fit the LDS even at 32 rows");
+      kern = p.rt == 64 ? (const void*)k_ppo_grad<64> : (const void*)k_ppo_grad<32>;
+      plain.actor = a.actor; plain.critic = a.critic;
+      image = &plain; image_bytes = sizeof plain;
+    }
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (lds > 48 * 1024 && e != hipSuccess) return fail(-5, ln ? "mqe_ppo_grad: cannot reserve LDS for k_ln_grad" : "mqe_ppo_grad: cannot reserve LDS for k_ppo_grad");
+    if (dalloc(s, &p.pst, (size_t)PPO_MAX_WG * PPO_PST) || dalloc(s, &p.nets, image_bytes / 4) ||
+        hipMemcpy(p.nets, image, image_bytes, hipMemcpyHostToDevice) != hipSuccess || dalloc(s, &p.part, (size_t)PPO_MAX_WG * a.n_params, 0)) {
       p.part = nullptr;                // the next call tries again; what was allocated is released with the handle
       return fail(-5, "device alloc failed (mqe_ppo_grad scratch)");
     }
@@ -1792,7 +1843,6 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   const int rt = s->ppo.rt;
   const long long tiles = (count + rt - 1) / rt;
   const int G = (int)(tiles < PPO_MAX_WG ? tiles : PPO_MAX_WG);
-  const PpoNets* nets = reinterpret_cast<const PpoNets*>(s->ppo.nets);
   PpoLoss ls;
   ls.clip = loss->clip_ratio; ls.value_coef = loss->value_coef; ls.entropy_coef = loss->entropy_coef; ls.value_clip = loss->value_clip;
   ls.inv_m = (float)(1.0 / (double)count); ls.clip_value = (flags & MQE_PPO_CLIP_VALUE) ? 1 : 0;
@@ -1806,8 +1856,17 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
                        vn_update ? (const double*)s->vn.part : nullptr, gm, s->vn.tgt);
     ret_dev = s->vn.tgt;
   }
-  hipLaunchKernelGGL(rt == 64 ? k_ppo_grad<64> : k_ppo_grad<32>, dim3(G), dim3(ACT_THREADS), lds, q, (const float*)a.params, nets, a.log_std_off, a.n_params, s->D, s->ppo.lds_rows, a.relu,
-                     packed_dev, row_stride, (int)rows, (long long)n, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, index_dev, first, count, ls, s->ppo.part, s->ppo.pst);
+  if (!ln) {
+    hipLaunchKernelGGL(rt == 64 ? k_ppo_grad<64> : k_ppo_grad<32>, dim3(G), dim3(ACT_THREADS), lds, q, (const float*)a.params, reinterpret_cast<const PpoNets*>(s->ppo.nets), a.log_std_off, a.n_params, s->D,
+                       s->ppo.lds_rows, a.relu,
+                       packed_dev, row_stride, (int)rows, (long long)n, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, index_dev, first, count, ls, s->ppo.part, s->ppo.pst);
+  } else {
+    PpoTraj tr;
+    tr.packed = packed_dev; tr.stride = row_stride; tr.rows = (int)rows; tr.n_total = (long long)n; tr.actions = actions_dev; tr.logp_old = logp_dev;
+    tr.value = value_dev; tr.adv = adv_dev; tr.ret = ret_dev; tr.index = index_dev; tr.first = first; tr.count = count;
+    hipLaunchKernelGGL(rt == 64 ? k_ln_grad<64> : k_ln_grad<32>, dim3(G), dim3(ACT_THREADS), lds, q, (const float*)a.params, reinterpret_cast<const LnNets*>(s->ppo.nets),
+                       a.log_std_off, a.n_params, s->D, s->ppo.lds_rows, s->ppo.uw, a.relu, tr, ls, s->ppo.part, s->ppo.pst);
+  }
   hipLaunchKernelGGL(k_ppo_reduce, dim3((a.n_params + PPO_REDUCE_THREADS - 1) / PPO_REDUCE_THREADS), dim3(PPO_REDUCE_THREADS), 0, q, (const float*)s->ppo.part,
                      (const double*)s->ppo.pst, G, a.n_params, a.log_std_off, count, ls.value_coef, ls.entropy_coef, (const float*)a.params, grad_dev, stats_dev);
   return launched();

@@ -122,7 +122,10 @@ PPO_CLIP_VALUE, PPO_STATS = 1, 6      # mqe_ppo_grad: flags bit 0; floats of sta
 ACTOR_VALUE_NORM, VALUE_NORM_STATE = 256, 5
 GAE_VALUE_NORM = 8
 PPO_VALUE_NORM, PPO_VALUE_NORM_UPDATE = 8, 16
-RNG_ACTOR = 0x70000000           # csrc/mqe_common.hpp MQE_RNG_ACTOR: `count` of the actor's draws = RNG_ACTOR + post-physics steps so far
+# layer normalisation (include/mqe_hip.h states the values, csrc/kernels_ln.hpp defines them): two bits of the kind byte of
+# mqe_actor_shape.activation, or-ed with ACTOR_TANH / ACTOR_RELU -- a LayerNorm behind every hidden activation / on the observation
+ACTOR_LAYER_NORM, ACTOR_FEATURE_NORM = 2, 4
+RNG_ACTOR = 0x70000000          # csrc/mqe_common.hpp MQE_RNG_ACTOR: `count` of the actor's draws = RNG_ACTOR + post-physics steps so far
 
 
 class ActorShape(C.Structure):
@@ -135,27 +138,38 @@ class PpoLoss(C.Structure):
     _fields_ = [("clip_ratio", f32), ("value_coef", f32), ("entropy_coef", f32), ("value_clip", f32)]
 
 
-def actor_param_layout(actor_dims, critic_dims=None, value_norm=False):
+def actor_param_layout(actor_dims, critic_dims=None, value_norm=False, layer_norm=False, feature_norm=False):
     """The flat parameter buffer of mqe_actor_params as an ordered {name: (offset, shape)}: per layer W (out, in) row-major as
     torch.nn.Linear.weight, then b; the actor's layers, then the critic's, then log_std[3].  Names: actor.<layer>.weight / .bias,
     critic.<layer>.weight / .bias, log_std.  value_norm (an actor created with ACTOR_VALUE_NORM): + "value_norm", the VALUE_NORM_STATE
-    floats (m, q, d, mu, sigma) behind log_std -- state of the normaliser, not a trainable parameter."""
+    floats (m, q, d, mu, sigma) behind log_std -- state of the normaliser, not a trainable parameter.  feature_norm (ACTOR_FEATURE_NORM):
+    <who>.norm_in.weight / .bias (D each) in front of a network's layer 0; layer_norm (ACTOR_LAYER_NORM): <who>.<layer>.norm.weight / .bias
+    (n each) behind the bias of every hidden layer.  With both off the layout is the plain one."""
     out, off = {}, 0
     for who, dims in (("actor", actor_dims), ("critic", critic_dims or ())):
+        if feature_norm and len(dims) > 1:
+            d = int(dims[0])
+            out[f"{who}.norm_in.weight"] = (off, (d,))
+            out[f"{who}.norm_in.bias"] = (off + d, (d,))
+            off += 2 * d
         for l in range(len(dims) - 1):
             k, n = int(dims[l]), int(dims[l + 1])
             out[f"{who}.{l}.weight"] = (off, (n, k))
             out[f"{who}.{l}.bias"] = (off + n * k, (n,))
             off += n * k + n
+            if layer_norm and l + 2 < len(dims):
+                out[f"{who}.{l}.norm.weight"] = (off, (n,))
+                out[f"{who}.{l}.norm.bias"] = (off + n, (n,))
+                off += 2 * n
     out["log_std"] = (off, (3,))
     if value_norm:
         out["value_norm"] = (off + 3, (VALUE_NORM_STATE,))
     return out
 
 
-def actor_param_count(actor_dims, critic_dims=None, value_norm=False):
+def actor_param_count(actor_dims, critic_dims=None, value_norm=False, layer_norm=False, feature_norm=False):
     """floats of the buffer: the trainable parameters, + VALUE_NORM_STATE with value_norm"""
-    off, shape = list(actor_param_layout(actor_dims, critic_dims, value_norm).values())[-1]
+    off, shape = list(actor_param_layout(actor_dims, critic_dims, value_norm, layer_norm, feature_norm).values())[-1]
     return off + shape[0]
 
 

@@ -167,12 +167,15 @@ class HipEngine(EngineBase):
         self._call("set_return_buffer", C.c_void_p(packed.data_ptr() if packed is not None else None))
 
     # ---- on-device rollouts (mqe_actor_create / mqe_actor_params / mqe_rollout) -------------------------------------------------------
-    def create_actor(self, actor_dims, critic_dims=None, activation="tanh", action_gain=1.0, value_norm=False):
+    def create_actor(self, actor_dims, critic_dims=None, activation="tanh", action_gain=1.0, value_norm=False, layer_norm=False, feature_norm=False):
         """The engine's actor (and critic): MLPs on the task observation.  actor_dims = (D, hidden ..., 3), critic_dims = (D, hidden ..., 1)
         or None; activation "tanh" / "relu" on every hidden layer; the step receives action_gain * a.  Parameters start at zero: fill the
         views of actor_params().  A second call replaces the first.  value_norm (needs a critic): the engine keeps OpenRL's ValueNorm beside
         the parameters (abi.ACTOR_VALUE_NORM; csrc/kernels_vn.hpp states the arithmetic): the critic's outputs are in units of the running
-        (mu, sigma) of the returns, and gae / ppo_grad / ppo_update follow (their value_norm=None)."""
+        (mu, sigma) of the returns, and gae / ppo_grad / ppo_update follow (their value_norm=None).  layer_norm / feature_norm
+        (abi.ACTOR_LAYER_NORM / ACTOR_FEATURE_NORM; csrc/kernels_ln.hpp states the arithmetic): torch.nn.LayerNorm(n, eps=1e-5) behind every
+        hidden activation / on the observation in front of layer 0, in both networks; their weights start at 1, and rollout, gae, ppo_grad,
+        adam_step and ppo_update work unchanged on such an actor."""
         actor_dims = [int(x) for x in actor_dims]
         critic_dims = [int(x) for x in critic_dims] if critic_dims is not None else []
         for who, dims in (("actor", actor_dims), ("critic", critic_dims)):
@@ -187,11 +190,12 @@ class HipEngine(EngineBase):
             sh.actor_dims[i] = v
         for i, v in enumerate(critic_dims):
             sh.critic_dims[i] = v
-        sh.activation = (abi.ACTOR_RELU if activation == "relu" else abi.ACTOR_TANH) | (abi.ACTOR_VALUE_NORM if value_norm else 0)
+        sh.activation = ((abi.ACTOR_RELU if activation == "relu" else abi.ACTOR_TANH) | (abi.ACTOR_VALUE_NORM if value_norm else 0)
+                         | (abi.ACTOR_LAYER_NORM if layer_norm else 0) | (abi.ACTOR_FEATURE_NORM if feature_norm else 0))
         sh.action_gain = float(action_gain)
         self._invoke("actor_create", C.byref(sh))
         self._actor = dict(actor_dims=actor_dims, critic_dims=critic_dims or None, activation=activation, action_gain=float(action_gain),
-                           value_norm=bool(value_norm))
+                           value_norm=bool(value_norm), layer_norm=bool(layer_norm), feature_norm=bool(feature_norm))
         self._actor_views = None
         self.ppo_step = 0            # the library dropped Adam's moments with the old actor
 
@@ -206,7 +210,7 @@ class HipEngine(EngineBase):
             self._call("actor_params", C.byref(v))
             flat = self._wrap(v.ptr, [int(v.shape[0])], v.dtype)
             vn = self._actor["value_norm"]
-            layout = abi.actor_param_layout(self._actor["actor_dims"], self._actor["critic_dims"], vn)
+            layout = abi.actor_param_layout(self._actor["actor_dims"], self._actor["critic_dims"], vn, self._actor["layer_norm"], self._actor["feature_norm"])
             views = {n: flat[o:o + int(np.prod(shp))].view(shp) for n, (o, shp) in layout.items()}
             if vn:
                 views["all"] = flat

@@ -140,29 +140,45 @@ class FusedTaskWrapper(EmptyWrapper):
                                       f"{type(eng).__name__} has no on-device actor")
         return eng
 
-    def set_actor(self, actor_module, critic_module=None, log_std=None, action_gain=1.0, value_norm=False):
+    def set_actor(self, actor_module, critic_module=None, log_std=None, action_gain=1.0, value_norm=False, layer_norm=False):
         """The policy a following rollout() evaluates inside the engine: torch.nn.Sequential stacks of Linear / Tanh / ReLU -- actor
         (obs_dim -> ... -> 3, the mean), optional critic (obs_dim -> ... -> 1) with the same activation -- and log_std (3 values; a tensor
         or Parameter is read again by every sync_actor(); None: zeros).  Anything else raises ValueError naming the offending layer.
         Creates the engine's actor and copies the parameters (on the device when the modules live there).  value_norm (needs a critic):
         the engine keeps OpenRL's ValueNorm beside the parameters (HipEngine.create_actor) -- the critic predicts returns in units of
         their running mean and standard deviation; rollout(gamma=...) and ppo_update() follow it.  The statistics start at (mu, sigma) =
-        (0, 0.1) with every set_actor; sync_actor() and pull_actor() never touch them."""
+        (0, 0.1) with every set_actor; sync_actor() and pull_actor() never touch them.  layer_norm=True: the stacks may hold OpenRL's
+        torch.nn.LayerNorm(n, eps=1e-5) layers -- one on the observation in front of the first Linear (the feature norm), one behind every
+        hidden activation (the hidden norm), either, both or none, the same choice in actor and critic (mqe.utils.actor_net.mlp_spec names
+        what it refuses); sync_actor() and pull_actor() copy their weights and biases too.  Without it a LayerNorm is refused like any
+        other layer."""
         from mqe.utils.actor_net import mlp_spec
         D = self.observation_space.shape[0]
-        a_dims, a_act, a_lin = mlp_spec(actor_module, "actor", D, 3)
-        c_dims, c_act, c_lin = (None, None, [])
+        no_norms = {"feature": None, "hidden": []}
+        spec = lambda module, what, out: mlp_spec(module, what, D, out, layer_norm=True) if layer_norm else (*mlp_spec(module, what, D, out), no_norms)
+        a_dims, a_act, a_lin, a_norm = spec(actor_module, "actor", 3)
+        c_dims, c_act, c_lin, c_norm = (None, None, [], a_norm)
         if critic_module is not None:
-            c_dims, c_act, c_lin = mlp_spec(critic_module, "critic", D, 1)
+            c_dims, c_act, c_lin, c_norm = spec(critic_module, "critic", 1)
             if a_act is not None and c_act is not None and a_act != c_act:
                 raise ValueError(f"critic: mixed activations; the actor uses {a_act}, the critic {c_act}: the engine applies one kind to both networks")
+            if (a_norm["feature"] is None) != (c_norm["feature"] is None):
+                raise ValueError("critic: the feature norm (a LayerNorm in front of the first Linear) is in one network and not in the other: "
+                                 "the engine applies one choice to both")
+            if len(a_dims) > 2 and len(c_dims) > 2 and bool(a_norm["hidden"]) != bool(c_norm["hidden"]):
+                raise ValueError("critic: the hidden norm (a LayerNorm behind every hidden activation) is in one network and not in the other: "
+                                 "the engine applies one choice to both")
         if log_std is not None and int(torch.as_tensor(log_std).numel()) != 3:
             raise ValueError(f"log_std must hold 3 values (one per action column), got {tuple(torch.as_tensor(log_std).shape)}")
         if value_norm and critic_module is None:
             raise ValueError("set_actor(value_norm=True): value normalisation is that of a critic's targets, and no critic was given")
         eng = self._rollout_engine("set_actor")
-        eng.create_actor(a_dims, c_dims, activation=a_act or c_act or "tanh", action_gain=action_gain, value_norm=value_norm)
+        norm_kw = {}
+        if layer_norm:                     # an engine without the keywords is never asked for them
+            norm_kw = dict(layer_norm=bool(a_norm["hidden"] or c_norm["hidden"]), feature_norm=a_norm["feature"] is not None)
+        eng.create_actor(a_dims, c_dims, activation=a_act or c_act or "tanh", action_gain=action_gain, value_norm=value_norm, **norm_kw)
         self._actor_src = (a_lin, c_lin, log_std)
+        self._actor_norms = (a_norm, c_norm if critic_module is not None else no_norms)
         self.sync_actor()
 
     def sync_actor(self):
@@ -177,10 +193,21 @@ class FusedTaskWrapper(EmptyWrapper):
                 for l, layer in enumerate(lin):
                     views[f"{who}.{l}.weight"].copy_(layer.weight.detach(), non_blocking=True)
                     views[f"{who}.{l}.bias"].copy_(layer.bias.detach(), non_blocking=True)
+            for name, norm in self._norm_modules():
+                views[f"{name}.weight"].copy_(norm.weight.detach(), non_blocking=True)
+                views[f"{name}.bias"].copy_(norm.bias.detach(), non_blocking=True)
             if log_std is None:
                 views["log_std"].zero_()
             else:
                 views["log_std"].copy_(torch.as_tensor(log_std).detach().reshape(3).to(torch.float32), non_blocking=True)
+
+    def _norm_modules(self):
+        """(the engine's name, the torch.nn.LayerNorm) of every norm set_actor(layer_norm=True) found: <who>.norm_in, <who>.<layer>.norm"""
+        for who, norms in zip(("actor", "critic"), self._actor_norms):
+            if norms["feature"] is not None:
+                yield f"{who}.norm_in", norms["feature"]
+            for l, norm in enumerate(norms["hidden"]):
+                yield f"{who}.{l}.norm", norm
 
     def pull_actor(self):
         """the reverse of sync_actor(): the engine's parameter buffer -> the torch modules and log_std given to set_actor, device to device
@@ -196,6 +223,9 @@ class FusedTaskWrapper(EmptyWrapper):
                 for l, layer in enumerate(lin):
                     layer.weight.copy_(views[f"{who}.{l}.weight"], non_blocking=True)
                     layer.bias.copy_(views[f"{who}.{l}.bias"], non_blocking=True)
+            for name, norm in self._norm_modules():
+                norm.weight.copy_(views[f"{name}.weight"], non_blocking=True)
+                norm.bias.copy_(views[f"{name}.bias"], non_blocking=True)
             if isinstance(log_std, torch.Tensor):
                 log_std.copy_(views["log_std"].reshape(log_std.shape), non_blocking=True)
 

@@ -45,10 +45,12 @@ class mqe_openrl_wrapper(Wrapper):
         obs, reward, termination, info = self.env.step((0.5 * actions).clip(-1, 1))
         return obs, reward.unsqueeze(-1), termination.unsqueeze(-1).repeat(1, self.agent_num)
 
-    def set_actor(self, actor_module, critic_module=None, log_std=None, value_norm=False):
+    def set_actor(self, actor_module, critic_module=None, log_std=None, value_norm=False, layer_norm=False):
         """the policy rollout_torch evaluates inside the engine (FusedTaskWrapper.set_actor) with this adapter's transform: the step
-        receives 0.5 * a, clipped to +-1 inside the engine.  value_norm: OpenRL's use_valuenorm, kept by the engine"""
-        self.env.set_actor(actor_module, critic_module, log_std=log_std, action_gain=0.5, value_norm=value_norm)
+        receives 0.5 * a, clipped to +-1 inside the engine.  value_norm: OpenRL's use_valuenorm, kept by the engine.  layer_norm: the stacks
+        may hold the LayerNorm layers of OpenRL's MLP base (use_feature_normalization, and one behind every hidden activation)"""
+        kw = {"layer_norm": True} if layer_norm else {}
+        self.env.set_actor(actor_module, critic_module, log_std=log_std, action_gain=0.5, value_norm=value_norm, **kw)
 
     def rollout_torch(self, T, deterministic=False, gamma=None, lam=0.95, normalize_advantages=False):
         """T steps of step_torch with the engine's own actor in one call (mqe_rollout, action_gain = 0.5): the wrapper's Rollout -- obs
