@@ -1,4 +1,6 @@
-// kernels_actor.hpp -- k_actor: the Gaussian actor (and optional critic) of an on-device rollout (mqe_rollout, include/mqe_hip.h).
+// kernels_actor.hpp -- the primitives of the Gaussian actor (and optional critic) of an on-device rollout (mqe_rollout, include/mqe_hip.h): the
+// shapes and the argument struct, one layer (actor_layer) and its dispatch by alignment (actor_layer_of), the observation load and the draw
+// (actor_finish).  The network walk and the entry points k_actor / k_actor_ln are in kernels_actor_critic.hpp, behind the norm (kernels_ln.hpp).
 // One launch per rollout step, in front of the five launches of the fused step; rows are R' = N x A' (env-major, the rows of
 // MQE_T_WRAPPER_OBS).  Per row: the D task-observation floats -> actor MLP -> mean[3]; a = mean + exp(log_std) z with z from the
 // engine's counter RNG; logp of the unclipped sample; critic MLP -> value.
@@ -14,8 +16,7 @@
 // wavefront ever take different paths (all control flow depends on the layer shapes and the wave index only; rows past R' are clamped
 // on the load side and masked at the final stores).  The wavefronts split a layer's OUTPUT neurons in blocks of ACT_NB; activations
 // live in LDS as [k][row] with a row stride of 65 floats, so a wavefront's read of x[k] and its write of y[o] hit 64 different banks
-// and the coalesced observation load (consecutive lanes = consecutive k of one row) does too.  Two activation buffers ping-pong
-// (observation in B -> A -> B -> A); the critic re-reads the observation (4 kB per workgroup, L2-hot) instead of holding a third buffer.
+// and the coalesced observation load (consecutive lanes = consecutive k of one row) does too.
 // WEIGHTS.  With lane = row a weight is the same for the whole wavefront: it is an SGPR operand of the FMA, fetched by scalar loads
 // through the scalar data cache from L2 -- no LDS staging.  Every workgroup reads all <= 200 kB of them and they stay L2-resident (4 MB
 // per XCD); staging them through LDS would cost a vector load, an LDS write and an LDS broadcast read per weight for a value that is
@@ -42,6 +43,13 @@ struct ActorNet {
   int dims[MQE_ACTOR_MAX_LAYERS + 1];         // in, hidden ..., out
   int w_off[MQE_ACTOR_MAX_LAYERS];            // offset of W[l] in the parameter buffer, floats; b[l] follows W[l]
 };
+// the shapes as the kernels read them (k_actor / k_actor_ln inside ActorArgs, k_ppo_grad / k_ln_grad from device memory: wave-uniform loads at the
+// layer loops, words that need no registers).  The plain kernels read the two ActorNet only
+struct ActorShapes {
+  ActorNet actor, critic;
+  float inv_actor[MQE_ACTOR_MAX_LAYERS], inv_critic[MQE_ACTOR_MAX_LAYERS];      // (float)(1.0 / dims[l]): the width of layer l's INPUT, the norms' 1 / n
+  int hidden, feat;                                                             // MQE_ACTOR_LAYER_NORM / MQE_ACTOR_FEATURE_NORM (kernels_ln.hpp)
+};
 struct ActorArgs {
   const float* params;     // the flat parameter buffer (mqe_actor_params)
   const float* obs;        // [rows][D]
@@ -49,7 +57,7 @@ struct ActorArgs {
   float* logp;             // [rows] or null
   float* value;            // [rows] or null
   float* stage;            // [rows][3] action_gain * a: what the following mqe_step reads
-  ActorNet actor, critic;
+  ActorShapes sh;
   int log_std_off;
   int rows, D, Aw, ldh;    // ldh: widest activation vector (floats) = rows of one LDS buffer
   int relu, deterministic;
@@ -122,6 +130,18 @@ __device__ __forceinline__ void actor_layer(const float* __restrict__ W, const f
   }
 }
 
+// layer l of a network: its weights by their offsets, no activation behind the last layer, and the ONE alignment test that picks the 16-byte loads
+template <int LD>
+__device__ __forceinline__ void actor_layer_of(const ActorNet& net, int l, const float* __restrict__ params, const float* x, float* dst, int lane, int wave,
+                                               int hidden_act) {
+  const int K = net.dims[l], Nout = net.dims[l + 1];
+  const float* W = params + net.w_off[l];
+  const float* b = W + (size_t)K * Nout;
+  const bool last = l + 1 == net.n_layers;
+  if (((K | net.w_off[l]) & 3) == 0) actor_layer<true, LD>(W, b, K, Nout, x, dst, lane, wave, last ? 0 : hidden_act);
+  else actor_layer<false, LD>(W, b, K, Nout, x, dst, lane, wave, last ? 0 : hidden_act);
+}
+
 // the observation of the workgroup's 64 rows -> LDS [k][row]: coalesced (thread t reads float t of the 64 x D block), clamped at the end
 __device__ __forceinline__ void actor_load_obs(const float* __restrict__ obs, int row0, int rows, int D, float* x, int tid) {
   const size_t last = (size_t)rows * D - 1;
@@ -129,24 +149,6 @@ __device__ __forceinline__ void actor_load_obs(const float* __restrict__ obs, in
     const int r = e / D, k = e - r * D;
     const size_t g = (size_t)row0 * D + e;
     x[k * ACT_LD + r] = obs[g < last ? g : last];
-  }
-}
-
-// a whole network: observation in bufB; result (last layer, linear) -> out[j * ACT_LD + row]
-__device__ __forceinline__ void actor_net(const ActorNet& net, const float* __restrict__ params, float* bufA, float* bufB, float* out,
-                                          int lane, int wave, int hidden_act) {
-  const float* x = bufB;
-  float* y = bufA;
-  for (int l = 0; l < net.n_layers; l++) {
-    const bool last = l + 1 == net.n_layers;
-    const int K = net.dims[l], Nout = net.dims[l + 1];
-    const float* W = params + net.w_off[l];
-    const float* b = W + (size_t)K * Nout;
-    float* dst = last ? out : y;
-    if (((K | net.w_off[l]) & 3) == 0) actor_layer<true>(W, b, K, Nout, x, dst, lane, wave, last ? 0 : hidden_act);
-    else actor_layer<false>(W, b, K, Nout, x, dst, lane, wave, last ? 0 : hidden_act);
-    __syncthreads();
-    float* t = const_cast<float*>(x); x = y; y = t;
   }
 }
 
@@ -176,28 +178,4 @@ __device__ __forceinline__ void actor_finish(const ActorArgs& a, const float* ou
     if (a.logp) a.logp[row] = lp;
   }
   if (critic) a.value[row] = v;
-}
-
-__global__ void __launch_bounds__(ACT_THREADS) k_actor(ActorArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float act_lds[];
-  float* bufA = act_lds;
-  float* bufB = act_lds + (size_t)a.ldh * ACT_LD;
-  float* out = act_lds + (size_t)2 * a.ldh * ACT_LD;       // [4][ACT_LD]: mean 0..2, value
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int row0 = blockIdx.x * ACT_ROWS;
-  const int hidden_act = a.relu ? 2 : 1;
-  const bool sample = a.actions != nullptr;                // false: the value-only launch behind the last step
-  if (sample) {
-    actor_load_obs(a.obs, row0, a.rows, a.D, bufB, tid);
-    __syncthreads();
-    actor_net(a.actor, a.params, bufA, bufB, out, lane, wave, hidden_act);
-  }
-  const bool critic = a.critic.n_layers > 0 && a.value != nullptr;
-  if (critic) {
-    actor_load_obs(a.obs, row0, a.rows, a.D, bufB, tid);
-    __syncthreads();
-    actor_net(a.critic, a.params, bufA, bufB, out + 3 * ACT_LD, lane, wave, hidden_act);
-  }
-  if (wave != 0) return;
-  actor_finish(a, out, sample, critic, row0, lane);
 }

@@ -1,7 +1,7 @@
-// kernels_ln.hpp -- k_actor_ln / k_ln_grad: layer normalisation in the engine's actor-critic, forward and backward (MQE_ACTOR_LAYER_NORM,
-// MQE_ACTOR_FEATURE_NORM; include/mqe_hip.h).  Siblings of k_actor (kernels_actor.hpp) and k_ppo_grad (kernels_ppo.hpp), built from their device
-// functions (actor_layer, actor_load_obs, actor_finish; ppo_load_tile, ppo_actor_head, ppo_critic_head, ppo_dw, ppo_dx, ppo_store_sums): a handle
-// created without the two bits never launches a kernel of this file, and one created with either launches these two INSTEAD of the plain pair.
+// kernels_ln.hpp -- layer normalisation in the engine's actor-critic (MQE_ACTOR_LAYER_NORM, MQE_ACTOR_FEATURE_NORM; include/mqe_hip.h): the norm
+// itself, forward (ln_rows), again from its stored statistics (ln_again) and backward (ln_back), its constants and its two LDS rules.  The walks of
+// kernels_actor_critic.hpp switch it in at compile time (LN): k_actor_ln and k_ln_grad are the instantiations with it, k_actor and k_ppo_grad those
+// without.  A handle created without the two bits never launches the first pair, and one created with either launches it INSTEAD of the plain pair.
 // k_ppo_reduce, k_ppo_norm and k_ppo_adam are shared: gamma and beta are ordinary entries of the flat parameter buffer.
 //
 // THE OPERATOR is torch.nn.LayerNorm(n, eps = 1e-5, elementwise_affine = True) on the n features of one row: u = gamma * xhat + beta,
@@ -52,10 +52,6 @@
 #define LN_EPS 1e-5f
 #define LN_PART (2 * ACT_WAVES)                      // LDS rows of per-wave partials: two sums at a time
 #define LN_STAT (2 * MQE_ACTOR_MAX_LAYERS)           // LDS rows of (mu, rstd): norm j at rows 2 j, 2 j + 1; j = 0 the feature norm, j = l the norm in front of layer l
-
-struct LnNet { ActorNet net; float inv_n[MQE_ACTOR_MAX_LAYERS]; };      // inv_n[l] = (float)(1.0 / dims[l]): the width of layer l's INPUT
-struct LnNets { LnNet actor, critic; int hidden, feat; };
-struct ActorLnArgs { ActorArgs a; float inv_actor[MQE_ACTOR_MAX_LAYERS], inv_critic[MQE_ACTOR_MAX_LAYERS]; int hidden, feat; };
 
 static inline size_t actor_ln_lds_bytes(int ldh) { return (size_t)(2 * ldh + 4 + LN_PART) * ACT_LD * sizeof(float); }
 static inline int ln_lds_rows(const ActorNet& a, const ActorNet& c, int D, bool hidden, bool feat) {
@@ -165,168 +161,4 @@ __device__ __forceinline__ void ln_back(float* a, const float* du, int n, const 
     a[k * LD + row] = relu ? (av > 0.0f ? da : 0.0f) : da * fmaf(-av, av, 1.0f);
   }
   __syncthreads();
-}
-
-// ---- k_actor_ln: k_actor with the norms; the two ping-pong buffers are normalised in place -----------------------------------------------------
-__device__ __forceinline__ void ln_actor_net(const ActorNet& net, const float* inv_n, int hidden, int feat, const float* __restrict__ params, float* bufA,
-                                             float* bufB, float* out, float* part, int lane, int wave, int hidden_act) {
-  if (feat) {
-    const float* g = params + ln_gamma_off(net, 0);
-    ln_rows<ACT_LD>(bufB, bufB, net.dims[0], g, g + net.dims[0], inv_n[0], part, nullptr, lane, wave);
-  }
-  const float* x = bufB;
-  float* y = bufA;
-  for (int l = 0; l < net.n_layers; l++) {
-    const bool last = l + 1 == net.n_layers;
-    const int K = net.dims[l], Nout = net.dims[l + 1];
-    const float* W = params + net.w_off[l];
-    const float* b = W + (size_t)K * Nout;
-    float* dst = last ? out : y;
-    if (((K | net.w_off[l]) & 3) == 0) actor_layer<true>(W, b, K, Nout, x, dst, lane, wave, last ? 0 : hidden_act);
-    else actor_layer<false>(W, b, K, Nout, x, dst, lane, wave, last ? 0 : hidden_act);
-    __syncthreads();
-    if (!last && hidden) ln_rows<ACT_LD>(y, y, Nout, b + Nout, b + 2 * Nout, inv_n[l + 1], part, nullptr, lane, wave);
-    float* t = const_cast<float*>(x); x = y; y = t;
-  }
-}
-
-__global__ void __launch_bounds__(ACT_THREADS) k_actor_ln(ActorLnArgs k) {
-  extern __shared__ __attribute__((aligned(16))) float act_ln_lds[];
-  const ActorArgs& a = k.a;
-  float* bufA = act_ln_lds;
-  float* bufB = act_ln_lds + (size_t)a.ldh * ACT_LD;
-  float* out = act_ln_lds + (size_t)2 * a.ldh * ACT_LD;       // [4][ACT_LD]: mean 0..2, value
-  float* part = out + 4 * ACT_LD;                             // [LN_PART][ACT_LD]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int row0 = blockIdx.x * ACT_ROWS;
-  const int hidden_act = a.relu ? 2 : 1;
-  const bool sample = a.actions != nullptr;
-  if (sample) {
-    actor_load_obs(a.obs, row0, a.rows, a.D, bufB, tid);
-    __syncthreads();
-    ln_actor_net(a.actor, k.inv_actor, k.hidden, k.feat, a.params, bufA, bufB, out, part, lane, wave, hidden_act);
-  }
-  const bool critic = a.critic.n_layers > 0 && a.value != nullptr;
-  if (critic) {
-    actor_load_obs(a.obs, row0, a.rows, a.D, bufB, tid);
-    __syncthreads();
-    ln_actor_net(a.critic, k.inv_critic, k.hidden, k.feat, a.params, bufA, bufB, out + 3 * ACT_LD, part, lane, wave, hidden_act);
-  }
-  if (wave != 0) return;
-  actor_finish(a, out, sample, critic, row0, lane);
-}
-
-// ---- k_ln_grad: k_ppo_grad with the norms ---------------------------------------------------------------------------------------------------------
-// forward of one network, every activation kept: observation at lds[0], the activation of hidden layer l behind it as in ppo_forward, u in U
-template <int LD>
-__device__ __forceinline__ void ln_forward(const LnNet& ln, int hidden, int feat, const float* __restrict__ params, float* lds, int D, float* U, float* stat,
-                                           float* part, float* out, int row, int wave, int hidden_act) {
-  const ActorNet& net = ln.net;
-  const float* x = lds;
-  if (feat) {
-    const float* g = params + ln_gamma_off(net, 0);
-    ln_rows<LD>(lds, U, D, g, g + D, ln.inv_n[0], part, stat, row, wave);
-    x = U;
-  }
-  float* y = lds + (size_t)D * LD;
-  for (int l = 0; l < net.n_layers; l++) {
-    const bool last = l + 1 == net.n_layers;
-    const int K = net.dims[l], Nout = net.dims[l + 1];
-    const float* W = params + net.w_off[l];
-    const float* b = W + (size_t)K * Nout;
-    float* dst = last ? out : y;
-    if (((K | net.w_off[l]) & 3) == 0) actor_layer<true, LD>(W, b, K, Nout, x, dst, row, wave, last ? 0 : hidden_act);
-    else actor_layer<false, LD>(W, b, K, Nout, x, dst, row, wave, last ? 0 : hidden_act);
-    __syncthreads();
-    if (last) break;
-    x = y;
-    if (hidden) {
-      ln_rows<LD>(y, U, Nout, b + Nout, b + 2 * Nout, ln.inv_n[l + 1], part, stat + (size_t)2 * (l + 1) * LD, row, wave);
-      x = U;
-    }
-    y += (size_t)Nout * LD;
-  }
-}
-
-// backward of one network: `out` holds the delta of the last layer; per layer, top down: u of its input into U again, the weight gradient, du over U,
-// the norm's backward (delta over the stored activation in place).  A layer whose input is not normalised goes the plain way (ppo_dx in place).
-template <int LD, int RT>
-__device__ __forceinline__ void ln_backward(const LnNet& ln, int hidden, int feat, const float* __restrict__ params, float* __restrict__ pg, float* lds, int D,
-                                            float* U, float* stat, float* part, float* out, int row, int wave, int tid, int relu, bool first) {
-  const ActorNet& net = ln.net;
-  int below = 0;
-  for (int l = 1; l + 1 < net.n_layers; l++) below += net.dims[l];
-  float* dY = out;
-  for (int l = net.n_layers - 1; l >= 0; l--) {
-    const int K = net.dims[l], Nout = net.dims[l + 1];
-    float* a = l == 0 ? lds : lds + (size_t)(D + below) * LD;      // the stored input of layer l: the observation, or the activation below
-    const bool normed = l == 0 ? feat != 0 : hidden != 0;
-    const int go = normed ? ln_gamma_off(net, l) : 0;
-    const float* st = stat + (size_t)2 * l * LD;
-    const float* x = a;
-    if (normed) {
-      ln_again<LD>(a, U, K, params + go, params + go + K, st, row, wave);
-      __syncthreads();
-      x = U;
-    }
-    ppo_dw<LD, RT>(dY, x, K, Nout, pg + net.w_off[l], pg + net.w_off[l] + (size_t)K * Nout, first, tid);
-    __syncthreads();
-    if (l == 0 && !normed) break;
-    if (!normed) {
-      ppo_dx<LD>(params + net.w_off[l], K, Nout, dY, a, row, wave, relu);
-      __syncthreads();
-    } else {
-      ppo_dx<LD, true>(params + net.w_off[l], K, Nout, dY, U, row, wave, relu);
-      __syncthreads();
-      if (l == 0) {
-        ln_back<LD, RT, false>(a, U, K, params + go, ln.inv_n[0], st, part, pg + go, pg + go + K, first, relu, row, tid & 63, wave);
-        break;
-      }
-      ln_back<LD, RT, true>(a, U, K, params + go, ln.inv_n[l], st, part, pg + go, pg + go + K, first, relu, row, tid & 63, wave);
-    }
-    dY = a;
-    if (l >= 2) below -= net.dims[l - 1];
-  }
-}
-
-struct PpoTraj {
-  const float* packed; long long stride; int rows; long long n_total;
-  const float *actions, *logp_old, *value, *adv, *ret;
-  const int32_t* index; long long first, count;
-};
-
-template <int RT>
-__global__ void __launch_bounds__(ACT_THREADS) k_ln_grad(const float* __restrict__ params, const LnNets* __restrict__ nets, int log_std_off, int n_params, int D,
-                                                         int rows_lds, int uw, int relu, PpoTraj tr, PpoLoss ls, float* __restrict__ part_all,
-                                                         double* __restrict__ pst) {
-  constexpr int LD = RT + 1;
-  extern __shared__ __attribute__((aligned(16))) float ln_lds[];
-  float* out = ln_lds + (size_t)(rows_lds - 4) * LD;
-  float* part = out - (size_t)LN_PART * LD;
-  float* stat = part - (size_t)LN_STAT * LD;
-  float* U = stat - (size_t)uw * LD;
-  long long* srow = reinterpret_cast<long long*>(ln_lds + (size_t)rows_lds * LD + (((size_t)rows_lds * LD) & 1));      // 8-byte aligned
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int row = lane & (RT - 1);
-  const int hidden_act = relu ? 2 : 1;
-  const int hidden = nets->hidden, feat = nets->feat;
-  float* pg = part_all + (size_t)blockIdx.x * n_params;
-  const long long tiles = (tr.count + RT - 1) / RT;
-  PpoSums S;
-  bool first_tile = true;
-  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    ppo_load_tile<LD, RT>(ln_lds, srow, tr.packed, tr.stride, tr.rows, tr.n_total, tr.index, tr.first, tr.count, tile, D, tid);
-    const bool valid = tile * RT + lane < tr.count && lane < RT;
-    ln_forward<LD>(nets->actor, hidden, feat, params, ln_lds, D, U, stat, part, out, row, wave, hidden_act);
-    if (wave == 0) ppo_actor_head<LD, RT>(params, log_std_off, out, srow, row, lane, valid, tr.actions, tr.logp_old, tr.adv, ls, S);
-    __syncthreads();
-    ln_backward<LD, RT>(nets->actor, hidden, feat, params, pg, ln_lds, D, U, stat, part, out, row, wave, tid, relu, first_tile);
-    ln_forward<LD>(nets->critic, hidden, feat, params, ln_lds, D, U, stat, part, out + 3 * LD, row, wave, hidden_act);
-    if (wave == 0) ppo_critic_head<LD, RT>(out, srow, row, lane, valid, tr.value, tr.ret, ls, S);
-    __syncthreads();
-    ln_backward<LD, RT>(nets->critic, hidden, feat, params, pg, ln_lds, D, U, stat, part, out + 3 * LD, row, wave, tid, relu, first_tile);
-    first_tile = false;
-  }
-  if (wave != 0) return;
-  ppo_store_sums(S, lane, pst + (size_t)blockIdx.x * PPO_PST);
 }

@@ -1,5 +1,7 @@
-// kernels_ppo.hpp -- k_ppo_grad / k_ppo_reduce / k_ppo_norm / k_ppo_adam: the clipped-surrogate PPO loss of rsl_rl, its gradient with respect
-// to the engine's actor-critic parameters, and the Adam step on them (mqe_ppo_grad, mqe_ppo_adam; include/mqe_hip.h).
+// kernels_ppo.hpp -- the clipped-surrogate PPO loss of rsl_rl, its gradient with respect to the engine's actor-critic parameters, and the Adam step
+// on them (mqe_ppo_grad, mqe_ppo_adam; include/mqe_hip.h).  This file holds the primitives of the gradient kernel -- the LDS rule, backward-data
+// (ppo_dx), the weight gradient (ppo_dw), the tile load, the two loss heads and the statistics -- and the kernels behind it: k_ppo_reduce, k_ppo_norm,
+// k_ppo_adam.  The walk over the layers and the entry points k_ppo_grad / k_ln_grad are in kernels_actor_critic.hpp, behind the norm (kernels_ln.hpp).
 //
 // THE LOSS.  A sample is a flat index s = t * R' + r into a trajectory in mqe_rollout's layout, 0 <= s < T * R': its observation is the D
 // floats at packed + t * row_stride + r * D; actions[s][3], logp_old[s], v_old = value[s] (the first T rows of the [T + 1][R'] array), adv[s],
@@ -21,13 +23,11 @@
 //     hidden layers:   delta_in = (W^T delta_out) * (1 - y^2) (tanh, from the stored output y) or (y > 0 ? . : 0) (relu)
 // 1 / M is one f32 value, formed on the host as (float)(1.0 / M).
 //
-// LAYOUT.  A workgroup is 1024 threads = 16 wavefronts (k_actor's) and walks row tiles of RT samples: tile i of the minibatch is samples
-// i RT .. i RT + RT - 1; workgroup b of G = min(tiles, PPO_MAX_WG) takes tiles b, b + G, b + 2 G, ... in that order (a fixed grid: a function
-// of count, the tile height and PPO_MAX_WG alone).  LDS holds, as [k][row] with an odd row stride, the observation and EVERY layer output of
-// ONE network -- the backward pass needs them -- and the two networks run one after the other (actor forward, actor head, actor backward,
-// critic forward on the observation that is still there, critic head, critic backward).  No separate delta buffers: the delta of layer l - 1
-// overwrites the stored output of layer l - 1 IN PLACE, element by element by the thread that reads that element for the activation
-// derivative, after the weight gradient of layer l (the last reader of that output as an input) is done.  So the footprint is
+// LAYOUT.  A workgroup is 1024 threads = 16 wavefronts (k_actor's) and walks row tiles of RT samples (kernels_actor_critic.hpp: the tile loop and the
+// order of the phases).  LDS holds, as [k][row] with an odd row stride, the observation and EVERY layer output of ONE network -- the backward pass
+// needs them.  No separate delta buffers: the delta of layer l - 1 overwrites the stored output of layer l - 1 IN PLACE, element by element by
+// the thread that reads that element for the activation derivative, after the weight gradient of layer l (the last reader of that output as
+// an input) is done.  So the footprint is
 // (D + sum of hidden widths + 4) rows; RT = 64 (stride 65) when that fits 160 KiB -- every network up to 128 x 128 x 128, the 64 x 64 case
 // included -- else RT = 32 (stride 33: lanes 32 .. 63 repeat rows 0 .. 31 in the lane = row phases), which holds the widest accepted stack
 // (128 + 3 x 256 + 4 rows = 116 KiB).  A 16-row tile is never needed.
@@ -160,51 +160,12 @@ __device__ __forceinline__ void ppo_dw(const float* dY, const float* x, int K, i
   }
 }
 
-struct PpoNets { ActorNet actor, critic; };      // read from device memory (wave-uniform loads at the layer loops): 20 words that need no registers
-
-// forward of one network with every layer output kept: observation at lds[0], hidden output l at hid + (sum of the widths below it) rows,
-// the last layer at `out`
-template <int LD>
-__device__ __forceinline__ void ppo_forward(const ActorNet& net, const float* __restrict__ params, float* lds, int D, float* out, int row, int wave,
-                                            int hidden_act) {
-  const float* x = lds;
-  float* y = lds + (size_t)D * LD;
-  for (int l = 0; l < net.n_layers; l++) {
-    const bool last = l + 1 == net.n_layers;
-    const int K = net.dims[l], Nout = net.dims[l + 1];
-    const float* W = params + net.w_off[l];
-    const float* b = W + (size_t)K * Nout;
-    float* dst = last ? out : y;
-    if (((K | net.w_off[l]) & 3) == 0) actor_layer<true, LD>(W, b, K, Nout, x, dst, row, wave, last ? 0 : hidden_act);
-    else actor_layer<false, LD>(W, b, K, Nout, x, dst, row, wave, last ? 0 : hidden_act);
-    __syncthreads();
-    x = y;
-    y += (size_t)Nout * LD;
-  }
-}
-
-// backward of one network: `out` holds the delta of the last layer; walks the layers down, weight gradient first, then the delta below in place
-template <int LD, int RT>
-__device__ __forceinline__ void ppo_backward(const ActorNet& net, const float* __restrict__ params, float* __restrict__ part, float* lds, int D,
-                                             float* out, int row, int wave, int tid, int relu, bool first) {
-  int below = 0;                       // rows under the input of layer l: D + hidden widths 1 .. l - 1, minus the input's own
-  for (int l = 1; l + 1 < net.n_layers; l++) below += net.dims[l];
-  // x of the last layer starts at row D + (sum of hidden widths but the last); for a single-layer network it is the observation
-  float* dY = out;
-  for (int l = net.n_layers - 1; l >= 0; l--) {
-    const int K = net.dims[l], Nout = net.dims[l + 1];
-    float* x = l == 0 ? lds : lds + (size_t)(D + below) * LD;
-    ppo_dw<LD, RT>(dY, x, K, Nout, part + net.w_off[l], part + net.w_off[l] + (size_t)K * Nout, first, tid);
-    __syncthreads();
-    if (l == 0) break;
-    ppo_dx<LD>(params + net.w_off[l], K, Nout, dY, x, row, wave, relu);
-    __syncthreads();
-    dY = x;
-    if (l >= 2) below -= net.dims[l - 1];
-  }
-}
-
 struct PpoLoss { float clip, value_coef, entropy_coef, value_clip, inv_m; int clip_value; };
+struct PpoTraj {                       // the trajectory and the minibatch of it (THE LOSS above)
+  const float* packed; long long stride; int rows; long long n_total;
+  const float *actions, *logp_old, *value, *adv, *ret;
+  const int32_t* index; long long first, count;
+};
 struct PpoSums { double Lpi = 0.0, Lv = 0.0, Kl = 0.0, Clip = 0.0, gls[3] = {0.0, 0.0, 0.0}; };      // f64 per lane of wavefront 0 over the workgroup's tiles
 
 // the samples of tile `tile` (past the end of the minibatch the last one again) and their observations -> LDS [k][row]
@@ -297,43 +258,6 @@ __device__ __forceinline__ void ppo_store_sums(const PpoSums& S, int lane, doubl
 #pragma unroll
     for (int q = 0; q < 7; q++) pst[q] = v[q];
   }
-}
-
-template <int RT>
-__global__ void __launch_bounds__(ACT_THREADS) k_ppo_grad(const float* __restrict__ params, const PpoNets* __restrict__ nets, int log_std_off, int n_params, int D, int rows_lds,
-                                                          int relu, const float* __restrict__ packed, long long stride, int rows, long long n_total,
-                                                          const float* __restrict__ actions, const float* __restrict__ logp_old,
-                                                          const float* __restrict__ value, const float* __restrict__ adv, const float* __restrict__ ret,
-                                                          const int32_t* __restrict__ index, long long first, long long count, PpoLoss ls,
-                                                          float* __restrict__ part_all, double* __restrict__ pst) {
-  constexpr int LD = RT + 1;
-  extern __shared__ __attribute__((aligned(16))) float ppo_lds[];
-  float* out = ppo_lds + (size_t)(rows_lds - 4) * LD;
-  long long* srow = reinterpret_cast<long long*>(ppo_lds + (size_t)rows_lds * LD + (((size_t)rows_lds * LD) & 1));      // 8-byte aligned
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int row = lane & (RT - 1);
-  const int hidden_act = relu ? 2 : 1;
-  float* part = part_all + (size_t)blockIdx.x * n_params;
-  const long long tiles = (count + RT - 1) / RT;
-  PpoSums S;
-  bool first_tile = true;
-  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    ppo_load_tile<LD, RT>(ppo_lds, srow, packed, stride, rows, n_total, index, first, count, tile, D, tid);
-    const bool valid = tile * RT + lane < count && lane < RT;
-    // ---- actor ----
-    ppo_forward<LD>(nets->actor, params, ppo_lds, D, out, row, wave, hidden_act);
-    if (wave == 0) ppo_actor_head<LD, RT>(params, log_std_off, out, srow, row, lane, valid, actions, logp_old, adv, ls, S);
-    __syncthreads();
-    ppo_backward<LD, RT>(nets->actor, params, part, ppo_lds, D, out, row, wave, tid, relu, first_tile);
-    // ---- critic: the observation is still in place ----
-    ppo_forward<LD>(nets->critic, params, ppo_lds, D, out + 3 * LD, row, wave, hidden_act);
-    if (wave == 0) ppo_critic_head<LD, RT>(out, srow, row, lane, valid, value, ret, ls, S);
-    __syncthreads();
-    ppo_backward<LD, RT>(nets->critic, params, part, ppo_lds, D, out + 3 * LD, row, wave, tid, relu, first_tile);
-    first_tile = false;
-  }
-  if (wave != 0) return;
-  ppo_store_sums(S, lane, pst + (size_t)blockIdx.x * PPO_PST);
 }
 
 // grad and the statistics from the G workgroups' partials, in workgroup order

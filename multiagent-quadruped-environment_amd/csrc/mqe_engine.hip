@@ -24,6 +24,7 @@
 #include "kernels_ppo.hpp"
 #include "kernels_vn.hpp"
 #include "kernels_ln.hpp"
+#include "kernels_actor_critic.hpp"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, const char* a = "", const char* b = "", const char* c = "") {      // fmt: up to three %s
@@ -124,12 +125,11 @@ struct mqe_sim {
   // step reads action_gain * a from.  Parameters are the trainer's, not simulation state: never in state_bufs
   struct Actor {
     bool on = false;
-    ActorNet actor, critic;
+    ActorShapes sh = {};          // the two networks, the norms' 1 / n, the two switches: what the four kernels of kernels_actor_critic.hpp read
     int log_std_off = 0, n_params = 0, ldh = 0, relu = 0;
     float gain = 1.0f;
     bool vnorm = false;           // MQE_ACTOR_VALUE_NORM: MQE_VALUE_NORM_STATE floats behind the n_params trainable ones
-    bool ln_hidden = false, ln_feat = false;      // MQE_ACTOR_LAYER_NORM / MQE_ACTOR_FEATURE_NORM: either one selects k_actor_ln and k_ln_grad (kernels_ln.hpp)
-    float inv_actor[MQE_ACTOR_MAX_LAYERS] = {}, inv_critic[MQE_ACTOR_MAX_LAYERS] = {};      // (float)(1.0 / dims[l]): the norms' 1 / n
+    bool ln() const { return sh.hidden || sh.feat; }      // MQE_ACTOR_LAYER_NORM / MQE_ACTOR_FEATURE_NORM: either one selects k_actor_ln and k_ln_grad
     float* params = nullptr;      // [n_params (+ MQE_VALUE_NORM_STATE)]
     float* stage = nullptr;       // [N, A', 3]
   } act;
@@ -151,7 +151,7 @@ struct mqe_sim {
   struct Ppo {
     float* part = nullptr;
     double* pst = nullptr;
-    int32_t* nets = nullptr;      // the two ActorNet shapes as k_ppo_grad reads them (PpoNets; LnNets for k_ln_grad)
+    ActorShapes* nets = nullptr;      // the actor's shapes on the device, as k_ppo_grad / k_ln_grad read them
     int rt = 0, lds_rows = 0, uw = 0;      // uw: rows of k_ln_grad's shared buffer of normalised inputs
     float* moments = nullptr;
     double* norm = nullptr;
@@ -1616,12 +1616,11 @@ extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
   if (not_finite(&sh->action_gain) || std::fabs(sh->action_gain) >= 1e30f) return fail(-6, "mqe_actor_create: action_gain is not finite");
   mqe_sim::Actor a;
   int off = 0, ldh = 0;
-  memset(&a.actor, 0, sizeof a.actor); memset(&a.critic, 0, sizeof a.critic);
-  if (int rc = actor_net_shape("actor", sh->actor_layers, sh->actor_dims, sh->obs_dim, 3, ln_hidden, ln_feat, &a.actor, a.inv_actor, &off, &ldh)) return rc;
+  if (int rc = actor_net_shape("actor", sh->actor_layers, sh->actor_dims, sh->obs_dim, 3, ln_hidden, ln_feat, &a.sh.actor, a.sh.inv_actor, &off, &ldh)) return rc;
   if (sh->critic_layers != 0)
-    if (int rc = actor_net_shape("critic", sh->critic_layers, sh->critic_dims, sh->obs_dim, 1, ln_hidden, ln_feat, &a.critic, a.inv_critic, &off, &ldh)) return rc;
+    if (int rc = actor_net_shape("critic", sh->critic_layers, sh->critic_dims, sh->obs_dim, 1, ln_hidden, ln_feat, &a.sh.critic, a.sh.inv_critic, &off, &ldh)) return rc;
   a.log_std_off = off; a.n_params = off + 3; a.ldh = ldh; a.relu = kind == MQE_ACTOR_RELU; a.gain = sh->action_gain; a.vnorm = vnorm;
-  a.ln_hidden = ln_hidden; a.ln_feat = ln_feat;
+  a.sh.hidden = ln_hidden; a.sh.feat = ln_feat;
   const bool ln = ln_hidden || ln_feat;
   const size_t lds = ln ? actor_ln_lds_bytes(ldh) : actor_lds_bytes(ldh);
   if (lds > 48 * 1024 && hipFuncSetAttribute(ln ? (const void*)k_actor_ln : (const void*)k_actor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -1642,7 +1641,7 @@ extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
   if (ln) {                            // every gamma starts at 1 (torch.nn.LayerNorm's own start); the rest of the buffer stays zero
     std::vector<float> ones(MQE_ACTOR_MAX_HIDDEN > MQE_ACTOR_MAX_OBS ? MQE_ACTOR_MAX_HIDDEN : MQE_ACTOR_MAX_OBS, 1.0f);
     bool ok = true;
-    for (const ActorNet* net : {&a.actor, &a.critic})
+    for (const ActorNet* net : {&a.sh.actor, &a.sh.critic})
       for (int l = 0; l < net->n_layers; l++)
         if (l == 0 ? ln_feat : ln_hidden)
           ok = ok && hipMemcpy(a.params + ln_gamma_off(*net, l), ones.data(), (size_t)net->dims[l] * 4, hipMemcpyHostToDevice) == hipSuccess;
@@ -1665,19 +1664,12 @@ extern "C" int mqe_actor_params(mqe_sim* s, mqe_tensor_view* v) {
 static void launch_actor(mqe_sim* s, const float* obs, float* actions, float* logp, float* value, int flags, bool value_only, hipStream_t q) {
   const mqe_sim::Actor& a = s->act;
   ActorArgs k;
-  k.params = a.params; k.obs = obs; k.actions = value_only ? nullptr : actions; k.logp = logp; k.value = value; k.stage = a.stage;
-  k.actor = a.actor; k.critic = a.critic; k.log_std_off = a.log_std_off;
+  k.sh = a.sh; k.params = a.params; k.obs = obs; k.actions = value_only ? nullptr : actions; k.logp = logp; k.value = value; k.stage = a.stage;
+  k.log_std_off = a.log_std_off;
   k.rows = s->N * s->Aw; k.D = s->D; k.Aw = s->Aw; k.ldh = a.ldh; k.relu = a.relu; k.deterministic = (flags & MQE_ROLLOUT_DETERMINISTIC) ? 1 : 0;
   k.gain = a.gain; k.seed = (uint32_t)s->d.seed; k.genv0 = (uint32_t)s->d.env_id_offset; k.count = MQE_RNG_ACTOR + (uint32_t)s->n_post_steps;
   const dim3 grid((k.rows + ACT_ROWS - 1) / ACT_ROWS);
-  if (!a.ln_hidden && !a.ln_feat) {
-    hipLaunchKernelGGL(k_actor, grid, dim3(ACT_THREADS), actor_lds_bytes(a.ldh), q, k);
-    return;
-  }
-  ActorLnArgs kl;
-  kl.a = k; kl.hidden = a.ln_hidden; kl.feat = a.ln_feat;
-  memcpy(kl.inv_actor, a.inv_actor, sizeof kl.inv_actor); memcpy(kl.inv_critic, a.inv_critic, sizeof kl.inv_critic);
-  hipLaunchKernelGGL(k_actor_ln, grid, dim3(ACT_THREADS), actor_ln_lds_bytes(a.ldh), q, kl);
+  hipLaunchKernelGGL(a.ln() ? k_actor_ln : k_actor, grid, dim3(ACT_THREADS), a.ln() ? actor_ln_lds_bytes(a.ldh) : actor_lds_bytes(a.ldh), q, k);
 }
 extern "C" int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* packed_dev, long long row_stride, float* actions_dev, float* logp_dev,
                            float* value_dev, int flags, void* stream) {
@@ -1688,7 +1680,7 @@ extern "C" int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* pack
   TrajShape ts;
   if (int rc = traj_shape(s, "mqe_rollout", T, row_stride, &ts)) return rc;
   if (int rc = check_aligned("mqe_rollout", {{packed_dev, 16}, {obs0_dev, 4}, {actions_dev, 4}, {logp_dev, 4}, {value_dev, 4}}, "packed_dev: 16 bytes, the others: 4")) return rc;
-  if (value_dev && s->act.critic.n_layers == 0) return fail(-6, "mqe_rollout: value_dev given, but the actor was created without a critic");
+  if (value_dev && s->act.sh.critic.n_layers == 0) return fail(-6, "mqe_rollout: value_dev given, but the actor was created without a critic");
   if (s->to_rec && T > s->to_rec_cap) return fail(-6, "mqe_rollout: T exceeds capacity_steps of the registered time-out record (mqe_rollout_time_outs)");
   hipStream_t q = (hipStream_t)stream;
   const size_t rows = ts.rows, nobs = rows * s->D;
@@ -1767,6 +1759,8 @@ extern "C" int mqe_gae(mqe_sim* s, int T, const float* packed_dev, long long row
 }
 
 // ---- mqe_ppo_grad / mqe_ppo_optimizer / mqe_ppo_adam (include/mqe_hip.h; kernels_ppo.hpp) ------------------------------------------------------
+// the gradient kernel of an actor: with or without the norms, by the row tile its shapes allow
+static auto ppo_grad_kernel(bool ln, int rt) { return ln ? (rt == 64 ? k_ln_grad<64> : k_ln_grad<32>) : (rt == 64 ? k_ppo_grad<64> : k_ppo_grad<32>); }
 extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long long row_stride, const float* actions_dev, const float* logp_dev,
                             const float* value_dev, const float* adv_dev, const float* ret_dev, const int32_t* index_dev, long long first,
                             long long count, const mqe_ppo_loss* loss, int flags, float* grad_dev, float* stats_dev, void* stream) {
@@ -1774,7 +1768,7 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   if (!packed_dev || !actions_dev || !logp_dev || !value_dev || !adv_dev || !ret_dev || !loss || !grad_dev)
     return fail(-1, "mqe_ppo_grad: packed_dev, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, loss and grad_dev are required");
   if (!s->act.on) return fail(-6, "mqe_ppo_grad: no actor (mqe_actor_create)");
-  if (s->act.critic.n_layers == 0) return fail(-6, "mqe_ppo_grad: the actor was created without a critic: the loss has a value term");
+  if (s->act.sh.critic.n_layers == 0) return fail(-6, "mqe_ppo_grad: the actor was created without a critic: the loss has a value term");
   TrajShape ts;
   if (int rc = traj_shape(s, "mqe_ppo_grad", T, row_stride, &ts)) return rc;
   if (int rc = check_aligned("mqe_ppo_grad", {{packed_dev, 16}, {actions_dev, 4}, {logp_dev, 4}, {value_dev, 4}, {adv_dev, 4}, {ret_dev, 4}, {index_dev, 4},
@@ -1804,37 +1798,21 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
                                                {vn_state, MQE_VALUE_NORM_STATE * 4, "the value-normalisation state"}}, 2)) return rc;
   if (vn && (vn_scratch(s, &s->vn.tgt, &s->vn.tgt_cap, n) || (!s->vn.part && dalloc(s, &s->vn.part, (size_t)VN_PART))))
     return fail(-5, "device alloc failed (mqe_ppo_grad value-normalisation scratch)");
-  const bool ln = a.ln_hidden || a.ln_feat;
+  const bool ln = a.ln();
   if (!s->ppo.part) {                  // once per actor: the row tile of its shapes, the scratch (hipMalloc synchronises)
     mqe_sim::Ppo& p = s->ppo;
-    p.lds_rows = ln ? ln_lds_rows(a.actor, a.critic, s->D, a.ln_hidden, a.ln_feat) : ppo_lds_rows(a.actor, a.critic, s->D);
-    p.uw = ln ? p.lds_rows - ppo_lds_rows(a.actor, a.critic, s->D) - LN_STAT - LN_PART : 0;
+    const int plain_rows = ppo_lds_rows(a.sh.actor, a.sh.critic, s->D);
+    p.lds_rows = ln ? ln_lds_rows(a.sh.actor, a.sh.critic, s->D, a.sh.hidden, a.sh.feat) : plain_rows;
+    p.uw = ln ? p.lds_rows - plain_rows - LN_STAT - LN_PART : 0;
     p.rt = ppo_lds_bytes(p.lds_rows, 64) <= PPO_LDS_LIMIT ? 64 : 32;
     const int lds = (int)ppo_lds_bytes(p.lds_rows, p.rt);
-    // the shapes as the selected kernel reads them: LnNets (with the norms' 1 / n and the two switches) for k_ln_grad, PpoNets for k_ppo_grad
-    LnNets with_norms;
-    PpoNets plain;
-    const void* kern;
-    const void* image;
-    size_t image_bytes;
-    if (ln) {
-      if (lds > PPO_LDS_LIMIT)
-        return fail(-5, "mqe_ppo_grad: the layer outputs of one network, the widest norm's input and k_ln_grad's statistics do not fit the LDS even at 32 rows");
-      kern = p.rt == 64 ? (const void*)k_ln_grad<64> : (const void*)k_ln_grad<32>;
-      memset(&with_norms, 0, sizeof with_norms);
-      with_norms.actor.net = a.actor; with_norms.critic.net = a.critic; with_norms.hidden = a.ln_hidden; with_norms.feat = a.ln_feat;
-      memcpy(with_norms.actor.inv_n, a.inv_actor, sizeof a.inv_actor); memcpy(with_norms.critic.inv_n, a.inv_critic, sizeof a.inv_critic);
-      image = &with_norms; image_bytes = sizeof with_norms;
-    } else {
-      if (lds > PPO_LDS_LIMIT) return fail(-5, "mqe_ppo_grad: the layer outputs of one network do not fit the LDS even at 32 rows");
-      kern = p.rt == 64 ? (const void*)k_ppo_grad<64> : (const void*)k_ppo_grad<32>;
-      plain.actor = a.actor; plain.critic = a.critic;
-      image = &plain; image_bytes = sizeof plain;
-    }
-    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (lds > PPO_LDS_LIMIT)
+      return fail(-5, ln ? "mqe_ppo_grad: the layer outputs of one network, the widest norm's input and k_ln_grad's statistics do not fit the LDS even at 32 rows"
+                         : "mqe_ppo_grad: the layer outputs of one network do not fit the LDS even at 32 rows");
+    const hipError_t e = hipFuncSetAttribute((const void*)ppo_grad_kernel(ln, p.rt), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (lds > 48 * 1024 && e != hipSuccess) return fail(-5, ln ? "mqe_ppo_grad: cannot reserve LDS for k_ln_grad" : "mqe_ppo_grad: cannot reserve LDS for k_ppo_grad");
-    if (dalloc(s, &p.pst, (size_t)PPO_MAX_WG * PPO_PST) || dalloc(s, &p.nets, image_bytes / 4) ||
-        hipMemcpy(p.nets, image, image_bytes, hipMemcpyHostToDevice) != hipSuccess || dalloc(s, &p.part, (size_t)PPO_MAX_WG * a.n_params, 0)) {
+    if (dalloc(s, &p.pst, (size_t)PPO_MAX_WG * PPO_PST) || dalloc(s, &p.nets, 1) ||
+        hipMemcpy(p.nets, &a.sh, sizeof a.sh, hipMemcpyHostToDevice) != hipSuccess || dalloc(s, &p.part, (size_t)PPO_MAX_WG * a.n_params, 0)) {
       p.part = nullptr;                // the next call tries again; what was allocated is released with the handle
       return fail(-5, "device alloc failed (mqe_ppo_grad scratch)");
     }
@@ -1856,17 +1834,11 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
                        vn_update ? (const double*)s->vn.part : nullptr, gm, s->vn.tgt);
     ret_dev = s->vn.tgt;
   }
-  if (!ln) {
-    hipLaunchKernelGGL(rt == 64 ? k_ppo_grad<64> : k_ppo_grad<32>, dim3(G), dim3(ACT_THREADS), lds, q, (const float*)a.params, reinterpret_cast<const PpoNets*>(s->ppo.nets), a.log_std_off, a.n_params, s->D,
-                       s->ppo.lds_rows, a.relu,
-                       packed_dev, row_stride, (int)rows, (long long)n, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, index_dev, first, count, ls, s->ppo.part, s->ppo.pst);
-  } else {
-    PpoTraj tr;
-    tr.packed = packed_dev; tr.stride = row_stride; tr.rows = (int)rows; tr.n_total = (long long)n; tr.actions = actions_dev; tr.logp_old = logp_dev;
-    tr.value = value_dev; tr.adv = adv_dev; tr.ret = ret_dev; tr.index = index_dev; tr.first = first; tr.count = count;
-    hipLaunchKernelGGL(rt == 64 ? k_ln_grad<64> : k_ln_grad<32>, dim3(G), dim3(ACT_THREADS), lds, q, (const float*)a.params, reinterpret_cast<const LnNets*>(s->ppo.nets),
-                       a.log_std_off, a.n_params, s->D, s->ppo.lds_rows, s->ppo.uw, a.relu, tr, ls, s->ppo.part, s->ppo.pst);
-  }
+  PpoTraj tr;
+  tr.packed = packed_dev; tr.stride = row_stride; tr.rows = (int)rows; tr.n_total = (long long)n; tr.actions = actions_dev; tr.logp_old = logp_dev;
+  tr.value = value_dev; tr.adv = adv_dev; tr.ret = ret_dev; tr.index = index_dev; tr.first = first; tr.count = count;
+  hipLaunchKernelGGL(ppo_grad_kernel(ln, rt), dim3(G), dim3(ACT_THREADS), lds, q, (const float*)a.params, (const ActorShapes*)s->ppo.nets, tr, a.log_std_off,
+                     a.n_params, s->D, s->ppo.lds_rows, s->ppo.uw, a.relu, s->ppo.part, s->ppo.pst, ls);
   hipLaunchKernelGGL(k_ppo_reduce, dim3((a.n_params + PPO_REDUCE_THREADS - 1) / PPO_REDUCE_THREADS), dim3(PPO_REDUCE_THREADS), 0, q, (const float*)s->ppo.part,
                      (const double*)s->ppo.pst, G, a.n_params, a.log_std_off, count, ls.value_coef, ls.entropy_coef, (const float*)a.params, grad_dev, stats_dev);
   return launched();

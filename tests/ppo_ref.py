@@ -1,6 +1,8 @@
 """Host side of the PPO tests (mqe_ppo_grad, mqe_ppo_adam; csrc/kernels_ppo.hpp): the loss in torch (for autograd), a manual backward at any
 dtype (float64 is the reference; float32, whole batch or tile by tile, is the yardstick), deliberately wrong variants, Adam with the norm
-clip, the seeded kink-free trajectory in mqe_rollout's layout that the CPU and the GPU tests share, and the tolerances.
+clip, the seeded kink-free trajectory in mqe_rollout's layout that the CPU and the GPU tests share, and the tolerances.  Every loss function
+takes hidden= and feat=, the two layer-norm switches (csrc/kernels_ln.hpp; tests/layer_norm_ref.py holds its cases and its K): one statement
+of the loss and of its backward for the plain networks and for those with norms, on the one walk rollout_ref.forward.
 
 THE GRADIENT BOUND.  For every parameter tensor n the float64 backward also yields S_n, the largest entry of the sum over the samples of the
 ABSOLUTE per-sample contributions (|Delta|^T |X| for a weight, sum |Delta| for a bias, sum |dlogp (z^2 - 1)| + entropy_coef for log_std):
@@ -28,6 +30,7 @@ import torch
 
 from mqe.engine import abi
 import rollout_ref
+from rollout_ref import forward
 
 EPS32 = 2.0 ** -24
 SENT = 0x7FC12345
@@ -55,24 +58,14 @@ def shape_for(M, D=16):
 
 
 # ---- the loss ---------------------------------------------------------------------------------------------------------------------------
-def _forward(params, who, dims, act, x):
-    """all layer outputs: [x, h_1, ..., out]"""
-    hs = [x]
-    n = len(dims) - 1
-    for l in range(n):
-        x = x @ params[f"{who}.{l}.weight"].T + params[f"{who}.{l}.bias"]
-        if l + 1 < n:
-            x = torch.tanh(x) if act == "tanh" else torch.relu(x)
-        hs.append(x)
-    return hs
-
-
-def loss_torch(params, a_dims, c_dims, act, b, cfg):
-    """the stated loss as a torch expression (for autograd) in the dtype of params: -> (L, stats[6])"""
+def loss_torch(params, a_dims, c_dims, act, b, cfg, variant=None, hidden=False, feat=False):
+    """the stated loss as a torch expression (for autograd) in the dtype of params: -> (L, stats[6]).  A norm is torch.nn.functional.layer_norm
+    unless a wrong network is asked for (variant: layer_norm_ref.VARIANTS_FORWARD)"""
     c, vc, ec, cv = cfg["clip"], cfg["value_coef"], cfg["entropy_coef"], cfg["value_clip"]
     ls = params["log_std"]
-    mean = _forward(params, "actor", a_dims, act, b["obs"])[-1]
-    v = _forward(params, "critic", c_dims, act, b["obs"])[-1][:, 0]
+    net = dict(hidden=hidden, feat=feat, variant=variant, functional=variant is None)
+    mean = forward(params, "actor", a_dims, act, b["obs"], **net)[0]
+    v = forward(params, "critic", c_dims, act, b["obs"], **net)[0][:, 0]
     z = (b["actions"] - mean) * torch.exp(-ls)
     logp = (-0.5 * z * z - ls).sum(-1) - 1.5 * LN2PI
     ratio = torch.exp(logp - b["logp_old"])
@@ -87,19 +80,21 @@ def loss_torch(params, a_dims, c_dims, act, b, cfg):
     return L, stats
 
 
-def autograd(params, a_dims, c_dims, act, b, cfg, dtype):
+def autograd(params, a_dims, c_dims, act, b, cfg, dtype, variant=None, hidden=False, feat=False):
     """torch autograd of loss_torch at `dtype` on the whole batch: -> ({name: grad}, stats)"""
     p = {k: v.to(dtype).clone().requires_grad_(True) for k, v in params.items()}
     bb = {k: v.to(dtype) for k, v in b.items()}
-    L, stats = loss_torch(p, a_dims, c_dims, act, bb, cfg)
+    L, stats = loss_torch(p, a_dims, c_dims, act, bb, cfg, variant, hidden, feat)
     L.backward()
     return {k: (v.grad if v.grad is not None else torch.zeros_like(v)).detach() for k, v in p.items()}, stats.detach()
 
 
-def manual(params, a_dims, c_dims, act, b, cfg, dtype=torch.float64, tile=None, variant=None):
-    """The manual backward at `dtype`: the gradient as csrc/kernels_ppo.hpp states it (selects at the kinks), accumulated over tiles of `tile`
-    rows in order (None: the whole batch at once).  -> (grads, stats[6], S, stat_scales): S[name] = the scale S_n of the module docstring.
-    variant: "gate_ignored", "no_inv_m", "entropy_sign", "value_clip_ignored", "z_no_inv" -- each a wrong gradient."""
+def manual(params, a_dims, c_dims, act, b, cfg, dtype=torch.float64, tile=None, variant=None, hidden=False, feat=False):
+    """The manual backward at `dtype`: the gradient as csrc/kernels_ppo.hpp states it (selects at the kinks) and the norms' backward as
+    csrc/kernels_ln.hpp does (float32: the norm in the kernel's order), accumulated over tiles of `tile` rows in order (None: the whole batch
+    at once).  -> (grads, stats[6], S, stat_scales): S[name] = the scale S_n of the module docstring (for a norm: sum |du xhat| for its weight,
+    sum |du| for its bias).  variant, each a wrong gradient: "gate_ignored", "no_inv_m", "entropy_sign", "value_clip_ignored", "z_no_inv"; of
+    the norm's backward: "no_gamma" (dxhat = du), "no_xhat_term" (the xhat * mean(dxhat xhat) term dropped)."""
     c, vc, ec, cv = cfg["clip"], cfg["value_coef"], cfg["entropy_coef"], cfg["value_clip"]
     if variant == "value_clip_ignored":
         cv = None
@@ -113,55 +108,64 @@ def manual(params, a_dims, c_dims, act, b, cfg, dtype=torch.float64, tile=None, 
     S = {k: torch.zeros_like(v) for k, v in p.items()}
     sums = torch.zeros(4, dtype=dtype)           # L_pi, L_v, logp_old - logp, clipped
     sc = torch.zeros(3, dtype=dtype)             # scales of L_pi, L_v, KL sums
+    net = dict(hidden=hidden, feat=feat, kernel_order=dtype == torch.float32)
     tile = tile or M
     for r0 in range(0, M, tile):
         sl = slice(r0, min(r0 + tile, M))
         obs = b["obs"][sl]
-        delta_out, hs_all = {}, {}
+        fa = forward(p, "actor", a_dims, act, obs, **net)
+        fc = forward(p, "critic", c_dims, act, obs, **net)
         # actor head
-        hs = _forward(p, "actor", a_dims, act, obs)
-        mean = hs[-1]
+        mean, v = fa[0], fc[0][:, 0]
         z = (b["actions"][sl] - mean) * inv
         logp = (-0.5 * z * z - ls).sum(-1) - 1.5 * LN2PI
-        lpo, adv = b["logp_old"][sl], b["adv"][sl]
+        lpo, adv, ret = b["logp_old"][sl], b["adv"][sl], b["ret"][sl]
         ratio = torch.exp(logp - lpo)
         Lpi = -torch.minimum(ratio * adv, torch.clamp(ratio, 1 - c, 1 + c) * adv)
         gate = ((adv > 0) & (ratio > 1 + c)) | ((adv < 0) & (ratio < 1 - c))
         dlp = -adv * ratio * inv_m
         if variant != "gate_ignored":
             dlp = torch.where(gate, torch.zeros_like(dlp), dlp)
-        delta_out["actor"], hs_all["actor"] = dlp[:, None] * z * inv, hs
         g["log_std"] += (dlp[:, None] * (z * z - 1)).sum(0)
         S["log_std"] += (dlp[:, None] * (z * z - 1)).abs().sum(0)
         # critic head
-        hs = _forward(p, "critic", c_dims, act, obs)
-        v, ret = hs[-1][:, 0], b["ret"][sl]
         d1 = v - ret
         Lv, dv = d1 * d1, 2 * d1
         if cv is not None:
             vo = b["v_old"][sl]
-            v_c = vo + torch.clamp(v - vo, -cv, cv)
-            d2 = v_c - ret
+            d2 = vo + torch.clamp(v - vo, -cv, cv) - ret
             Lv = torch.maximum(d1 * d1, d2 * d2)
             dv = torch.where(d1 * d1 >= d2 * d2, 2 * d1, torch.where((v - vo).abs() < cv, 2 * d2, torch.zeros_like(d1)))
-        delta_out["critic"], hs_all["critic"] = (vc * inv_m * dv)[:, None], hs
         sums += torch.stack([Lpi.sum(), Lv.sum(), (lpo - logp).sum(), ((ratio - 1).abs() > c).to(dtype).sum()])
         # the magnitudes that the last layers' sums act on, for the statistics' scales
-        mag = lambda who, dims, hs: hs[-2].abs() @ p[f"{who}.{len(dims) - 2}.weight"].abs().T + p[f"{who}.{len(dims) - 2}.bias"].abs()
-        A = (0.5 * z * z + ls.abs()).sum(-1) + 1.5 * LN2PI + lpo.abs() + (z.abs() * inv * mag("actor", a_dims, hs_all["actor"])).sum(-1)
-        vmag = mag("critic", c_dims, hs)[:, 0] + ret.abs() + (b["v_old"][sl].abs() if cv is not None else 0)
+        mag = lambda who, dims, f: f[1][-1].abs() @ p[f"{who}.{len(dims) - 2}.weight"].abs().T + p[f"{who}.{len(dims) - 2}.bias"].abs()
+        A = (0.5 * z * z + ls.abs()).sum(-1) + 1.5 * LN2PI + lpo.abs() + (z.abs() * inv * mag("actor", a_dims, fa)).sum(-1)
+        vmag = mag("critic", c_dims, fc)[:, 0] + ret.abs() + (b["v_old"][sl].abs() if cv is not None else 0)
         sc += torch.stack([(adv.abs() * ratio * (1 + A)).sum(), (vmag * vmag).sum(), A.sum()])
         # the two networks, top layer down
-        for who, dims in (("actor", a_dims), ("critic", c_dims)):
-            delta, hs = delta_out[who], hs_all[who]
+        for who, dims, f, delta in (("actor", a_dims, fa, dlp[:, None] * z * inv), ("critic", c_dims, fc, (vc * inv_m * dv)[:, None])):
+            _, xs, norms, _ = f
             for l in range(len(dims) - 2, -1, -1):
                 W = p[f"{who}.{l}.weight"]
-                g[f"{who}.{l}.weight"] += delta.T @ hs[l]
+                g[f"{who}.{l}.weight"] += delta.T @ xs[l]
                 g[f"{who}.{l}.bias"] += delta.sum(0)
-                S[f"{who}.{l}.weight"] += delta.abs().T @ hs[l].abs()
+                S[f"{who}.{l}.weight"] += delta.abs().T @ xs[l].abs()
                 S[f"{who}.{l}.bias"] += delta.abs().sum(0)
-                if l > 0:
-                    delta = (delta @ W) * ((1 - hs[l] * hs[l]) if act == "tanh" else (hs[l] > 0).to(dtype))
+                if l == 0 and norms[0] is None:
+                    break
+                da, y = delta @ W, xs[l]
+                if norms[l] is not None:
+                    name, y, xhat, rstd = norms[l]
+                    g[name + ".weight"] += (da * xhat).sum(0)
+                    g[name + ".bias"] += da.sum(0)
+                    S[name + ".weight"] += (da * xhat).abs().sum(0)
+                    S[name + ".bias"] += da.abs().sum(0)
+                    if l == 0:
+                        break
+                    dxh = da if variant == "no_gamma" else da * p[name + ".weight"]
+                    m2 = (dxh * xhat).mean(-1, keepdim=True)
+                    da = rstd * (dxh - dxh.mean(-1, keepdim=True) - (0 if variant == "no_xhat_term" else xhat * m2))
+                delta = da * ((1 - y * y) if act == "tanh" else (y > 0).to(dtype))
     g["log_std"] = g["log_std"] + (ec if variant == "entropy_sign" else -ec)
     S["log_std"] = S["log_std"] + ec
     H = ls.sum() + 1.5 * (1 + LN2PI)
@@ -245,7 +249,7 @@ def adam_tolerances(p, m, v, g, step, lr, b1=0.9, b2=0.999, eps=1e-8, max_norm=N
 
 
 # ---- the synthetic trajectory -----------------------------------------------------------------------------------------------------------
-def kinks(params, a_dims, c_dims, act, b, cfg):
+def kinks(params, a_dims, c_dims, act, b, cfg, hidden=False, feat=False):
     """bool per row (float64): the row is within the margins of a kink of the loss"""
     p = {k: v.double() for k, v in params.items()}
     c, cv = cfg["clip"], cfg["value_clip"]
@@ -253,16 +257,10 @@ def kinks(params, a_dims, c_dims, act, b, cfg):
     bad = torch.zeros(obs.shape[0], dtype=torch.bool)
     outs = {}
     for who, dims in (("actor", a_dims), ("critic", c_dims)):
-        x = obs
-        for l in range(len(dims) - 1):
-            x = x @ p[f"{who}.{l}.weight"].T + p[f"{who}.{l}.bias"]
-            if l + 1 < len(dims) - 1:
-                if act == "relu":
-                    bad |= (x.abs() < 1e-4).any(-1)
-                    x = torch.relu(x)
-                else:
-                    x = torch.tanh(x)
-        outs[who] = x
+        outs[who], _, _, pres = forward(p, who, dims, act, obs, hidden, feat)
+        if act == "relu":
+            for pre in pres:
+                bad |= (pre.abs() < 1e-4).any(-1)
     ls = p["log_std"]
     z = (b["actions"].double() - outs["actor"]) * torch.exp(-ls)
     ratio = torch.exp((-0.5 * z * z - ls).sum(-1) - 1.5 * LN2PI - b["logp_old"].double())
@@ -275,12 +273,13 @@ def kinks(params, a_dims, c_dims, act, b, cfg):
     return bad
 
 
-def synth(net, shape, M, seed, pseed=None, extra_stride=8, guard=64):
+def synth(net, shape, M, seed, pseed=None, extra_stride=8, guard=64, dims=None, hidden=False, feat=False, weight_scale=1.0):
     """A seeded kink-free trajectory of `shape` = (N, A', T, D) for the network NETS[net], in mqe_ppo_grad's buffers, with at least M samples.
     Every one of the n = T N A' rows is drawn -- observation N(0, 1); action = mean64 + exp(log_std) N(0, 1); logp_old = logp64 + 0.25 N(0, 1)
     (ratios on both sides of 1 +- CLIP); adv N(0, 1); v_old = v64 + 0.3 N(0, 1) (both sides of VALUE_CLIP); ret = v64 + N(0, 1) -- and
     every row inside a kink margin (kinks(), with CLIP and VALUE_CLIP) is drawn again until none is left, so that ANY minibatch of it is
-    kink-free.  -> dict: params (float32 tensors), a_dims, c_dims, act, the logical float32 tensors obs (n, D), actions (n, 3), logp_old, v_old,
+    kink-free.  dims: (a_dims, c_dims, act) of a network that NETS does not hold; hidden, feat: with the norms, whose parameters join `params`;
+    weight_scale: rollout_ref.seeded_params'.  -> dict: params (float32 tensors), a_dims, c_dims, act, the logical float32 tensors obs (n, D), actions (n, 3), logp_old, v_old,
     adv, ret (n), index (a seeded int32 permutation of n), redraws (rows drawn again, in all), and the flat int32 images: `packed` ((T + 1)
     stride + guard words: the observations of rows 0 .. T in place, everything else the sentinel), `value` ((T + 1) R': v_old, then a filler
     row), `grad` (n_params + guard) and `stats` (6 + guard), both all sentinel."""
@@ -288,8 +287,9 @@ def synth(net, shape, M, seed, pseed=None, extra_stride=8, guard=64):
     R = N * Aw
     n = T * R
     assert n >= M
-    a_dims, c_dims, act = dims_of(net, D)
-    params = rollout_ref.seeded_params(a_dims, c_dims, 500 + seed if pseed is None else pseed)
+    a_dims, c_dims, act = dims or dims_of(net, D)
+    norms = dict(hidden=hidden, feat=feat)
+    params = rollout_ref.seeded_params(a_dims, c_dims, 500 + seed if pseed is None else pseed, hidden, feat, weight_scale)
     cfg = dict(clip=CLIP, value_clip=VALUE_CLIP)
     g = torch.Generator().manual_seed(seed)
     p64 = {k: v.double() for k, v in params.items()}
@@ -297,8 +297,8 @@ def synth(net, shape, M, seed, pseed=None, extra_stride=8, guard=64):
 
     def draw(k):
         obs = torch.randn(k, D, generator=g).float()
-        mean = _forward(p64, "actor", a_dims, act, obs.double())[-1]
-        v = _forward(p64, "critic", c_dims, act, obs.double())[-1][:, 0]
+        mean = forward(p64, "actor", a_dims, act, obs.double(), **norms)[0]
+        v = forward(p64, "critic", c_dims, act, obs.double(), **norms)[0][:, 0]
         actions = (mean + torch.exp(ls) * torch.randn(k, 3, generator=g).double()).float()
         z = (actions.double() - mean) * torch.exp(-ls)
         logp = (-0.5 * z * z - ls).sum(-1) - 1.5 * LN2PI
@@ -309,7 +309,7 @@ def synth(net, shape, M, seed, pseed=None, extra_stride=8, guard=64):
     b = draw(n)
     redraws = 0
     for _ in range(200):
-        bad = torch.nonzero(kinks(params, a_dims, c_dims, act, b, cfg))[:, 0]
+        bad = torch.nonzero(kinks(params, a_dims, c_dims, act, b, cfg, **norms))[:, 0]
         if len(bad) == 0:
             break
         redraws += len(bad)
@@ -326,11 +326,11 @@ def synth(net, shape, M, seed, pseed=None, extra_stride=8, guard=64):
     rows[:T, :nobs] = b["obs"].numpy().reshape(T, nobs).view(np.int32)
     rows[T, :nobs] = torch.randn(nobs, generator=g).float().numpy().view(np.int32)
     value = np.concatenate([b["v_old"].numpy(), torch.randn(R, generator=g).float().numpy()]).view(np.int32).copy()
-    n_params = abi.actor_param_count(a_dims, c_dims)
+    n_params = abi.actor_param_count(a_dims, c_dims, False, hidden, feat)
     out = lambda k: np.full(k + guard, SENT, np.int32)
     index = torch.randperm(n, generator=g).to(torch.int32)
     return dict(net=net, shape=shape, N=N, Aw=Aw, T=T, D=D, R=R, n=n, nobs=nobs, pf=pf, stride=stride, guard=guard, params=params, a_dims=a_dims,
-                c_dims=c_dims, act=act, n_params=n_params, index=index, redraws=redraws, packed=packed, value=value, grad=out(n_params),
+                c_dims=c_dims, act=act, **norms, n_params=n_params, index=index, redraws=redraws, packed=packed, value=value, grad=out(n_params),
                 stats=out(abi.PPO_STATS), **b)
 
 
@@ -341,14 +341,15 @@ def batch(s, sel):
     return {k: s[k][sel] for k in ("obs", "actions", "logp_old", "v_old", "adv", "ret")}
 
 
-def flat_grad(g, a_dims, c_dims):
+def flat_grad(g, a_dims, c_dims, hidden=False, feat=False):
     """{name: tensor} -> the engine's flat layout (float64)"""
-    flat = torch.zeros(abi.actor_param_count(a_dims, c_dims), dtype=torch.float64)
-    for name, (off, shape) in abi.actor_param_layout(a_dims, c_dims).items():
+    flat = torch.zeros(abi.actor_param_count(a_dims, c_dims, False, hidden, feat), dtype=torch.float64)
+    for name, (off, shape) in abi.actor_param_layout(a_dims, c_dims, False, hidden, feat).items():
         flat[off:off + int(np.prod(shape))] = g[name].reshape(-1).double()
     return flat
 
 
-def split_flat(flat, a_dims, c_dims):
+def split_flat(flat, a_dims, c_dims, hidden=False, feat=False):
     """the engine's flat layout -> {name: tensor}"""
-    return {name: flat[off:off + int(np.prod(shape))].reshape(shape) for name, (off, shape) in abi.actor_param_layout(a_dims, c_dims).items()}
+    layout = abi.actor_param_layout(a_dims, c_dims, False, hidden, feat)
+    return {name: flat[off:off + int(np.prod(shape))].reshape(shape) for name, (off, shape) in layout.items()}

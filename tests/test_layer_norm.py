@@ -29,7 +29,7 @@ def case(name, M, seed, **kw):
     if key not in _SYNTH:
         _SYNTH[key] = ref.synth(name, ppo_ref.shape_for(M), M, seed, **kw)
     s = _SYNTH[key]
-    return s, ref.args_of(s, s["index"][:M], CFG)
+    return (s, *ref.args_of(s, s["index"][:M], CFG))
 
 
 # ---- layout and constants ---------------------------------------------------------------------------------------------------------------------
@@ -178,10 +178,10 @@ def test_float64_norm_is_torch_layer_norm_and_the_float32_twin_is_near(n):
 @pytest.mark.parametrize("name", list(ref.CASES))
 def test_manual_float64_backward_is_autograd_of_the_stated_loss(name):
     cfg = dict(CFG, entropy_coef=0.03, value_coef=0.7)
-    s, args = case(name, 130, 1)
+    s, args, norms = case(name, 130, 1)
     args = args[:-1] + (cfg,)
-    g, st, S, _ = ref.manual(*args)
-    ga, sta = ref.autograd(*args, torch.float64)
+    g, st, S, _ = ppo_ref.manual(*args, **norms)
+    ga, sta = ppo_ref.autograd(*args, torch.float64, **norms)
     assert set(g) == set(ga) == set(ref.layout(s["a_dims"], s["c_dims"], s["hidden"], s["feat"]))
     for n in g:
         scale = max(float(ga[n].abs().max()), 1e-300)
@@ -190,10 +190,10 @@ def test_manual_float64_backward_is_autograd_of_the_stated_loss(name):
         if "norm" in n:
             assert float(ga[n].abs().max()) > 0, f"{n}: the case exercises this norm"
     assert float((st - sta).abs().max()) <= 1e-12 * float(sta.abs().max())
-    gt = ref.manual(*args, tile=64)[0]
+    gt = ppo_ref.manual(*args, tile=64, **norms)[0]
     assert all(float((gt[n] - g[n]).abs().max()) <= 1e-11 * max(float(g[n].abs().max()), 1e-300) for n in g)
     full = ppo_ref.batch(s, slice(None))
-    assert not bool(ref.kinks(s["params"], s["a_dims"], s["c_dims"], s["act"], s["hidden"], s["feat"], full, CFG).any()), "kink-free by the redraw rule"
+    assert not bool(ppo_ref.kinks(s["params"], s["a_dims"], s["c_dims"], s["act"], full, CFG, **norms).any()), "kink-free by the redraw rule"
 
 
 # ---- K ------------------------------------------------------------------------------------------------------------------------------------------------
@@ -202,10 +202,10 @@ def test_two_float32_evaluations_are_inside_k(name, M, seed):
     """torch float32 autograd on the whole batch and the float32 manual backward (the norm in the kernel's order) over 64-row tiles, against the
     float64 backward: every tensor inside K_LN_CPU 2^-24 S_n, every statistic inside K_LN_CPU 2^-24 of its scale; and the forward of the
     kernel-order twin inside 4x torch's float32 error (layer_norm_ref's docstring holds the measured table)"""
-    s, args = case(name, M, seed)
-    g64, st64, S, ss = ref.manual(*args)
-    ga, sta = ref.autograd(*args, torch.float32)
-    gm, stm, _, _ = ref.manual(*args, torch.float32, tile=64)
+    s, args, norms = case(name, M, seed)
+    g64, st64, S, ss = ppo_ref.manual(*args, **norms)
+    ga, sta = ppo_ref.autograd(*args, torch.float32, **norms)
+    gm, stm, _, _ = ppo_ref.manual(*args, torch.float32, tile=64, **norms)
     ra, na = ppo_ref.ratio_to_bound(ga, g64, S)
     rm, nm = ppo_ref.ratio_to_bound(gm, g64, S)
     sa, sm = ppo_ref.stats_ratio(sta, st64, ss), ppo_ref.stats_ratio(stm, st64, ss)
@@ -213,11 +213,11 @@ def test_two_float32_evaluations_are_inside_k(name, M, seed):
     assert max(ra, rm, sa, sm) <= ref.K_LN_CPU
     assert ref.K_LN_GPU == 4 * ref.K_LN_CPU
     if M >= 63:
-        obs = args[6]["obs"]
+        obs = args[4]["obs"]
         e = ref.forward_errors(s["params"], s["a_dims"], s["c_dims"], s["act"], s["hidden"], s["feat"], obs)
         p32 = {k: v.float() for k, v in s["params"].items()}
         for who, dims, key in (("actor", s["a_dims"], "mean"), ("critic", s["c_dims"], "value")):
-            y = ref.forward(p32, who, dims, s["act"], s["hidden"], s["feat"], obs.float(), kernel_order=True)[0].double()
+            y = ref.forward(p32, who, dims, s["act"], obs.float(), kernel_order=True, **norms)[0].double()
             y = y if key == "mean" else y[..., 0]
             assert float((y - e[key + "64"]).abs().max()) <= 4 * e["yard_" + key], (who, "the kernel-order twin against the forward yardstick")
 
@@ -226,14 +226,14 @@ def test_two_float32_evaluations_are_inside_k(name, M, seed):
 def test_wrong_norms_are_far_outside(variant):
     """16 -> 7 / 17 with the hidden norm, layer 0 scaled by 0.01 so that a row's variance is of the size of eps (where `eps outside the root`
     differs), M = 1000: each wrong variant misses K_LN_GPU 2^-24 S_n by more than 100x in at least one tensor"""
-    s, args = case("tanh7_17", 1000, 0, weight_scale=0.01)
-    g64, _, S, _ = ref.manual(*args)
-    ok = ref.manual(*args, torch.float32, tile=64)[0]
+    s, args, norms = case("tanh7_17", 1000, 0, weight_scale=0.01)
+    g64, _, S, _ = ppo_ref.manual(*args, **norms)
+    ok = ppo_ref.manual(*args, torch.float32, tile=64, **norms)[0]
     assert ppo_ref.ratio_to_bound(ok, g64, S)[0] <= ref.K_LN_CPU, "the right float32 evaluation of these inputs is inside"
     if variant in ref.VARIANTS_FORWARD:
-        bad = ref.autograd(*args, torch.float32, variant=variant)[0]
+        bad = ppo_ref.autograd(*args, torch.float32, variant=variant, **norms)[0]
     else:
-        bad = ref.manual(*args, torch.float32, tile=64, variant=variant)[0]
+        bad = ppo_ref.manual(*args, torch.float32, tile=64, variant=variant, **norms)[0]
     r, at = ppo_ref.ratio_to_bound(bad, g64, S)
     print(f"ln_wrong {variant}: {r:.3g} x 2^-24 S at {at} = {r / ref.K_LN_GPU:.0f} x the GPU bound")
     assert r > 100 * ref.K_LN_GPU, variant

@@ -22,7 +22,7 @@ from test_ppo_gpu import upload, call, outputs
 
 pytestmark = pytest.mark.gpu
 
-EPS32 = ref.EPS32
+EPS32 = ppo_ref.EPS32
 TASK, N, D, AW, T = "go1gate", 33, 16, 2, 2
 CFG = dict(clip=ref.CLIP, value_coef=0.7, entropy_coef=0.01, value_clip=ref.VALUE_CLIP)
 _HANDLE, _SYNTH, _REF = [], {}, {}
@@ -54,9 +54,11 @@ def install(eng, s, **kw):
 def reference(s, sel, key):
     """float64 gradient (flat), statistics and their bounds K_LN_GPU 2^-24 S_n / scale of a minibatch"""
     if key not in _REF:
-        g64, st64, S, ss = ref.manual(*ref.args_of(s, sel, CFG))
-        bound = ref.flat_grad({n: torch.full_like(g64[n], S[n]) for n in g64}, s) * (ref.K_LN_GPU * EPS32)
-        _REF[key] = (ref.flat_grad(g64, s), st64, bound, ss * (ref.K_LN_GPU * EPS32))
+        args, norms = ref.args_of(s, sel, CFG)
+        g64, st64, S, ss = ppo_ref.manual(*args, **norms)
+        flat = lambda g: ppo_ref.flat_grad(g, s["a_dims"], s["c_dims"], **norms)
+        bound = flat({n: torch.full_like(g64[n], S[n]) for n in g64}) * (ref.K_LN_GPU * EPS32)
+        _REF[key] = (flat(g64), st64, bound, ss * (ref.K_LN_GPU * EPS32))
     return _REF[key]
 
 
@@ -119,7 +121,7 @@ def test_gradient_against_float64_and_same_bits(case):
         torch.cuda.synchronize()
         assert torch.equal(t["grad"], u["grad"]) and torch.equal(t["stats"], u["stats"]), "two calls on the same inputs differ"
         n = s["n_params"]
-        assert bool((t["grad"][n:] == ref.SENT).all()) and not bool((t["grad"][:n] == ref.SENT).any()), "guard touched or an element unwritten"
+        assert bool((t["grad"][n:] == ppo_ref.SENT).all()) and not bool((t["grad"][:n] == ppo_ref.SENT).any()), "guard touched or an element unwritten"
         sel = s["index"][first:first + M] if use_index else torch.arange(first, first + M)
         grad, stats = outputs(s, t)
         g64, st64, bound, sbound = reference(s, sel, (case, M, first, use_index))

@@ -84,8 +84,8 @@ def test_generator_guarantees(net, M):
     full = ref.batch(s, slice(None))
     assert not bool(ref.kinks(s["params"], s["a_dims"], s["c_dims"], s["act"], full, CFG).any()), "every row is outside the kink margins"
     p64 = {k: v.double() for k, v in s["params"].items()}
-    mean = ref._forward(p64, "actor", s["a_dims"], s["act"], b["obs"].double())[-1]
-    v = ref._forward(p64, "critic", s["c_dims"], s["act"], b["obs"].double())[-1][:, 0]
+    mean = ref.forward(p64, "actor", s["a_dims"], s["act"], b["obs"].double())[0]
+    v = ref.forward(p64, "critic", s["c_dims"], s["act"], b["obs"].double())[0][:, 0]
     z = (b["actions"].double() - mean) * torch.exp(-p64["log_std"])
     ratio = torch.exp((-0.5 * z * z - p64["log_std"]).sum(-1) - 1.5 * ref.LN2PI - b["logp_old"].double())
     adv, vo, ret = b["adv"].double(), b["v_old"].double(), b["ret"].double()

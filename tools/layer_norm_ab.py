@@ -8,11 +8,17 @@ go1gate 4096 envs x 2 agents, T = 200, two 64 x 64 tanh networks.
   --parent LIB   starts NO GPU work itself: alternates child processes --rounds times -- this tool --plain-only and `bench.py --gpus 1` -- once
               with the in-tree library and once with MQE_HIP_LIB=LIB (a build of the parent commit), and prints per path the medians of both and
               their spread.  The plain path is expected inside the alternating windows' own spread of the parent.
+  --all-paths    with --parent: the children run without --plain-only, for a parent library that has the norm kernels too: all four paths
+              (rollout and epoch, plain and with norms) for both libraries.
+Every measuring child first prints, per handle, LAYER_NORM_DIGEST: the SHA-256 of the bytes of the handle's first rollout (fixed seeds; actions,
+logp, value) and of one ppo_grad on it (grad, stats), taken before any timing, while the handle is as created.  --parent prints whether the two
+libraries' digests are equal: the same bits, which the tests' float64 bounds do not show.
   --trace-only   warm-up and seven rollout steps / gradient calls on the handle with the switches and nothing else: the run to put under
               `rocprofv3 --kernel-trace --stats -- python tools/layer_norm_ab.py --trace-only` for the kernels' own times.
 Every figure of the first two modes is a HIP-event time (events recorded on the stream around a window, synchronised after it); all paths are
 warmed up.  --out FILE: the printed lines go to that file as well (profiles/layer_norm.txt keeps one run)."""
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -63,6 +69,16 @@ def measure(a, say):
         traj = eng.gae(eng.rollout(T, time_outs=True), 0.99, 0.95, normalize=True)
         handles[kind] = (env, eng, traj)
     total = T * a.envs * 2
+    digest = {}
+    for kind, (_, eng, traj) in ({} if a.trace_only else handles).items():      # the first rollout of a fresh handle and one gradient on it: before anything is timed or updated
+        grad, stats = eng.ppo_grad(traj, first=0, count=total // mb, **kw)
+        torch.cuda.synchronize()
+        h = hashlib.sha256()
+        for t in (traj.actions, traj.logp, traj.value, grad, stats):
+            h.update(t.detach().cpu().contiguous().numpy().tobytes())
+        digest[kind] = h.hexdigest()
+    if digest:
+        print("LAYER_NORM_DIGEST " + json.dumps(digest), flush=True)
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -115,12 +131,12 @@ def measure(a, say):
 def against_parent(a, say):
     """child processes only: the in-tree library and the parent's, alternated"""
     me = os.path.abspath(__file__)
-    jobs = {"tool": [sys.executable, me, "--plain-only", "--envs", str(a.envs), "--T", str(a.T), "--rounds", str(a.rounds), "--minibatches", str(a.minibatches)],
+    jobs = {"tool": [sys.executable, me, *([] if a.all_paths else ["--plain-only"]), "--envs", str(a.envs), "--T", str(a.T), "--rounds", str(a.rounds), "--minibatches", str(a.minibatches)],
             "bench": [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(a.bench_steps), "--warmup", "50", "--no_cpu_baseline",
                       "--no_strict_f32", "--no_configs"]}
-    got = {}
+    got, digests = {}, {}
     for r in range(a.parent_rounds):
-        for lib in ("in-tree", "parent"):
+        for lib in (("in-tree", "parent") if r % 2 == 0 else ("parent", "in-tree")):      # neither library always goes first
             env = dict(os.environ)
             env.pop("MQE_HIP_LIB", None)
             if lib == "parent":
@@ -131,19 +147,24 @@ def against_parent(a, say):
                     say(f"{job} with the {lib} library ended with {out.returncode}: {out.stderr[-400:]}")
                     return 1
                 if job == "tool":
+                    digests.setdefault(lib, set()).add(next(l for l in out.stdout.splitlines() if l.startswith("LAYER_NORM_DIGEST ")))
                     line = next(l for l in out.stdout.splitlines() if l.startswith("LAYER_NORM_AB "))
                     for n, v in json.loads(line[len("LAYER_NORM_AB "):]).items():
                         got.setdefault((n, lib), []).append(v)
                 else:
                     res = json.loads(next(l for l in reversed(out.stdout.splitlines()) if l.startswith("{")))
                     got.setdefault(("bench.py ms_per_step", lib), []).append(res["ms_per_step"])
-    say(f"plain path, in-tree library against {a.parent}: {a.parent_rounds} alternated child processes each")
+    say(f"{'all four paths' if a.all_paths else 'plain path'}, in-tree library against {a.parent}: {a.parent_rounds} alternated child processes each")
+    for lib, lines in digests.items():
+        say(f"{lib:8s} {' | '.join(sorted(lines))}")
+    same = len(digests["in-tree"]) == 1 and digests["in-tree"] == digests["parent"]
+    say("digests of the in-tree and the parent library: " + ("EQUAL in every child, for every handle" if same else "DIFFERENT"))
     for n in sorted({n for n, _ in got}):
         mine, base = got[(n, "in-tree")], got[(n, "parent")]
         m, b = statistics.median(mine), statistics.median(base)
         say(f"{n:34s} in-tree median {m:10.4f} ({min(mine):.4f} .. {max(mine):.4f})   parent median {b:10.4f} ({min(base):.4f} .. {max(base):.4f})   "
             f"{(m / b - 1) * 100:+.2f} %, the parent's own spread {spread(base):.2f} %")
-    return 0
+    return 0 if same else 1
 
 
 def main():
@@ -156,6 +177,7 @@ def main():
     ap.add_argument("--plain-only", action="store_true")
     ap.add_argument("--trace-only", action="store_true")
     ap.add_argument("--parent", default=None, metavar="LIB")
+    ap.add_argument("--all-paths", action="store_true")
     ap.add_argument("--parent-rounds", type=int, default=3)
     ap.add_argument("--bench-steps", type=int, default=300)
     ap.add_argument("--child-timeout", type=int, default=300)
