@@ -942,9 +942,15 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
       /* bias accelerations (all generalized accelerations zero) */
       real aq[3] = {bk[b].a[0] * qdj, bk[b].a[1] * qdj, bk[b].a[2] * qdj};
       cross3(bk[pb].w, aq, t);
+#if MQO_DEFECT == 3      /* defect build (Makefile: defects; tests/test_substep_ref.py): no w x (a qd) in the link's angular bias */
+      t[0] = t[1] = t[2] = 0;
+#endif
       for (int k = 0; k < 3; k++) bk[b].al[k] = bk[pb].al[k] + t[k];
       cross3(bk[pb].al, dd, t);
       real wd[3]; cross3(bk[pb].w, dd, wd); cross3(bk[pb].w, wd, t2);
+#if MQO_DEFECT == 2      /* defect build: no centripetal term w x (w x d) of the joint offsets */
+      t2[0] = t2[1] = t2[2] = 0;
+#endif
       for (int k = 0; k < 3; k++) bk[b].ap[k] = bk[pb].ap[k] + t[k] + t2[k];
     }
     for (int b = 0; b < NB; b++) {
@@ -987,6 +993,11 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
       cross3(bk[b].al, rc, t); cross3(bk[b].w, rc, wr); cross3(bk[b].w, wr, t2);
       for (int k = 0; k < 3; k++) { ac[k] = bk[b].ap[k] + t[k] + t2[k]; f[k] = mb * (ac[k] - g[k]); }
       mat3_vec(bk[b].Iw, bk[b].w, Iw_); cross3(bk[b].w, Iw_, t); mat3_vec(bk[b].Iw, bk[b].al, Ial);
+#if MQO_DEFECT == 1      /* defect build: no gyroscopic term w x I w, on any body */
+      t[0] = t[1] = t[2] = 0;
+#elif MQO_DEFECT == 4    /* defect build: no gyroscopic term on ONE link (body 3) */
+      if (b == 3) t[0] = t[1] = t[2] = 0;
+#endif
       for (int k = 0; k < 3; k++) nn[k] = Ial[k] + t[k];
       for (int i = 0; i < RD; i++) h[i] += dot3(Jv[i], f) + dot3(Jw[i], nn);
     }
