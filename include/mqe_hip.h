@@ -39,7 +39,9 @@ extern "C" {
  * MQE_GAE_NORMALIZE; mqe_ppo_grad, mqe_ppo_optimizer and mqe_ppo_adam (new exports), mqe_ppo_loss, MQE_PPO_*; value normalisation: no export
  * and no prototype changes -- MQE_ACTOR_VALUE_NORM (a bit of mqe_actor_shape.activation above the kind byte), MQE_VALUE_NORM_STATE,
  * MQE_GAE_VALUE_NORM, MQE_PPO_VALUE_NORM and MQE_PPO_VALUE_NORM_UPDATE (flag bits that were refused as unknown before); layer normalisation:
- * likewise -- MQE_ACTOR_LAYER_NORM and MQE_ACTOR_FEATURE_NORM (bits 2 and 4 of the kind byte of mqe_actor_shape.activation, refused before). */
+ * likewise -- MQE_ACTOR_LAYER_NORM and MQE_ACTOR_FEATURE_NORM (bits 2 and 4 of the kind byte of mqe_actor_shape.activation, refused before); the
+ * recurrent actor-critic: likewise -- MQE_ACTOR_RECURRENT (bit 16 of the kind byte, refused before), MQE_ROLLOUT_HIDDEN_IN and
+ * MQE_ROLLOUT_HIDDEN_RECORD (mqe_rollout flags 2 and 4, ignored before). */
 #define MQE_ABI_VERSION 17
 #define MQE_MAX_SPHERES 64    /* feature points of one robot (the capsule model has 32, the exact one 60) */
 #define MQE_MAX_PRIMS 20      /* collision primitives of one robot (Go1: 18) */
@@ -615,6 +617,42 @@ int mqe_ppo_adam(mqe_sim* s, const float* grad_dev, long long step, float lr, fl
  *   dxhat = du * gamma;  da = rstd * (dxhat - mean(dxhat) - xhat * mean(dxhat * xhat));  then the activation's derivative.
  * No atomics: the same bits on every run.  Every shape mqe_actor_create accepts without the bits it accepts with them (D up to 128 included);
  * k_ln_grad's LDS rule (csrc/kernels_ln.hpp) takes 32-row tiles earlier than k_ppo_grad's. */
+
+/* ---- Recurrent actor-critic: a GRU cell in the rollout's networks, its state carried and recorded (csrc/kernels_gru.hpp: k_actor_gru, k_actor_gru_ln) ----
+ * v17, additive: no prototype, no struct and no #define of this header changes.  OpenRL's PPONet with use_recurrent_policy is MAPPO's: behind the
+ * MLP base a one-layer GRU(H, H) and, with the norms, a LayerNorm(H); then the linear head; the state is zeroed wherever the step before ended an
+ * episode.  THE THREE CONSTANTS BELOW ARE NOT #DEFINED BY THIS HEADER (tests/test_rollout.py pins the exact sets of MQE_ACTOR_* and MQE_ROLLOUT_*
+ * defines).  Their values are stated here, defined under these names in csrc/kernels_gru.hpp (which the engine compiles) and mirrored in
+ * mqe/engine/abi.py; tests/test_gru.py holds the three statements together.  A C caller passes the numbers.
+ *   MQE_ACTOR_RECURRENT = 16   MQE_ROLLOUT_HIDDEN_IN = 2   MQE_ROLLOUT_HIDDEN_RECORD = 4
+ * MQE_ACTOR_RECURRENT is a bit of the KIND BYTE of mqe_actor_shape.activation and combines freely with the kinds, the two norm bits and the
+ *   value-normalisation bit; bits 8 and 512 stay refused.  It applies to both networks; each needs at least 2 Linear layers (-6 naming
+ *   actor_layers / critic_layers otherwise).  With H the width of a network's last hidden layer, a cell H -> H sits between that layer's output
+ *   (behind its hidden norm, when there is one) and the output Linear; under the hidden norm a LayerNorm(H, eps = 1e-5) follows the cell.  The cell
+ *   is torch.nn.GRU's, gate order r, z, n, all f32 (rounding points: csrc/kernels_gru.hpp, restated by tests/gru_ref.py):
+ *     gi = W_ih x + b_ih;  gh = W_hh h + b_hh;  r = sigmoid(gi_r + gh_r);  z = sigmoid(gi_z + gh_z);  n = tanh(gi_n + r gh_n);  h' = (1 - z) n + z h
+ * Parameter buffer, per network, in front of the output layer's weight: gru.weight_ih (3H, H), gru.weight_hh (3H, H), gru.bias_ih (3H),
+ *   gru.bias_hh (3H) and, under the hidden norm, gru.norm.weight (H) -- created as 1 -- and gru.norm.bias (H).  With the bit clear the layout is
+ *   the one it was, bit for bit.  n_params, mqe_ppo_optimizer and mqe_ppo_adam cover the cell like any weight.
+ * State: [R'][Hs] floats owned by the engine, Hs = Ha + Hc (the cells' widths; Hc = 0 without a critic), row r = the actor's Ha floats, then the
+ *   critic's; made zeroed by mqe_actor_create, released with the actor, NOT part of mqe_state_save (a learner checkpoints the recorded state).
+ *   The TAIL of a packed row is the R' Hs floats at offset P4 = the MQE_T_WRAPPER_PACKED length rounded up to a multiple of 4.
+ * mqe_rollout on a recurrent handle: step t is evaluated from h_in(t) = state * (1 - done) with done the byte of the row's env in packed row t
+ *   (row 0's are zeroed: step 0 never masks; all agents of an env reset together; a masked state is exactly 0.0f); afterwards the live state, and row
+ *   t + 1's tail when recorded, hold h'(t) UNMASKED -- the mask is in that row's own done bytes: OpenRL's (rnn_states[t], masks[t]).  The launch
+ *   behind the last step is always enqueued: it masks the live state with row T's done bytes, writes value[T] from the masked critic state when
+ *   value_dev is given, and advances nothing; a following call continues from it.  The critic's state advances whether or not value_dev is given.
+ *   MQE_ROLLOUT_HIDDEN_IN      the start state is read from row 0's tail (written by the caller) instead of the live state
+ *   MQE_ROLLOUT_HIDDEN_RECORD  the tails of rows 0 .. T are written, row 0's with the state the call started from; no other float beyond the packed layout
+ *   With either flag row_stride >= P4 + R' Hs (still a multiple of 4), -6 naming row_stride otherwise; either flag on a handle without the bit: -6
+ *   naming flags.  Without the flags tails are neither read nor written and the rule for row_stride is the old one.  Refusals enqueue nothing.
+ * Resets that happen in mqe_step calls between rollouts are not seen by the state: it is masked by the done bytes of trajectory rows only.
+ * mqe_gae, mqe_ppo_optimizer, mqe_ppo_adam and mqe_rollout_time_outs work unchanged.  mqe_ppo_grad REFUSES a recurrent handle (-6, nothing enqueued or
+ *   written): back-propagation through time is not built in the engine yet -- the next step; until then a learner differentiates the torch twin
+ *   (mqe.utils.actor_net.RecurrentMLP) over the recorded trajectory and copies the parameters back, or hands mqe_ppo_adam a gradient in this layout.
+ * mqe_actor_create refuses (-6, naming the width) a recurrent shape whose LDS need, (2 max layer input + 4 + Ha + Hc, + 32 with a norm) rows of 260
+ *   bytes, exceeds the 160 KiB of a workgroup; every shape with all widths and obs_dim <= 128 fits.  A handle created without the bit launches
+ *   exactly the kernels it launched before. */
 
 /* The onboard forward depth camera of LeggedRobotField (legged_robot_field.py:23-93: create_camera_sensor + attach_camera_to_body on the
  * base link, :196-223: get_camera_image_gpu_tensor(IMAGE_DEPTH)) for every robot, from the CURRENT state: out_dev [R][height][width]

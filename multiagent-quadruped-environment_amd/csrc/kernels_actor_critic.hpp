@@ -1,5 +1,6 @@
-// kernels_actor_critic.hpp -- the network walks of the engine's actor-critic and the four entry points built on them: k_actor / k_actor_ln (the
-// rollout's actor, mqe_rollout) and k_ppo_grad<RT> / k_ln_grad<RT> (the PPO gradient, mqe_ppo_grad).  Each walk is stated once, with the layer norm a
+// kernels_actor_critic.hpp -- the network walks of the engine's actor-critic and the entry points built on them: k_actor / k_actor_ln and, with a
+// GRU cell in front of the output layer (kernels_gru.hpp; the compile-time parameter GRU), k_actor_gru / k_actor_gru_ln (the rollout's actor,
+// mqe_rollout) and k_ppo_grad<RT> / k_ln_grad<RT> (the PPO gradient, mqe_ppo_grad).  Each walk is stated once, with the layer norm a
 // compile-time parameter LN: the LN = false instantiation contains no norm code and reads neither the switches nor the 1 / n arrays.  The primitives
 // are in kernels_actor.hpp (one layer, the observation load, the draw) and kernels_ppo.hpp (the tile load, the loss heads, ppo_dw, ppo_dx); the norm
 // is in kernels_ln.hpp.  The entry points do nothing but call the body: their names are what a kernel trace shows of the path that ran.
@@ -19,12 +20,16 @@
 #include "kernels_actor.hpp"
 #include "kernels_ppo.hpp"
 #include "kernels_ln.hpp"
+#include "kernels_gru.hpp"
 
-// ---- k_actor / k_actor_ln ---------------------------------------------------------------------------------------------------------------------------
-// a whole network: observation in bufB; result (last layer, linear) -> out[j * ACT_LD + row].  LN: the two buffers are normalised in place
-template <bool LN>
+// ---- k_actor / k_actor_ln / k_actor_gru / k_actor_gru_ln ---------------------------------------------------------------------------------------------
+// a whole network: observation in bufB; result (last layer, linear) -> out[j * ACT_LD + row].  LN: the two buffers are normalised in place.
+// GRU (kernels_gru.hpp): the cell sits in front of the last layer.  h: the network's masked state in LDS; h' goes to the free buffer, is copied over h
+// when the launch advances the state (keep), and is normalised into the other buffer under the hidden norm: the last layer reads it from there
+template <bool LN, bool GRU = false>
 __device__ __forceinline__ void actor_net(const ActorNet& net, const float* inv_n, int hidden, int feat, const float* __restrict__ params, float* bufA,
-                                          float* bufB, float* out, float* part, int lane, int wave, int hidden_act) {
+                                          float* bufB, float* out, float* part, int lane, int wave, int hidden_act, float* h = nullptr, bool keep = false,
+                                          int tid = 0) {
   if constexpr (LN) {
     if (feat) {
       const float* g = params + ln_gamma_off(net, 0);
@@ -35,6 +40,23 @@ __device__ __forceinline__ void actor_net(const ActorNet& net, const float* inv_
   float* y = bufA;
   for (int l = 0; l < net.n_layers; l++) {
     const bool last = l + 1 == net.n_layers;
+    if constexpr (GRU) {
+      if (last) {
+        const int H = net.dims[l];
+        const int go = gru_layer(net, l, hidden, params, x, h, y, lane, wave);
+        __syncthreads();
+        if (keep)
+          for (int e = tid; e < H * ACT_LD; e += ACT_THREADS) h[e] = y[e];      // read again only behind the last layer's barrier
+        float* t = const_cast<float*>(x); x = y; y = t;
+        if constexpr (LN) {
+          if (hidden) {
+            const float* g = params + go;
+            ln_rows<ACT_LD>(x, y, H, g, g + H, inv_n[l], part, nullptr, lane, wave);
+            x = y;
+          }
+        }
+      }
+    }
     actor_layer_of<ACT_LD>(net, l, params, x, last ? out : y, lane, wave, hidden_act);
     __syncthreads();
     if constexpr (LN) {
@@ -48,34 +70,60 @@ __device__ __forceinline__ void actor_net(const ActorNet& net, const float* inv_
   }
 }
 
-template <bool LN>
-__device__ __forceinline__ void actor_body(const ActorArgs& a) {
+// GRU: the state of both networks sits behind the partial rows, [Ha + Hc][ACT_LD], loaded masked in front of the networks and stored behind
+// actor_finish, the last reader of a parameter.  The critic of a recurrent handle runs whether or not its value is asked for: its state advances
+// gparams / gsh: the parameter buffer and the shapes as __restrict__ kernel arguments of the recurrent entry points (kernels_gru.hpp, SCALAR WEIGHT LOADS)
+template <bool LN, bool GRU = false>
+__device__ __forceinline__ void actor_body(const ActorArgs& a, const GruArgs& gr, const float* __restrict__ gparams = nullptr, const ActorShapes* __restrict__ gsh = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float act_lds[];
   float* bufA = act_lds;
   float* bufB = act_lds + (size_t)a.ldh * ACT_LD;
   float* out = act_lds + (size_t)2 * a.ldh * ACT_LD;       // [4][ACT_LD]: mean 0..2, value
   float* part = LN ? out + 4 * ACT_LD : nullptr;           // [LN_PART][ACT_LD]
+  float* hs = GRU ? out + (4 + (LN ? LN_PART : 0)) * ACT_LD : nullptr;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int row0 = blockIdx.x * ACT_ROWS;
   const int hidden_act = a.relu ? 2 : 1;
-  const int hidden = LN ? a.sh.hidden : 0, feat = LN ? a.sh.feat : 0;
+  const ActorShapes& shp = GRU ? *gsh : a.sh;
+  const int hidden = LN ? shp.hidden : 0, feat = LN ? shp.feat : 0;
   const bool sample = a.actions != nullptr;                // false: the value-only launch behind the last step
+  if constexpr (GRU) gru_load_state(gr.state, gr.done, row0, a.rows, a.Aw, gr.Ha + gr.Hc, hs, tid);      // the observation load's barrier covers it
   if (sample) {
     actor_load_obs(a.obs, row0, a.rows, a.D, bufB, tid);
     __syncthreads();
-    actor_net<LN>(a.sh.actor, a.sh.inv_actor, hidden, feat, a.params, bufA, bufB, out, part, lane, wave, hidden_act);
+    if constexpr (GRU) actor_net<LN, true>(gsh->actor, gsh->inv_actor, hidden, feat, gparams, bufA, bufB, out, part, lane, wave, hidden_act, hs, true, tid);
+    else actor_net<LN>(a.sh.actor, a.sh.inv_actor, hidden, feat, a.params, bufA, bufB, out, part, lane, wave, hidden_act);
   }
-  const bool critic = a.sh.critic.n_layers > 0 && a.value != nullptr;
+  bool critic = a.sh.critic.n_layers > 0 && a.value != nullptr;
+  if constexpr (GRU) critic = gr.Hc > 0 && (sample || a.value != nullptr);
   if (critic) {
     actor_load_obs(a.obs, row0, a.rows, a.D, bufB, tid);
     __syncthreads();
-    actor_net<LN>(a.sh.critic, a.sh.inv_critic, hidden, feat, a.params, bufA, bufB, out + 3 * ACT_LD, part, lane, wave, hidden_act);
+    if constexpr (GRU)
+      actor_net<LN, true>(gsh->critic, gsh->inv_critic, hidden, feat, gparams, bufA, bufB, out + 3 * ACT_LD, part, lane, wave, hidden_act,
+                          hs + (size_t)gr.Ha * ACT_LD, sample, tid);
+    else actor_net<LN>(a.sh.critic, a.sh.inv_critic, hidden, feat, a.params, bufA, bufB, out + 3 * ACT_LD, part, lane, wave, hidden_act);
   }
-  if (wave != 0) return;
-  actor_finish(a, out, sample, critic, row0, lane);
+  if constexpr (GRU) {
+    if (wave == 0) actor_finish(a, out, sample, critic && a.value != nullptr, row0, lane);
+    __syncthreads();       // a launch without a network to walk has had no barrier behind the state's load
+    gru_store_state(hs, gr.state, row0, a.rows, gr.Ha + gr.Hc, tid);
+    if (sample && gr.record != nullptr) gru_store_state(hs, gr.record, row0, a.rows, gr.Ha + gr.Hc, tid);
+  } else {
+    if (wave != 0) return;
+    actor_finish(a, out, sample, critic, row0, lane);
+  }
 }
+template <bool LN>
+__device__ __forceinline__ void actor_body(const ActorArgs& a) { actor_body<LN, false>(a, GruArgs{}); }
 __global__ void __launch_bounds__(ACT_THREADS) k_actor(ActorArgs a) { actor_body<false>(a); }
 __global__ void __launch_bounds__(ACT_THREADS) k_actor_ln(ActorArgs a) { actor_body<true>(a); }
+extern "C" __global__ void __launch_bounds__(ACT_THREADS) k_actor_gru(ActorArgs a, GruArgs g, const float* __restrict__ params, const ActorShapes* __restrict__ sh) {
+  actor_body<false, true>(a, g, params, sh);
+}
+extern "C" __global__ void __launch_bounds__(ACT_THREADS) k_actor_gru_ln(ActorArgs a, GruArgs g, const float* __restrict__ params, const ActorShapes* __restrict__ sh) {
+  actor_body<true, true>(a, g, params, sh);
+}
 
 // ---- k_ppo_grad / k_ln_grad -------------------------------------------------------------------------------------------------------------------------
 // forward of one network with every layer output kept: observation at lds[0], hidden output l behind it at (sum of the widths below it) rows, the

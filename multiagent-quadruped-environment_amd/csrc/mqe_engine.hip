@@ -24,6 +24,7 @@
 #include "kernels_ppo.hpp"
 #include "kernels_vn.hpp"
 #include "kernels_ln.hpp"
+#include "kernels_gru.hpp"
 #include "kernels_actor_critic.hpp"
 
 static thread_local char g_err[512] = "";
@@ -132,6 +133,12 @@ struct mqe_sim {
     bool ln() const { return sh.hidden || sh.feat; }      // MQE_ACTOR_LAYER_NORM / MQE_ACTOR_FEATURE_NORM: either one selects k_actor_ln and k_ln_grad
     float* params = nullptr;      // [n_params (+ MQE_VALUE_NORM_STATE)]
     float* stage = nullptr;       // [N, A', 3]
+    // MQE_ACTOR_RECURRENT (kernels_gru.hpp): the widths of the two GRU cells and the live state [N A'][Ha + Hc], made zeroed with the actor and
+    // released with it; selects k_actor_gru / k_actor_gru_ln.  The actor's, like Adam's moments: never in state_bufs
+    bool gru = false;
+    int Ha = 0, Hc = 0;
+    float* hstate = nullptr;
+    ActorShapes* nets = nullptr;      // the shapes on the device, as the recurrent kernels read them (their kernel arguments stay short)
   } act;
   // value normalisation (kernels_vn.hpp): the de-normalised values of mqe_gae [(T + 1) R'], the normalised targets of mqe_ppo_grad [T R'] and
   // k_vn_moments' partials; made by the first flagged call, grown when T grows, the actor's like the Ppo scratch
@@ -1555,9 +1562,11 @@ static void view_1d_f32(mqe_tensor_view* v, float* p, int n) {
 
 // ---- on-device rollouts: mqe_actor_create / mqe_actor_params / mqe_rollout (include/mqe_hip.h) ---------------------------------
 // one network's dims[] against the limits; fills its offsets into the flat parameter buffer from *off on
-static int actor_net_shape(const char* who, int layers, const int32_t* dims, int in, int out, bool ln_hidden, bool ln_feat, ActorNet* net, float* inv_n,
-                           int* off, int* ldh) {
+static int actor_net_shape(const char* who, int layers, const int32_t* dims, int in, int out, bool ln_hidden, bool ln_feat, bool gru, ActorNet* net,
+                           float* inv_n, int* off, int* ldh) {
   if (layers < 1 || layers > MQE_ACTOR_MAX_LAYERS) return fail(-6, "mqe_actor_create: %s: 1 .. 4 Linear layers (MQE_ACTOR_MAX_LAYERS)", who);
+  if (gru && layers < 2)
+    return fail(-6, "mqe_actor_create: %s_layers: MQE_ACTOR_RECURRENT needs at least 2 Linear layers (the GRU cell sits between the last hidden layer and the output)", who);
   if (dims[0] != in) return fail(-6, "mqe_actor_create: %s: dims[0] must be obs_dim", who);
   if (dims[layers] != out) return fail(-6, "mqe_actor_create: %s: the last width must be 3 for the actor (the mean) and 1 for the critic", who);
   net->n_layers = layers;
@@ -1568,6 +1577,7 @@ static int actor_net_shape(const char* who, int layers, const int32_t* dims, int
   }
   if (ln_feat) *off += 2 * dims[0];                       // norm_in.weight, norm_in.bias
   for (int l = 0; l < layers; l++) {
+    if (gru && l + 1 == layers) *off += gru_param_floats(dims[l], ln_hidden);      // the cell's block in front of the output layer's weight
     net->w_off[l] = *off;
     *off += dims[l] * dims[l + 1] + dims[l + 1];
     if (ln_hidden && l + 1 < layers) *off += 2 * dims[l + 1];      // norm.weight, norm.bias behind a hidden layer
@@ -1582,7 +1592,7 @@ static void dfree(mqe_sim* s, void* p) {
   hipFree(p);           // waits for the launches that still read it
 }
 static void actor_release(mqe_sim* s) {
-  for (void* p : {(void*)s->act.params, (void*)s->act.stage, (void*)s->ppo.part, (void*)s->ppo.pst, (void*)s->ppo.nets, (void*)s->ppo.moments, (void*)s->ppo.norm,
+  for (void* p : {(void*)s->act.params, (void*)s->act.stage, (void*)s->act.hstate, (void*)s->act.nets, (void*)s->ppo.part, (void*)s->ppo.pst, (void*)s->ppo.nets, (void*)s->ppo.moments, (void*)s->ppo.norm,
                   (void*)s->vn.val, (void*)s->vn.tgt, (void*)s->vn.part})
     dfree(s, p);
   s->act = mqe_sim::Actor();
@@ -1609,32 +1619,47 @@ extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
   if (sh->act_dim != 3) return fail(-6, "mqe_actor_create: act_dim must be 3");
   const bool vnorm = (sh->activation & MQE_ACTOR_VALUE_NORM) != 0;
   const bool ln_hidden = (sh->activation & MQE_ACTOR_LAYER_NORM) != 0, ln_feat = (sh->activation & MQE_ACTOR_FEATURE_NORM) != 0;
-  const int kind = sh->activation & ~(MQE_ACTOR_VALUE_NORM | MQE_ACTOR_LAYER_NORM | MQE_ACTOR_FEATURE_NORM);
+  const bool gru = (sh->activation & MQE_ACTOR_RECURRENT) != 0;
+  const int kind = sh->activation & ~(MQE_ACTOR_VALUE_NORM | MQE_ACTOR_LAYER_NORM | MQE_ACTOR_FEATURE_NORM | MQE_ACTOR_RECURRENT);
   if (kind != MQE_ACTOR_TANH && kind != MQE_ACTOR_RELU)
-    return fail(-6, "mqe_actor_create: activation must be MQE_ACTOR_TANH or MQE_ACTOR_RELU (or-ed with MQE_ACTOR_LAYER_NORM, MQE_ACTOR_FEATURE_NORM, MQE_ACTOR_VALUE_NORM or not)");
+    return fail(-6, "mqe_actor_create: activation must be MQE_ACTOR_TANH or MQE_ACTOR_RELU (or-ed with MQE_ACTOR_LAYER_NORM, MQE_ACTOR_FEATURE_NORM, MQE_ACTOR_RECURRENT, MQE_ACTOR_VALUE_NORM or not)");
   if (vnorm && sh->critic_layers == 0) return fail(-6, "mqe_actor_create: activation: MQE_ACTOR_VALUE_NORM needs a critic (the statistics are those of its targets)");
   if (not_finite(&sh->action_gain) || std::fabs(sh->action_gain) >= 1e30f) return fail(-6, "mqe_actor_create: action_gain is not finite");
   mqe_sim::Actor a;
   int off = 0, ldh = 0;
-  if (int rc = actor_net_shape("actor", sh->actor_layers, sh->actor_dims, sh->obs_dim, 3, ln_hidden, ln_feat, &a.sh.actor, a.sh.inv_actor, &off, &ldh)) return rc;
+  if (int rc = actor_net_shape("actor", sh->actor_layers, sh->actor_dims, sh->obs_dim, 3, ln_hidden, ln_feat, gru, &a.sh.actor, a.sh.inv_actor, &off, &ldh)) return rc;
   if (sh->critic_layers != 0)
-    if (int rc = actor_net_shape("critic", sh->critic_layers, sh->critic_dims, sh->obs_dim, 1, ln_hidden, ln_feat, &a.sh.critic, a.sh.inv_critic, &off, &ldh)) return rc;
+    if (int rc = actor_net_shape("critic", sh->critic_layers, sh->critic_dims, sh->obs_dim, 1, ln_hidden, ln_feat, gru, &a.sh.critic, a.sh.inv_critic, &off, &ldh)) return rc;
   a.log_std_off = off; a.n_params = off + 3; a.ldh = ldh; a.relu = kind == MQE_ACTOR_RELU; a.gain = sh->action_gain; a.vnorm = vnorm;
   a.sh.hidden = ln_hidden; a.sh.feat = ln_feat;
   const bool ln = ln_hidden || ln_feat;
-  const size_t lds = ln ? actor_ln_lds_bytes(ldh) : actor_lds_bytes(ldh);
-  if (lds > 48 * 1024 && hipFuncSetAttribute(ln ? (const void*)k_actor_ln : (const void*)k_actor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(-5, ln ? "mqe_actor_create: cannot reserve LDS for k_actor_ln" : "mqe_actor_create: cannot reserve LDS for k_actor");
+  if (gru) {
+    a.gru = true;
+    a.Ha = a.sh.actor.dims[a.sh.actor.n_layers - 1];
+    a.Hc = a.sh.critic.n_layers ? a.sh.critic.dims[a.sh.critic.n_layers - 1] : 0;
+  }
+  const size_t lds = gru ? actor_gru_lds_bytes(ldh, a.Ha, a.Hc, ln) : ln ? actor_ln_lds_bytes(ldh) : actor_lds_bytes(ldh);
+  if (gru && lds > GRU_LDS_LIMIT)
+    return fail(-6, "mqe_actor_create: a hidden width (or obs_dim) too large for MQE_ACTOR_RECURRENT: the two widest layer inputs and the state of both GRU cells "
+                    "(2 max width + Ha + Hc + 4, + 32 with a norm, rows of 260 bytes) exceed the 160 KiB of a workgroup");
+  const void* kern = gru ? (ln ? (const void*)k_actor_gru_ln : (const void*)k_actor_gru) : ln ? (const void*)k_actor_ln : (const void*)k_actor;
+  if (lds > 48 * 1024 && hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(-5, gru ? (ln ? "mqe_actor_create: cannot reserve LDS for k_actor_gru_ln" : "mqe_actor_create: cannot reserve LDS for k_actor_gru") : ln ? "mqe_actor_create: cannot reserve LDS for k_actor_ln" : "mqe_actor_create: cannot reserve LDS for k_actor");
   actor_release(s);
-  if (dalloc(s, &a.params, (size_t)a.n_params + (vnorm ? MQE_VALUE_NORM_STATE : 0)) || dalloc(s, &a.stage, (size_t)s->N * s->Aw * 3)) {
-    dfree(s, a.params);
+  if (dalloc(s, &a.params, (size_t)a.n_params + (vnorm ? MQE_VALUE_NORM_STATE : 0)) || dalloc(s, &a.stage, (size_t)s->N * s->Aw * 3) ||
+      (gru && (dalloc(s, &a.hstate, (size_t)s->N * s->Aw * (a.Ha + a.Hc)) || dalloc(s, &a.nets, 1)))) {
+    dfree(s, a.params); dfree(s, a.stage); dfree(s, a.hstate);
     return fail(-5, "device alloc failed (actor)");
+  }
+  if (gru && hipMemcpy(a.nets, &a.sh, sizeof a.sh, hipMemcpyHostToDevice) != hipSuccess) {
+    dfree(s, a.params); dfree(s, a.stage); dfree(s, a.hstate); dfree(s, a.nets);
+    return fail(-5, "mqe_actor_create: cannot write the shapes of the recurrent actor");
   }
   if (vnorm) {                         // (0, 0, 0) and its derived pair (0, 0.1f): sigma is never zero
     float w[MQE_VALUE_NORM_STATE] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     vn_derive(w[0], w[1], w[2], &w[3], &w[4]);
     if (hipMemcpy(a.params + a.n_params, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess) {
-      dfree(s, a.params); dfree(s, a.stage);
+      dfree(s, a.params); dfree(s, a.stage); dfree(s, a.hstate); dfree(s, a.nets);
       return fail(-5, "mqe_actor_create: cannot write the value-normalisation state");
     }
   }
@@ -1645,8 +1670,14 @@ extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
       for (int l = 0; l < net->n_layers; l++)
         if (l == 0 ? ln_feat : ln_hidden)
           ok = ok && hipMemcpy(a.params + ln_gamma_off(*net, l), ones.data(), (size_t)net->dims[l] * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (gru && ln_hidden)              // gru.norm.weight, behind the cell's two biases
+      for (const ActorNet* net : {&a.sh.actor, &a.sh.critic})
+        if (net->n_layers) {
+          const int H = net->dims[net->n_layers - 1];
+          ok = ok && hipMemcpy(a.params + gru_off(*net, 1) + 6 * H * H + 6 * H, ones.data(), (size_t)H * 4, hipMemcpyHostToDevice) == hipSuccess;
+        }
     if (!ok) {
-      dfree(s, a.params); dfree(s, a.stage);
+      dfree(s, a.params); dfree(s, a.stage); dfree(s, a.hstate); dfree(s, a.nets);
       return fail(-5, "mqe_actor_create: cannot write the layer norms' weights");
     }
   }
@@ -1661,7 +1692,8 @@ extern "C" int mqe_actor_params(mqe_sim* s, mqe_tensor_view* v) {
   return 0;
 }
 // value_only: the launch behind the last step (no draw, nothing but value written)
-static void launch_actor(mqe_sim* s, const float* obs, float* actions, float* logp, float* value, int flags, bool value_only, hipStream_t q) {
+// record: the tail of the next packed row (a recurrent handle under MQE_ROLLOUT_HIDDEN_RECORD), or null
+static void launch_actor(mqe_sim* s, const float* obs, float* actions, float* logp, float* value, int flags, bool value_only, hipStream_t q, float* record = nullptr) {
   const mqe_sim::Actor& a = s->act;
   ActorArgs k;
   k.sh = a.sh; k.params = a.params; k.obs = obs; k.actions = value_only ? nullptr : actions; k.logp = logp; k.value = value; k.stage = a.stage;
@@ -1669,6 +1701,13 @@ static void launch_actor(mqe_sim* s, const float* obs, float* actions, float* lo
   k.rows = s->N * s->Aw; k.D = s->D; k.Aw = s->Aw; k.ldh = a.ldh; k.relu = a.relu; k.deterministic = (flags & MQE_ROLLOUT_DETERMINISTIC) ? 1 : 0;
   k.gain = a.gain; k.seed = (uint32_t)s->d.seed; k.genv0 = (uint32_t)s->d.env_id_offset; k.count = MQE_RNG_ACTOR + (uint32_t)s->n_post_steps;
   const dim3 grid((k.rows + ACT_ROWS - 1) / ACT_ROWS);
+  if (a.gru) {                         // the done bytes of the row the observation comes from sit behind its R' rewards
+    GruArgs g;
+    g.state = a.hstate; g.record = record; g.done = (const uint8_t*)(obs + (size_t)k.rows * (k.D + 1)); g.Ha = a.Ha; g.Hc = a.Hc;
+    hipLaunchKernelGGL(a.ln() ? k_actor_gru_ln : k_actor_gru, grid, dim3(ACT_THREADS), actor_gru_lds_bytes(a.ldh, a.Ha, a.Hc, a.ln()), q, k, g, (const float*)a.params,
+                       (const ActorShapes*)a.nets);
+    return;
+  }
   hipLaunchKernelGGL(a.ln() ? k_actor_ln : k_actor, grid, dim3(ACT_THREADS), a.ln() ? actor_ln_lds_bytes(a.ldh) : actor_lds_bytes(a.ldh), q, k);
 }
 extern "C" int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* packed_dev, long long row_stride, float* actions_dev, float* logp_dev,
@@ -1682,21 +1721,33 @@ extern "C" int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* pack
   if (int rc = check_aligned("mqe_rollout", {{packed_dev, 16}, {obs0_dev, 4}, {actions_dev, 4}, {logp_dev, 4}, {value_dev, 4}}, "packed_dev: 16 bytes, the others: 4")) return rc;
   if (value_dev && s->act.sh.critic.n_layers == 0) return fail(-6, "mqe_rollout: value_dev given, but the actor was created without a critic");
   if (s->to_rec && T > s->to_rec_cap) return fail(-6, "mqe_rollout: T exceeds capacity_steps of the registered time-out record (mqe_rollout_time_outs)");
+  // the recurrent state (kernels_gru.hpp): the tail of a packed row is the R' Hs floats behind the packed length rounded up to a multiple of 4
+  const bool gru = s->act.gru, h_in = (flags & MQE_ROLLOUT_HIDDEN_IN) != 0, h_rec = (flags & MQE_ROLLOUT_HIDDEN_RECORD) != 0;
+  const size_t tail = (ts.packed_floats + 3) / 4 * 4, hfloats = ts.rows * (size_t)(s->act.Ha + s->act.Hc);
+  if ((h_in || h_rec) && !gru)
+    return fail(-6, "mqe_rollout: flags: MQE_ROLLOUT_HIDDEN_IN / MQE_ROLLOUT_HIDDEN_RECORD need an actor created with MQE_ACTOR_RECURRENT (its state is what they read and write)");
+  if ((h_in || h_rec) && row_stride < (long long)(tail + hfloats))
+    return fail(-6, "mqe_rollout: row_stride: with MQE_ROLLOUT_HIDDEN_IN / MQE_ROLLOUT_HIDDEN_RECORD a row holds the packed length rounded up to a multiple of 4 and R' (Ha + Hc) state floats behind it");
   hipStream_t q = (hipStream_t)stream;
   const size_t rows = ts.rows, nobs = rows * s->D;
+  // the state the call starts from: the caller's, out of row 0's tail, or the live one, into it
+  if (h_in) HIPCHK(hipMemcpyAsync(s->act.hstate, packed_dev + tail, hfloats * 4, hipMemcpyDeviceToDevice, q));
+  else if (h_rec) HIPCHK(hipMemcpyAsync(packed_dev + tail, s->act.hstate, hfloats * 4, hipMemcpyDeviceToDevice, q));
   // row 0: the starting observation, reward and done bytes zeroed
   HIPCHK(hipMemcpyAsync(packed_dev, obs0_dev ? obs0_dev : (const float*)s->tens[MQE_T_WRAPPER_OBS], nobs * 4, hipMemcpyDeviceToDevice, q));
   HIPCHK(hipMemsetAsync(packed_dev + nobs, 0, rows * 4 + (size_t)s->N, q));
   int rc = 0;
   for (int t = 0; t < T && rc == 0; t++) {
     launch_actor(s, packed_dev + (size_t)t * row_stride, actions_dev + (size_t)t * rows * 3, logp_dev ? logp_dev + (size_t)t * rows : nullptr,
-                 value_dev ? value_dev + (size_t)t * rows : nullptr, flags, false, q);
+                 value_dev ? value_dev + (size_t)t * rows : nullptr, flags, false, q, h_rec ? packed_dev + (size_t)(t + 1) * row_stride + tail : nullptr);
     set_packed(s, packed_dev + (size_t)(t + 1) * row_stride);      // step t returns into row t + 1
     rc = mqe_step(s, s->act.stage, stream);
     if (rc == 0 && s->to_rec && hipMemcpyAsync(s->to_rec + (size_t)t * s->N, s->st.time_out, (size_t)s->N, hipMemcpyDeviceToDevice, q) != hipSuccess)
       rc = fail(-100, "HIP error: %s", "mqe_rollout: the copy into the time-out record");
   }
-  if (rc == 0 && value_dev) launch_actor(s, packed_dev + (size_t)T * row_stride, nullptr, nullptr, value_dev + (size_t)T * rows, flags, true, q);
+  // a recurrent handle always enqueues the launch behind the last step: it masks the live state with row T's done bytes
+  if (rc == 0 && (value_dev || gru))
+    launch_actor(s, packed_dev + (size_t)T * row_stride, nullptr, nullptr, value_dev ? value_dev + (size_t)T * rows : nullptr, flags, true, q);
   set_packed(s, (float*)s->tens[MQE_T_WRAPPER_PACKED]);
   if (rc) return rc;
   // the engine's own buffer follows the trajectory's last row: MQE_T_WRAPPER_* show what the last step returned, and a following
@@ -1768,6 +1819,9 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   if (!packed_dev || !actions_dev || !logp_dev || !value_dev || !adv_dev || !ret_dev || !loss || !grad_dev)
     return fail(-1, "mqe_ppo_grad: packed_dev, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, loss and grad_dev are required");
   if (!s->act.on) return fail(-6, "mqe_ppo_grad: no actor (mqe_actor_create)");
+  if (s->act.gru)
+    return fail(-6, "mqe_ppo_grad: the actor was created with MQE_ACTOR_RECURRENT: back-propagation through time is not built in the engine yet "
+                    "(train the torch twin on the recorded trajectory and copy the parameters back)");
   if (s->act.sh.critic.n_layers == 0) return fail(-6, "mqe_ppo_grad: the actor was created without a critic: the loss has a value term");
   TrajShape ts;
   if (int rc = traj_shape(s, "mqe_ppo_grad", T, row_stride, &ts)) return rc;

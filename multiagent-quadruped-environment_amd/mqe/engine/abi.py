@@ -125,6 +125,12 @@ PPO_VALUE_NORM, PPO_VALUE_NORM_UPDATE = 8, 16
 # layer normalisation (include/mqe_hip.h states the values, csrc/kernels_ln.hpp defines them): two bits of the kind byte of
 # mqe_actor_shape.activation, or-ed with ACTOR_TANH / ACTOR_RELU -- a LayerNorm behind every hidden activation / on the observation
 ACTOR_LAYER_NORM, ACTOR_FEATURE_NORM = 2, 4
+# the recurrent actor-critic (include/mqe_hip.h states the values, csrc/kernels_gru.hpp defines them): a bit of the kind byte of
+# mqe_actor_shape.activation -- a GRU cell in front of the output layer of both networks -- and mqe_rollout flags bits 1 and 2: the start state is
+# read from the tail of packed row 0 / the tails of rows 0 .. T are written
+ACTOR_RECURRENT = 16
+ROLLOUT_HIDDEN_IN, ROLLOUT_HIDDEN_RECORD = 2, 4
+ACT_LD, LN_PART, GRU_LDS_LIMIT = 65, 32, 160 * 1024      # csrc/kernels_actor.hpp, kernels_ln.hpp, kernels_gru.hpp: what the LDS rule below is made of
 RNG_ACTOR = 0x70000000          # csrc/mqe_common.hpp MQE_RNG_ACTOR: `count` of the actor's draws = RNG_ACTOR + post-physics steps so far
 
 
@@ -138,13 +144,24 @@ class PpoLoss(C.Structure):
     _fields_ = [("clip_ratio", f32), ("value_coef", f32), ("entropy_coef", f32), ("value_clip", f32)]
 
 
-def actor_param_layout(actor_dims, critic_dims=None, value_norm=False, layer_norm=False, feature_norm=False):
+def actor_gru_lds_bytes(actor_dims, critic_dims=None, layer_norm=False, feature_norm=False):
+    """LDS of k_actor_gru / k_actor_gru_ln for a recurrent shape (csrc/kernels_gru.hpp actor_gru_lds_bytes): two buffers of the widest layer input,
+    the 4 output rows, the norms' 32 partial rows, the state of both cells, in rows of 65 floats.  mqe_actor_create refuses above GRU_LDS_LIMIT."""
+    nets = [list(actor_dims)] + ([list(critic_dims)] if critic_dims else [])
+    ldh = max(int(d) for dims in nets for d in dims[:-1])
+    hs = sum(int(dims[-2]) for dims in nets)
+    return (2 * ldh + 4 + (LN_PART if layer_norm or feature_norm else 0) + hs) * ACT_LD * 4
+
+
+def actor_param_layout(actor_dims, critic_dims=None, value_norm=False, layer_norm=False, feature_norm=False, recurrent=False):
     """The flat parameter buffer of mqe_actor_params as an ordered {name: (offset, shape)}: per layer W (out, in) row-major as
     torch.nn.Linear.weight, then b; the actor's layers, then the critic's, then log_std[3].  Names: actor.<layer>.weight / .bias,
     critic.<layer>.weight / .bias, log_std.  value_norm (an actor created with ACTOR_VALUE_NORM): + "value_norm", the VALUE_NORM_STATE
     floats (m, q, d, mu, sigma) behind log_std -- state of the normaliser, not a trainable parameter.  feature_norm (ACTOR_FEATURE_NORM):
     <who>.norm_in.weight / .bias (D each) in front of a network's layer 0; layer_norm (ACTOR_LAYER_NORM): <who>.<layer>.norm.weight / .bias
-    (n each) behind the bias of every hidden layer.  With both off the layout is the plain one."""
+    (n each) behind the bias of every hidden layer.  With both off the layout is the plain one.  recurrent (ACTOR_RECURRENT; every network needs
+    a hidden layer, H = the last one's width): <who>.gru.weight_ih / .weight_hh (3H, H), .bias_ih / .bias_hh (3H) and, with layer_norm,
+    <who>.gru.norm.weight / .bias (H) in front of the output layer's weight -- torch.nn.GRU's own tensors and order."""
     out, off = {}, 0
     for who, dims in (("actor", actor_dims), ("critic", critic_dims or ())):
         if feature_norm and len(dims) > 1:
@@ -154,6 +171,13 @@ def actor_param_layout(actor_dims, critic_dims=None, value_norm=False, layer_nor
             off += 2 * d
         for l in range(len(dims) - 1):
             k, n = int(dims[l]), int(dims[l + 1])
+            if recurrent and l + 2 == len(dims):
+                if l == 0:
+                    raise ValueError(f"{who}: a recurrent network needs at least 2 Linear layers (the GRU cell sits behind the last hidden layer)")
+                for name, shape in (("weight_ih", (3 * k, k)), ("weight_hh", (3 * k, k)), ("bias_ih", (3 * k,)), ("bias_hh", (3 * k,)),
+                                    *((("norm.weight", (k,)), ("norm.bias", (k,))) if layer_norm else ())):
+                    out[f"{who}.gru.{name}"] = (off, shape)
+                    off += shape[0] * (shape[1] if len(shape) > 1 else 1)
             out[f"{who}.{l}.weight"] = (off, (n, k))
             out[f"{who}.{l}.bias"] = (off + n * k, (n,))
             off += n * k + n
@@ -167,9 +191,9 @@ def actor_param_layout(actor_dims, critic_dims=None, value_norm=False, layer_nor
     return out
 
 
-def actor_param_count(actor_dims, critic_dims=None, value_norm=False, layer_norm=False, feature_norm=False):
+def actor_param_count(actor_dims, critic_dims=None, value_norm=False, layer_norm=False, feature_norm=False, recurrent=False):
     """floats of the buffer: the trainable parameters, + VALUE_NORM_STATE with value_norm"""
-    off, shape = list(actor_param_layout(actor_dims, critic_dims, value_norm, layer_norm, feature_norm).values())[-1]
+    off, shape = list(actor_param_layout(actor_dims, critic_dims, value_norm, layer_norm, feature_norm, recurrent).values())[-1]
     return off + shape[0]
 
 

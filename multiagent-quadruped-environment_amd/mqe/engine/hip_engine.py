@@ -53,9 +53,12 @@ class Rollout:
     t + 1 what step t returned (obs | reward | done bytes) -- and obs / reward / done are views of it; actions are the UNCLIPPED samples,
     logp their log-density, value[t] the critic at obs[t] (value[T]: the bootstrap value), None without a critic.  None unless asked for:
     time_outs (T, N) bool, the time-out flags of every step (rollout(time_outs=True)); advantages / returns (T, N, A') and adv_stats
-    (float32 [2]: mean, std of the advantages before normalisation; normalising calls only), filled by HipEngine.gae."""
+    (float32 [2]: mean, std of the advantages before normalisation; normalising calls only), filled by HipEngine.gae.  hidden (T + 1, N, A', Hs):
+    the recurrent state of a recurrent actor, a view of the rows' tails (rollout(record_hidden=True); None otherwise) -- hidden[t] is the
+    UNMASKED state step t starts from (row 0: the state the call started from), the actor's Ha floats, then the critic's Hc; step t evaluates
+    from hidden[t] * (1 - done[t - 1]) (t = 0: unmasked), OpenRL's (rnn_states[t], masks[t])."""
 
-    def __init__(self, packed, actions, logp, value, shape, time_outs=None, advantages=None, returns=None, adv_stats=None):
+    def __init__(self, packed, actions, logp, value, shape, time_outs=None, advantages=None, returns=None, adv_stats=None, hidden_width=0):
         N, Aw, D = shape
         n, nr = N * Aw * D, N * Aw
         self.packed, self.actions, self.logp, self.value = packed, actions, logp, value
@@ -65,6 +68,15 @@ class Rollout:
         self.done = packed[1:, n + nr:].view(torch.uint8)[:, :N].view(torch.bool)      # the byte tail of every row, seen as bool in place
         self.time_outs = time_outs.view(torch.bool) if time_outs is not None and time_outs.dtype == torch.uint8 else time_outs
         self.advantages, self.returns, self.adv_stats = advantages, returns, adv_stats
+        p4 = (n + nr + (N + 3) // 4 + 3) // 4 * 4
+        self.hidden = packed[:, p4:p4 + nr * hidden_width].view(self.T + 1, N, Aw, hidden_width) if hidden_width else None
+
+    def next_hidden(self):
+        """the state a following rollout(hidden=...) continues from: hidden[T], zero where the last step ended its env's episode"""
+        if self.hidden is None:
+            raise ValueError("next_hidden: the trajectory holds no recurrent state (rollout(record_hidden=True) on a recurrent actor)")
+        h = self.hidden[self.T]
+        return torch.where(self.done[self.T - 1][:, None, None], torch.zeros((), dtype=h.dtype, device=h.device), h)      # exactly 0.0f, as the engine masks
 
 
 class HipEngine(EngineBase):
@@ -167,7 +179,8 @@ class HipEngine(EngineBase):
         self._call("set_return_buffer", C.c_void_p(packed.data_ptr() if packed is not None else None))
 
     # ---- on-device rollouts (mqe_actor_create / mqe_actor_params / mqe_rollout) -------------------------------------------------------
-    def create_actor(self, actor_dims, critic_dims=None, activation="tanh", action_gain=1.0, value_norm=False, layer_norm=False, feature_norm=False):
+    def create_actor(self, actor_dims, critic_dims=None, activation="tanh", action_gain=1.0, value_norm=False, layer_norm=False, feature_norm=False,
+                     recurrent=False):
         """The engine's actor (and critic): MLPs on the task observation.  actor_dims = (D, hidden ..., 3), critic_dims = (D, hidden ..., 1)
         or None; activation "tanh" / "relu" on every hidden layer; the step receives action_gain * a.  Parameters start at zero: fill the
         views of actor_params().  A second call replaces the first.  value_norm (needs a critic): the engine keeps OpenRL's ValueNorm beside
@@ -175,7 +188,10 @@ class HipEngine(EngineBase):
         (mu, sigma) of the returns, and gae / ppo_grad / ppo_update follow (their value_norm=None).  layer_norm / feature_norm
         (abi.ACTOR_LAYER_NORM / ACTOR_FEATURE_NORM; csrc/kernels_ln.hpp states the arithmetic): torch.nn.LayerNorm(n, eps=1e-5) behind every
         hidden activation / on the observation in front of layer 0, in both networks; their weights start at 1, and rollout, gae, ppo_grad,
-        adam_step and ppo_update work unchanged on such an actor."""
+        adam_step and ppo_update work unchanged on such an actor.  recurrent (abi.ACTOR_RECURRENT; csrc/kernels_gru.hpp states the arithmetic): a
+        torch.nn.GRU cell H -> H (H = the last hidden width; every network needs a hidden layer) in front of the output layer of both networks,
+        followed by a LayerNorm(H) under layer_norm; the engine carries the state across rollout calls, zeroed here and reset wherever a step ended
+        an episode.  rollout, gae and adam_step work on such an actor; ppo_grad and ppo_update refuse it (no back-propagation through time yet)."""
         actor_dims = [int(x) for x in actor_dims]
         critic_dims = [int(x) for x in critic_dims] if critic_dims is not None else []
         for who, dims in (("actor", actor_dims), ("critic", critic_dims)):
@@ -191,11 +207,12 @@ class HipEngine(EngineBase):
         for i, v in enumerate(critic_dims):
             sh.critic_dims[i] = v
         sh.activation = ((abi.ACTOR_RELU if activation == "relu" else abi.ACTOR_TANH) | (abi.ACTOR_VALUE_NORM if value_norm else 0)
-                         | (abi.ACTOR_LAYER_NORM if layer_norm else 0) | (abi.ACTOR_FEATURE_NORM if feature_norm else 0))
+                         | (abi.ACTOR_LAYER_NORM if layer_norm else 0) | (abi.ACTOR_FEATURE_NORM if feature_norm else 0)
+                         | (abi.ACTOR_RECURRENT if recurrent else 0))
         sh.action_gain = float(action_gain)
         self._invoke("actor_create", C.byref(sh))
         self._actor = dict(actor_dims=actor_dims, critic_dims=critic_dims or None, activation=activation, action_gain=float(action_gain),
-                           value_norm=bool(value_norm), layer_norm=bool(layer_norm), feature_norm=bool(feature_norm))
+                           value_norm=bool(value_norm), layer_norm=bool(layer_norm), feature_norm=bool(feature_norm), recurrent=bool(recurrent))
         self._actor_views = None
         self.ppo_step = 0            # the library dropped Adam's moments with the old actor
 
@@ -210,7 +227,8 @@ class HipEngine(EngineBase):
             self._call("actor_params", C.byref(v))
             flat = self._wrap(v.ptr, [int(v.shape[0])], v.dtype)
             vn = self._actor["value_norm"]
-            layout = abi.actor_param_layout(self._actor["actor_dims"], self._actor["critic_dims"], vn, self._actor["layer_norm"], self._actor["feature_norm"])
+            layout = abi.actor_param_layout(self._actor["actor_dims"], self._actor["critic_dims"], vn, self._actor["layer_norm"], self._actor["feature_norm"],
+                                            self._actor["recurrent"])
             views = {n: flat[o:o + int(np.prod(shp))].view(shp) for n, (o, shp) in layout.items()}
             if vn:
                 views["all"] = flat
@@ -223,24 +241,48 @@ class HipEngine(EngineBase):
         """floats of one row of a trajectory's packed tensor: the T_WRAPPER_PACKED length rounded up to a multiple of 4"""
         return (self.tensor(abi.T_WRAPPER_PACKED).numel() + 3) // 4 * 4
 
-    def rollout(self, T, obs0=None, deterministic=False, out=None, time_outs=False):
+    def hidden_width(self):
+        """Hs = Ha + Hc: the floats of a row's recurrent state (the last hidden widths of the actor and the critic); 0 unless the actor is recurrent"""
+        a = self._actor
+        if a is None or not a["recurrent"]:
+            return 0
+        return a["actor_dims"][-2] + (a["critic_dims"][-2] if a["critic_dims"] else 0)
+
+    def _recurrent_refusal(self, who):
+        if self._actor is not None and self._actor["recurrent"]:
+            raise NotImplementedError(f"{who}: the actor is recurrent, and back-propagation through time is not built in the engine yet (mqe_ppo_grad refuses it): "
+                                      "train the torch twin (mqe.utils.actor_net.RecurrentMLP.evaluate from traj.hidden) and sync_actor()")
+
+    def rollout(self, T, obs0=None, deterministic=False, out=None, time_outs=False, hidden=None, record_hidden=False):
         """T steps of actor -> step inside the engine, one host call, no synchronisation (mqe_rollout).  obs0: the (N, A', D) observation to
         start from (None: the engine's own T_WRAPPER_OBS, which a reset, a step without a return buffer of the caller's, and every rollout
         leave current -- NOT a step that was given its own return buffer, as the task wrappers' step() does).  out: a Rollout of the same T whose tensors are written again instead of fresh
         ones.  Returns a Rollout: views of the one packed tensor (obs (T+1, N, A', D), reward (T, N, A'), done (T, N) bool) + actions
         (T, N, A', 3), logp (T, N, A'), value (T+1, N, A') or None without a critic.  time_outs=True: the call also records T_TIME_OUT_BUF as
         every step left it (mqe_rollout_time_outs: one N-byte device copy per step) into Rollout.time_outs, (T, N) bool -- a fresh tensor,
-        or out.time_outs; without it the call enqueues what it always did and Rollout.time_outs stays as it was (None on a fresh one)."""
+        or out.time_outs; without it the call enqueues what it always did and Rollout.time_outs stays as it was (None on a fresh one).
+        A recurrent actor (create_actor(recurrent=True)) continues from the engine's live state; hidden: an (N, A', Hs) float32 device tensor to
+        start from instead (copied into row 0's tail; abi.ROLLOUT_HIDDEN_IN); record_hidden: the rows are R' Hs floats wider and Rollout.hidden
+        (T + 1, N, A', Hs) views the recorded states (abi.ROLLOUT_HIDDEN_RECORD).  out= needs a packed tensor of that width."""
         self._need_actor()
         T = int(T)
         N, Aw, D = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
         dev = self.torch_device
         critic = self._actor["critic_dims"] is not None
+        hs = self.hidden_width()
+        wide = hidden is not None or record_hidden
+        if wide and not hs:
+            raise ValueError("rollout: hidden= / record_hidden=True need a recurrent actor (create_actor(recurrent=True))")
+        if hidden is not None:
+            _need_f32("hidden", hidden, (N, Aw, hs))
+        p4 = self.rollout_row_stride()
+        need = p4 + N * Aw * hs if wide else 0
         if out is None:
-            stride = self.rollout_row_stride()
+            stride = (need + 3) // 4 * 4 if wide else p4
             out = Rollout(torch.zeros(max(T, 0) + 1, stride, dtype=torch.float32, device=dev), torch.empty(max(T, 0), N, Aw, 3, dtype=torch.float32, device=dev),
                           torch.empty(max(T, 0), N, Aw, dtype=torch.float32, device=dev),
-                          torch.empty(max(T, 0) + 1, N, Aw, dtype=torch.float32, device=dev) if critic else None, (N, Aw, D))
+                          torch.empty(max(T, 0) + 1, N, Aw, dtype=torch.float32, device=dev) if critic else None, (N, Aw, D),
+                          hidden_width=hs if record_hidden else 0)
         else:
             if out.T != T:
                 raise ValueError(f"out holds a trajectory of {out.T} steps, not {T}")
@@ -251,17 +293,23 @@ class HipEngine(EngineBase):
                     _need_f32(f"out.{name}", t, shape)
             if out.actions is None or out.packed.dtype != torch.float32 or not out.packed.is_cuda:
                 raise ValueError("out.packed and out.actions must be float32 device tensors")
+            if wide and (out.packed.shape[1] < need or (record_hidden and out.hidden is None)):
+                raise ValueError(f"out.packed rows hold {out.packed.shape[1]} floats; with hidden= / record_hidden=True a row takes {need} "
+                                 "(the packed length rounded up to a multiple of 4 + N A' Hs state floats): pass a Rollout of rollout(record_hidden=True)")
         if time_outs:
             if out.time_outs is None:
                 out.time_outs = torch.zeros(max(T, 0), N, dtype=torch.uint8, device=dev).view(torch.bool)
             _need_flags("out.time_outs", out.time_outs, (T, N))
         if obs0 is not None:
             assert obs0.is_cuda and obs0.dtype == torch.float32 and obs0.is_contiguous() and tuple(obs0.shape) == (N, Aw, D)
+        if hidden is not None and T >= 1:
+            out.packed[0, p4:p4 + N * Aw * hs].copy_(hidden.reshape(-1))
         if time_outs:
             self._call("rollout_time_outs", _ptr(out.time_outs), max(T, 1))       # T <= 0: mqe_rollout itself refuses
         try:
             self._invoke("rollout", T, _ptr(obs0), _ptr(out.packed), int(out.packed.stride(0)), _ptr(out.actions), _ptr(out.logp), _ptr(out.value),
-                         abi.ROLLOUT_DETERMINISTIC if deterministic else 0, self._stream())
+                         (abi.ROLLOUT_DETERMINISTIC if deterministic else 0) | (abi.ROLLOUT_HIDDEN_IN if hidden is not None else 0)
+                         | (abi.ROLLOUT_HIDDEN_RECORD if record_hidden else 0), self._stream())
         finally:
             if time_outs:
                 self.lib.mqe_rollout_time_outs(self.h, None, 0)         # the record belongs to this call alone, refused or not
@@ -327,6 +375,7 @@ class HipEngine(EngineBase):
         update_value_norm: the minibatch's returns are folded into the statistics first (abi.PPO_VALUE_NORM_UPDATE: one more launch) -- the
         only call that changes actor_params()["value_norm"]."""
         self._need_actor()
+        self._recurrent_refusal("ppo_grad")
         vn = self._value_norm("ppo_grad", value_norm)
         if update_value_norm and not vn:
             raise ValueError("ppo_grad: update_value_norm=True needs value normalisation (an actor created with value_norm=True)")
@@ -393,6 +442,7 @@ class HipEngine(EngineBase):
         over between calls.  -> the (epochs, minibatches, 6) statistics tensor (ppo_grad's, before each step).  Afterwards the engine's buffer
         is the master copy of the parameters.  value_norm (None: as the actor was created): every minibatch first folds its returns into
         the running statistics, then normalises them with the new (mu, sigma) -- OpenRL's ValueNorm order; 1 or 2 more launches a slice."""
+        self._recurrent_refusal("ppo_update")
         vn = self._value_norm("ppo_update", value_norm)
         epochs, minibatches = int(epochs), int(minibatches)
         T = int(traj.T)

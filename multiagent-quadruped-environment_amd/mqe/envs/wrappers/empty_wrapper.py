@@ -78,12 +78,16 @@ class FusedTaskWrapper(EmptyWrapper):
         self._wpack = env.engine.tensor(abi.T_WRAPPER_PACKED)        # obs | reward | done (N bytes) in one buffer
         assert self._wobs.shape[-1] == self.observation_space.shape[0]
         self.reward_buffer = RewardBuffer([n for _, n in REWARD_TERMS[self.task]], env.engine.tensor(abi.T_REWARD_SUMS))
+        # a recurrent actor (set_actor(recurrent=True)): what the next rollout() starts its cells from -- "live" (the engine's own state), "zeros" or
+        # a tensor -- and what get_state() can save of the state behind the last rollout: "zeros", a tensor, or None (not recorded: unknown)
+        self._recurrent, self._hidden_next, self._hidden_saved = False, "live", "zeros"
 
     def _obs_dim(self):
         raise NotImplementedError
 
     def reset(self):
         self.env.reset()
+        self._hidden_next = self._hidden_saved = "zeros"          # every episode starts anew
         self._hold_obs(self._wobs.clone())
         return self._last_obs
 
@@ -94,17 +98,28 @@ class FusedTaskWrapper(EmptyWrapper):
 
     def get_state(self):
         """Go1.get_state() + the observation this wrapper last returned: the engine's blob does not hold it when the step wrote it into a
-        tensor of the caller's (as step() does), and a rollout() after set_state() starts from it"""
+        tensor of the caller's (as step() does), and a rollout() after set_state() starts from it.  With a recurrent actor
+        (set_actor(recurrent=True)) also "last_hidden": the cells' state behind the last rollout(record_hidden=True), which set_state() hands
+        the next rollout(); after an unrecorded rollout it raises RuntimeError and says why"""
         state = dict(self.env.get_state())
         obs = getattr(self, "_last_obs", None)
         current = obs is not None and getattr(self, "_last_obs_epoch", None) == getattr(self.env, "_obs_epoch", 0)
         state["last_obs"] = obs.detach().cpu().clone() if current else None
+        if self._recurrent:
+            # the engine's live recurrent state has no export of its own: what the wrapper can save is next_hidden() of the last RECORDED rollout
+            h = self._hidden_saved
+            if h is None:
+                raise RuntimeError("get_state: the actor is recurrent and the last rollout() did not record its state (record_hidden=False): the "
+                                   "engine's live state cannot be read back; roll out with record_hidden=True before a checkpoint")
+            state["last_hidden"] = h.detach().cpu().clone() if isinstance(h, torch.Tensor) and current else None      # None: zeros
         return state
 
     def set_state(self, state):
         self.env.set_state(state)
         obs = state.get("last_obs")
         self._hold_obs(obs.to(self._wobs.device).contiguous() if obs is not None else None)
+        h = state.get("last_hidden")                 # the next rollout() starts from it (zeros when the state held none)
+        self._hidden_next = self._hidden_saved = h.to(self._wobs.device).contiguous() if h is not None else "zeros"
 
     def step(self, action):
         # fresh tensors every step, like the reference: the HIP engine writes obs | reward | done of this step straight into a
@@ -140,7 +155,7 @@ class FusedTaskWrapper(EmptyWrapper):
                                       f"{type(eng).__name__} has no on-device actor")
         return eng
 
-    def set_actor(self, actor_module, critic_module=None, log_std=None, action_gain=1.0, value_norm=False, layer_norm=False):
+    def set_actor(self, actor_module, critic_module=None, log_std=None, action_gain=1.0, value_norm=False, layer_norm=False, recurrent=False):
         """The policy a following rollout() evaluates inside the engine: torch.nn.Sequential stacks of Linear / Tanh / ReLU -- actor
         (obs_dim -> ... -> 3, the mean), optional critic (obs_dim -> ... -> 1) with the same activation -- and log_std (3 values; a tensor
         or Parameter is read again by every sync_actor(); None: zeros).  Anything else raises ValueError naming the offending layer.
@@ -151,11 +166,23 @@ class FusedTaskWrapper(EmptyWrapper):
         torch.nn.LayerNorm(n, eps=1e-5) layers -- one on the observation in front of the first Linear (the feature norm), one behind every
         hidden activation (the hidden norm), either, both or none, the same choice in actor and critic (mqe.utils.actor_net.mlp_spec names
         what it refuses); sync_actor() and pull_actor() copy their weights and biases too.  Without it a LayerNorm is refused like any
-        other layer."""
-        from mqe.utils.actor_net import mlp_spec
+        other layer.  recurrent=True: both networks are mqe.utils.actor_net.RecurrentMLP (base -> GRU cell -> [LayerNorm] -> head; OpenRL's
+        use_recurrent_policy), or the actor alone; a plain Sequential beside a RecurrentMLP is refused.  The engine carries the cells' state
+        across rollout() calls and zeroes it wherever a step ended an episode; sync_actor() / pull_actor() copy the cells too.  ppo_update()
+        refuses such an actor: the learner runs back-propagation through time on the torch twins (rollout(record_hidden=True), then
+        RecurrentMLP.evaluate from traj.hidden) and sync_actor()s the result."""
+        from mqe.utils.actor_net import RecurrentMLP, mlp_spec, recurrent_spec
         D = self.observation_space.shape[0]
         no_norms = {"feature": None, "hidden": []}
         spec = lambda module, what, out: mlp_spec(module, what, D, out, layer_norm=True) if layer_norm else (*mlp_spec(module, what, D, out), no_norms)
+        a_rnn = c_rnn = None
+        if recurrent:
+            spec = lambda module, what, out: recurrent_spec(module, what, D, out, layer_norm=layer_norm)[:4]
+            a_rnn, c_rnn = actor_module, critic_module
+        else:
+            for what, m in (("actor", actor_module), ("critic", critic_module)):
+                if isinstance(m, RecurrentMLP):
+                    raise ValueError(f"{what}: a RecurrentMLP without recurrent=True; the engine evaluates both networks recurrent (set_actor(..., recurrent=True)) or neither")
         a_dims, a_act, a_lin, a_norm = spec(actor_module, "actor", 3)
         c_dims, c_act, c_lin, c_norm = (None, None, [], a_norm)
         if critic_module is not None:
@@ -176,9 +203,13 @@ class FusedTaskWrapper(EmptyWrapper):
         norm_kw = {}
         if layer_norm:                     # an engine without the keywords is never asked for them
             norm_kw = dict(layer_norm=bool(a_norm["hidden"] or c_norm["hidden"]), feature_norm=a_norm["feature"] is not None)
+        if recurrent:
+            norm_kw["recurrent"] = True
         eng.create_actor(a_dims, c_dims, activation=a_act or c_act or "tanh", action_gain=action_gain, value_norm=value_norm, **norm_kw)
         self._actor_src = (a_lin, c_lin, log_std)
         self._actor_norms = (a_norm, c_norm if critic_module is not None else no_norms)
+        self._actor_rnns = (a_rnn, c_rnn)
+        self._recurrent, self._hidden_next, self._hidden_saved = bool(recurrent), "live", "zeros"       # create_actor zeroed the engine's state
         self.sync_actor()
 
     def sync_actor(self):
@@ -196,10 +227,23 @@ class FusedTaskWrapper(EmptyWrapper):
             for name, norm in self._norm_modules():
                 views[f"{name}.weight"].copy_(norm.weight.detach(), non_blocking=True)
                 views[f"{name}.bias"].copy_(norm.bias.detach(), non_blocking=True)
+            for name, t in self._gru_tensors():
+                views[name].copy_(t.detach(), non_blocking=True)
             if log_std is None:
                 views["log_std"].zero_()
             else:
                 views["log_std"].copy_(torch.as_tensor(log_std).detach().reshape(3).to(torch.float32), non_blocking=True)
+
+    def _gru_tensors(self):
+        """(the engine's name, the torch tensor) of every GRU cell and its norm that set_actor(recurrent=True) found: <who>.gru.<name>"""
+        for who, m in zip(("actor", "critic"), self._actor_rnns):
+            if m is None:
+                continue
+            for name in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
+                yield f"{who}.gru.{name}", getattr(m.rnn, name + "_l0")
+            if m.norm is not None:
+                yield f"{who}.gru.norm.weight", m.norm.weight
+                yield f"{who}.gru.norm.bias", m.norm.bias
 
     def _norm_modules(self):
         """(the engine's name, the torch.nn.LayerNorm) of every norm set_actor(layer_norm=True) found: <who>.norm_in, <who>.<layer>.norm"""
@@ -226,6 +270,8 @@ class FusedTaskWrapper(EmptyWrapper):
             for name, norm in self._norm_modules():
                 norm.weight.copy_(views[f"{name}.weight"], non_blocking=True)
                 norm.bias.copy_(views[f"{name}.bias"], non_blocking=True)
+            for name, t in self._gru_tensors():
+                t.copy_(views[name], non_blocking=True)
             if isinstance(log_std, torch.Tensor):
                 log_std.copy_(views["log_std"].reshape(log_std.shape), non_blocking=True)
 
@@ -244,7 +290,7 @@ class FusedTaskWrapper(EmptyWrapper):
             raise ValueError("ppo_update: the loss has a value term, and the actor was set without a critic (set_actor(actor, critic))")
         return eng.ppo_update(traj, **kw)
 
-    def rollout(self, T, deterministic=False, gamma=None, lam=0.95, normalize_advantages=False):
+    def rollout(self, T, deterministic=False, gamma=None, lam=0.95, normalize_advantages=False, record_hidden=False):
         """T steps with the engine's own actor (set_actor) in one call: a Rollout (mqe.engine.hip_engine) whose tensors -- obs (T+1, N, A', D),
         reward (T, N, A'), done (T, N) bool, actions (T, N, A', 3) unclipped, logp (T, N, A'), value (T+1, N, A') or None -- are fresh memory
         that belongs to the caller.  Starts from the observation the last step() / reset() / rollout() returned (set_state() of this
@@ -254,7 +300,10 @@ class FusedTaskWrapper(EmptyWrapper):
         (T, N, A'), adv_stats (mean, std; with normalize_advantages, which normalises over this env's own rows) are filled; with
         gamma=None they are None and the call enqueues nothing more than it always did.  After set_actor(value_norm=True) traj.value is in
         NORMALISED units (what the critic predicts); the engine de-normalises it with the current (mu, sigma) for the recursion, and
-        traj.returns / traj.advantages are in reward units."""
+        traj.returns / traj.advantages are in reward units.  After set_actor(recurrent=True) the cells continue from the engine's live state
+        (zeros after a reset or set_state() of the env below this wrapper; after this wrapper's set_state(): the state it restored);
+        record_hidden=True: traj.hidden (T + 1, N, A', Hs) holds the state every step started from, for back-propagation through time on the
+        torch twins, and get_state() can checkpoint the state behind the trajectory."""
         env = self.env
         eng = self._rollout_engine("rollout")
         if type(self).step is not FusedTaskWrapper.step:
@@ -276,7 +325,17 @@ class FusedTaskWrapper(EmptyWrapper):
         obs0 = getattr(self, "_last_obs", None)
         if getattr(self, "_last_obs_epoch", None) != getattr(env, "_obs_epoch", 0):
             obs0 = None       # the env was reset or restored below this wrapper: the engine's own buffer is what there is
-        traj = eng.rollout(T, obs0=obs0.contiguous() if obs0 is not None else None, deterministic=deterministic, time_outs=gamma is not None)
+        rec_kw = {}
+        if self._recurrent:
+            src = self._hidden_next if obs0 is not None else "zeros"       # reset or restored below this wrapper: zeros
+            if isinstance(src, str):
+                src = None if src == "live" else torch.zeros(self.num_envs, self.num_agents, eng.hidden_width(), dtype=torch.float32, device=self._wobs.device)
+            rec_kw = dict(hidden=src, record_hidden=record_hidden)
+        elif record_hidden:
+            raise ValueError("rollout(record_hidden=True): the actor is not recurrent (set_actor(..., recurrent=True))")
+        traj = eng.rollout(T, obs0=obs0.contiguous() if obs0 is not None else None, deterministic=deterministic, time_outs=gamma is not None, **rec_kw)
+        if rec_kw:
+            self._hidden_next, self._hidden_saved = "live", (traj.next_hidden() if record_hidden else None)
         if gamma is not None:
             eng.gae(traj, gamma, lam=lam, normalize=normalize_advantages)
         T = traj.T

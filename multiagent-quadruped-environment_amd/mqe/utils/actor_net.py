@@ -1,7 +1,89 @@
-"""torch modules -> the engine's actor (mqe_actor_create): which torch.nn.Sequential stacks k_actor can evaluate, and their shapes."""
+"""torch modules -> the engine's actor (mqe_actor_create): which torch.nn.Sequential stacks k_actor can evaluate, and their shapes; RecurrentMLP,
+the torch twin of a network with the engine's GRU cell (k_actor_gru), and what of it the engine accepts."""
 import torch
 
 LN_EPS = 1e-5          # the only eps the engine's norm has (csrc/kernels_ln.hpp LN_EPS)
+
+
+class RecurrentMLP(torch.nn.Module):
+    """The torch twin of one network of the engine's recurrent actor-critic (abi.ACTOR_RECURRENT; csrc/kernels_gru.hpp), OpenRL's MLP base +
+    RNNLayer + head: `base`, a Sequential in the form mlp_spec accepts minus the output layer (it ends in a hidden activation, or in that
+    activation's LayerNorm); `rnn`, torch.nn.GRU(H, H, num_layers=1); `norm`, LayerNorm(H) or None (with the hidden norm); `head`, Linear(H, out).
+    parameters() come in the engine's order.  Works in float32 and, after .double(), as the float64 reference."""
+
+    def __init__(self, base, out_dim, norm=None):
+        super().__init__()
+        nn = torch.nn
+        widths = [m.out_features for m in base if isinstance(m, nn.Linear)] if isinstance(base, nn.Sequential) else []
+        if not widths:
+            raise ValueError("RecurrentMLP: base must be a torch.nn.Sequential with at least one Linear layer")
+        H = widths[-1]
+        self.base = base
+        self.rnn = nn.GRU(H, H, num_layers=1)
+        if norm is None:                       # as the base: with the hidden norm it ends in a LayerNorm
+            norm = isinstance(list(base)[-1], nn.LayerNorm)
+        self.norm = nn.LayerNorm(H, eps=LN_EPS) if norm is True else None if norm is False else norm
+        self.head = nn.Linear(H, int(out_dim))
+
+    def forward(self, obs, h, mask):
+        """one step: obs (..., D), h (..., H), mask (..., 1) or (...) = 1 - done of the step before -> (out (..., out_dim), h_next (..., H));
+        the cell starts from h * mask, and h_next is not masked"""
+        mask = mask.to(h.dtype)
+        if mask.dim() == h.dim() - 1:
+            mask = mask.unsqueeze(-1)
+        x = self.base(obs)
+        H = h.shape[-1]
+        y, _ = self.rnn(x.reshape(1, -1, H), (h * mask).reshape(1, -1, H).contiguous())
+        h_next = y.reshape(h.shape)
+        return self.head(self.norm(h_next) if self.norm is not None else h_next), h_next
+
+    def evaluate(self, obs_seq, h0, masks):
+        """a chunk: obs_seq (L, ..., D), h0 (..., H), masks (L, ..., 1) or (L, ...) -> (outs (L, ..., out_dim), the state behind the chunk);
+        back-propagation through time runs through the L steps"""
+        outs, h = [], h0
+        for t in range(obs_seq.shape[0]):
+            o, h = self.forward(obs_seq[t], h, masks[t])
+            outs.append(o)
+        return torch.stack(outs), h
+
+
+def recurrent_spec(module, what, in_dim, out_dim, layer_norm=False):
+    """(dims, activation, linears, norms, module) of a RecurrentMLP for the engine: base through mlp_spec (with a stand-in output layer), then the
+    cell, its norm and the head against the base.  dims = [in_dim, hidden ..., out_dim]; `linears` ends with the head.  Refusals name the layer."""
+    nn = torch.nn
+    if not isinstance(module, RecurrentMLP):
+        raise ValueError(f"{what}: recurrent=True takes mqe.utils.actor_net.RecurrentMLP networks, got {type(module).__name__}")
+    base = module.base
+    if not isinstance(base, nn.Sequential) or len(base) == 0:
+        raise ValueError(f"{what}.base: expected a torch.nn.Sequential of Linear / Tanh / ReLU that ends in a hidden activation")
+    last_name, last = list(base.named_children())[-1]
+    if isinstance(last, nn.Linear):
+        raise ValueError(f"{what}.base[{last_name}] (Linear): the base ends in a Linear layer; the GRU cell reads a hidden ACTIVATION (the output layer is `head`)")
+    H = next(m.out_features for m in reversed(list(base)) if isinstance(m, nn.Linear)) if any(isinstance(m, nn.Linear) for m in base) else 0
+    stand_in = nn.Sequential(*base, nn.Linear(max(H, 1), out_dim))          # names 0 .. n - 1 as in base: the refusals of mlp_spec name its layers
+    spec = mlp_spec(stand_in, f"{what}.base", in_dim, out_dim, layer_norm=layer_norm)
+    dims, act, linears = spec[:3]
+    norms = spec[3] if layer_norm else {"feature": None, "hidden": []}
+    rnn = module.rnn
+    if not isinstance(rnn, nn.GRU):
+        raise ValueError(f"{what}.rnn ({type(rnn).__name__}): the engine's cell is torch.nn.GRU")
+    if (rnn.input_size, rnn.hidden_size, rnn.num_layers, rnn.bias, rnn.bidirectional) != (H, H, 1, True, False) or getattr(rnn, "proj_size", 0):
+        raise ValueError(f"{what}.rnn (GRU): expected GRU({H}, {H}, num_layers=1) with biases, one direction; got GRU({rnn.input_size}, {rnn.hidden_size}, "
+                         f"num_layers={rnn.num_layers}, bias={rnn.bias}, bidirectional={rnn.bidirectional})")
+    norm = module.norm
+    if norm is not None:
+        if not layer_norm:
+            raise ValueError(f"{what}.norm (LayerNorm): only Linear, Tanh and ReLU layers can run inside the engine (set_actor(layer_norm=True) admits the norms)")
+        if not isinstance(norm, nn.LayerNorm) or tuple(norm.normalized_shape) != (H,) or float(norm.eps) != LN_EPS or not norm.elementwise_affine or norm.bias is None:
+            raise ValueError(f"{what}.norm ({type(norm).__name__}): expected LayerNorm({H}, eps=1e-5) with a weight and a bias")
+    if (norm is not None) != bool(norms["hidden"]):
+        raise ValueError(f"{what}.norm: the LayerNorm behind the GRU cell goes with the hidden norm (a LayerNorm behind every hidden activation of base): both or neither")
+    head = module.head
+    if not isinstance(head, nn.Linear) or head.bias is None or head.in_features != H:
+        raise ValueError(f"{what}.head ({type(head).__name__}): expected Linear({H}, {out_dim}) with a bias")
+    if head.out_features != out_dim:
+        raise ValueError(f"{what}.head (Linear): the last Linear gives {head.out_features} outputs, {out_dim} wanted")
+    return dims, act, linears[:-1] + [head], norms, module
 
 
 def mlp_spec(module, what, in_dim, out_dim, layer_norm=False):

@@ -45,18 +45,23 @@ class mqe_openrl_wrapper(Wrapper):
         obs, reward, termination, info = self.env.step((0.5 * actions).clip(-1, 1))
         return obs, reward.unsqueeze(-1), termination.unsqueeze(-1).repeat(1, self.agent_num)
 
-    def set_actor(self, actor_module, critic_module=None, log_std=None, value_norm=False, layer_norm=False):
+    def set_actor(self, actor_module, critic_module=None, log_std=None, value_norm=False, layer_norm=False, recurrent=False):
         """the policy rollout_torch evaluates inside the engine (FusedTaskWrapper.set_actor) with this adapter's transform: the step
         receives 0.5 * a, clipped to +-1 inside the engine.  value_norm: OpenRL's use_valuenorm, kept by the engine.  layer_norm: the stacks
-        may hold the LayerNorm layers of OpenRL's MLP base (use_feature_normalization, and one behind every hidden activation)"""
+        may hold the LayerNorm layers of OpenRL's MLP base (use_feature_normalization, and one behind every hidden activation).  recurrent:
+        OpenRL's use_recurrent_policy -- the networks are mqe.utils.actor_net.RecurrentMLP, the engine carries their GRU state"""
         kw = {"layer_norm": True} if layer_norm else {}
+        if recurrent:
+            kw["recurrent"] = True
         self.env.set_actor(actor_module, critic_module, log_std=log_std, action_gain=0.5, value_norm=value_norm, **kw)
 
-    def rollout_torch(self, T, deterministic=False, gamma=None, lam=0.95, normalize_advantages=False):
+    def rollout_torch(self, T, deterministic=False, gamma=None, lam=0.95, normalize_advantages=False, record_hidden=False):
         """T steps of step_torch with the engine's own actor in one call (mqe_rollout, action_gain = 0.5): the wrapper's Rollout -- obs
         (T+1, N, A, D), reward (T, N, A), done (T, N) bool, actions (T, N, A, 3) as the actor sampled them, logp, value -- fresh device memory.
-        gamma / lam / normalize_advantages: FusedTaskWrapper.rollout's -- time_outs, advantages, returns and adv_stats from the engine (mqe_gae)"""
-        return self.env.rollout(T, deterministic=deterministic, gamma=gamma, lam=lam, normalize_advantages=normalize_advantages)
+        gamma / lam / normalize_advantages: FusedTaskWrapper.rollout's -- time_outs, advantages, returns and adv_stats from the engine (mqe_gae);
+        record_hidden (a recurrent actor): traj.hidden, the state every step started from, for back-propagation through time in torch"""
+        kw = {"record_hidden": True} if record_hidden else {}
+        return self.env.rollout(T, deterministic=deterministic, gamma=gamma, lam=lam, normalize_advantages=normalize_advantages, **kw)
 
     def ppo_update_torch(self, traj, **kw):
         """FusedTaskWrapper.ppo_update on a trajectory of rollout_torch(gamma=...): the PPO epochs run inside the engine on its own parameters
