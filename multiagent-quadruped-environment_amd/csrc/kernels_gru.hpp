@@ -58,10 +58,6 @@ struct GruArgs {
 static inline size_t actor_gru_lds_bytes(int ldh, int Ha, int Hc, bool ln) { return (size_t)(2 * ldh + 4 + (ln ? LN_PART : 0) + Ha + Hc) * ACT_LD * sizeof(float); }
 // floats of one network's cell in the parameter buffer
 __host__ __device__ inline int gru_param_floats(int H, bool ln_hidden) { return 6 * H * H + 6 * H + (ln_hidden ? 2 * H : 0); }
-// the first float of the cell's block (weight_ih) of a network under the hidden-norm switch (host)
-static inline int gru_off(const ActorNet& net, bool ln_hidden) {
-  return net.w_off[net.n_layers - 1] - gru_param_floats(net.dims[net.n_layers - 1], ln_hidden);
-}
 
 // the state of the workgroup's 64 rows -> LDS [k][row], masked: coalesced (thread t reads float t of the 64 x Hs block), clamped at the end
 __device__ __forceinline__ void gru_load_state(const float* __restrict__ state, const uint8_t* __restrict__ done, int row0, int rows, int Aw, int Hs, float* hs, int tid) {

@@ -80,6 +80,8 @@ enum { PROF_GEMM_L0 = 0, PROF_GEMM_REST, PROF_TORQUES, PROF_SIMULATE, PROF_POST,
 
 struct ShapeRow;
 typedef void (*substeps_fn_t)(const DevModel*, DevState, int, int, PostArgs);
+struct ActorVariant { const void* kern; const char* name; size_t (*lds_bytes)(int ldh, int Ha, int Hc); };      // a row of ACTOR_VARIANTS
+typedef void (*ppo_grad_fn_t)(const float*, const ActorShapes*, PpoTraj, int, int, int, int, int, int, float*, double*, PpoLoss);
 struct mqe_sim {
   mqe_sim_desc d;
   Switches sw;            // the environment switches as mqe_sim_create found them
@@ -127,18 +129,18 @@ struct mqe_sim {
   struct Actor {
     bool on = false;
     ActorShapes sh = {};          // the two networks, the norms' 1 / n, the two switches: what the four kernels of kernels_actor_critic.hpp read
+    const ActorVariant* variant = nullptr; size_t lds = 0;      // the rollout kernel of its switches, the LDS of a launch: chosen once, by mqe_actor_create
     int log_std_off = 0, n_params = 0, ldh = 0, relu = 0;
     float gain = 1.0f;
     bool vnorm = false;           // MQE_ACTOR_VALUE_NORM: MQE_VALUE_NORM_STATE floats behind the n_params trainable ones
-    bool ln() const { return sh.hidden || sh.feat; }      // MQE_ACTOR_LAYER_NORM / MQE_ACTOR_FEATURE_NORM: either one selects k_actor_ln and k_ln_grad
+    bool ln() const { return sh.hidden || sh.feat; }      // MQE_ACTOR_LAYER_NORM / MQE_ACTOR_FEATURE_NORM: either one selects the kernels with the norms
     float* params = nullptr;      // [n_params (+ MQE_VALUE_NORM_STATE)]
     float* stage = nullptr;       // [N, A', 3]
     // MQE_ACTOR_RECURRENT (kernels_gru.hpp): the widths of the two GRU cells and the live state [N A'][Ha + Hc], made zeroed with the actor and
-    // released with it; selects k_actor_gru / k_actor_gru_ln.  The actor's, like Adam's moments: never in state_bufs
-    bool gru = false;
-    int Ha = 0, Hc = 0;
+    // released with it; selects the recurrent kernels.  The actor's, like Adam's moments: never in state_bufs
+    bool gru = false; int Ha = 0, Hc = 0;
     float* hstate = nullptr;
-    ActorShapes* nets = nullptr;      // the shapes on the device, as the recurrent kernels read them (their kernel arguments stay short)
+    ActorShapes* nets = nullptr;      // `sh` on the device, THE image of every actor: the recurrent rollout kernels and the gradient kernels read it
   } act;
   // value normalisation (kernels_vn.hpp): the de-normalised values of mqe_gae [(T + 1) R'], the normalised targets of mqe_ppo_grad [T R'] and
   // k_vn_moments' partials; made by the first flagged call, grown when T grows, the actor's like the Ppo scratch
@@ -158,8 +160,8 @@ struct mqe_sim {
   struct Ppo {
     float* part = nullptr;
     double* pst = nullptr;
-    ActorShapes* nets = nullptr;      // the actor's shapes on the device, as k_ppo_grad / k_ln_grad read them
-    int rt = 0, lds_rows = 0, uw = 0;      // uw: rows of k_ln_grad's shared buffer of normalised inputs
+    ppo_grad_fn_t kern = nullptr;          // the gradient kernel of that tile, and the LDS of a launch
+    int rt = 0, lds_rows = 0, uw = 0, lds = 0;      // uw: rows of k_ln_grad's shared buffer of normalised inputs
     float* moments = nullptr;
     double* norm = nullptr;
   } ppo;
@@ -1561,9 +1563,17 @@ static void view_1d_f32(mqe_tensor_view* v, float* p, int n) {
 }
 
 // ---- on-device rollouts: mqe_actor_create / mqe_actor_params / mqe_rollout (include/mqe_hip.h) ---------------------------------
-// one network's dims[] against the limits; fills its offsets into the flat parameter buffer from *off on
+// the four rollout kernels, [recurrent][any norm]: symbol, name in a refusal, LDS rule.  mqe_actor_create picks an actor's row; nothing else chooses
+static const ActorVariant ACTOR_VARIANTS[2][2] = {
+  {{(const void*)k_actor, "k_actor", [](int ldh, int, int) { return actor_lds_bytes(ldh); }},
+   {(const void*)k_actor_ln, "k_actor_ln", [](int ldh, int, int) { return actor_ln_lds_bytes(ldh); }}},
+  {{(const void*)k_actor_gru, "k_actor_gru", [](int ldh, int Ha, int Hc) { return actor_gru_lds_bytes(ldh, Ha, Hc, false); }},
+   {(const void*)k_actor_gru_ln, "k_actor_gru_ln", [](int ldh, int Ha, int Hc) { return actor_gru_lds_bytes(ldh, Ha, Hc, true); }}},
+};
+struct NormWeight { int off, n; };      // a norm's weight in the flat parameter buffer: the n floats that start at 1
+// one network's dims[] against the limits; fills its offsets into the flat parameter buffer from *off on and notes every norm weight it passes
 static int actor_net_shape(const char* who, int layers, const int32_t* dims, int in, int out, bool ln_hidden, bool ln_feat, bool gru, ActorNet* net,
-                           float* inv_n, int* off, int* ldh) {
+                           float* inv_n, int* off, int* ldh, std::vector<NormWeight>* gammas) {
   if (layers < 1 || layers > MQE_ACTOR_MAX_LAYERS) return fail(-6, "mqe_actor_create: %s: 1 .. 4 Linear layers (MQE_ACTOR_MAX_LAYERS)", who);
   if (gru && layers < 2)
     return fail(-6, "mqe_actor_create: %s_layers: MQE_ACTOR_RECURRENT needs at least 2 Linear layers (the GRU cell sits between the last hidden layer and the output)", who);
@@ -1575,12 +1585,13 @@ static int actor_net_shape(const char* who, int layers, const int32_t* dims, int
     net->dims[l] = dims[l];
     if (l < layers && dims[l] > *ldh) *ldh = dims[l];
   }
-  if (ln_feat) *off += 2 * dims[0];                       // norm_in.weight, norm_in.bias
+  const auto norm = [&](int at, int n) { gammas->push_back({at, n}); return 2 * n; };      // weight, bias: the floats of a norm of n features
+  if (ln_feat) *off += norm(*off, dims[0]);               // norm_in.weight, norm_in.bias
   for (int l = 0; l < layers; l++) {
-    if (gru && l + 1 == layers) *off += gru_param_floats(dims[l], ln_hidden);      // the cell's block in front of the output layer's weight
+    if (gru && l + 1 == layers) { *off += gru_param_floats(dims[l], false); if (ln_hidden) *off += norm(*off, dims[l]); }      // the cell's block, then gru.norm, in front of the output layer
     net->w_off[l] = *off;
     *off += dims[l] * dims[l + 1] + dims[l + 1];
-    if (ln_hidden && l + 1 < layers) *off += 2 * dims[l + 1];      // norm.weight, norm.bias behind a hidden layer
+    if (ln_hidden && l + 1 < layers) *off += norm(*off, dims[l + 1]);      // norm.weight, norm.bias behind a hidden layer
     inv_n[l] = (float)(1.0 / (double)dims[l]);
   }
   return 0;
@@ -1591,13 +1602,12 @@ static void dfree(mqe_sim* s, void* p) {
     if (s->allocs[i] == p) { s->allocs.erase(s->allocs.begin() + i); break; }
   hipFree(p);           // waits for the launches that still read it
 }
+// every device buffer of an actor, listed once: what actor_release and a create that fails part-way free
+static void actor_free(mqe_sim* s, const mqe_sim::Actor& a) { for (void* p : {(void*)a.params, (void*)a.stage, (void*)a.hstate, (void*)a.nets}) dfree(s, p); }
 static void actor_release(mqe_sim* s) {
-  for (void* p : {(void*)s->act.params, (void*)s->act.stage, (void*)s->act.hstate, (void*)s->act.nets, (void*)s->ppo.part, (void*)s->ppo.pst, (void*)s->ppo.nets, (void*)s->ppo.moments, (void*)s->ppo.norm,
-                  (void*)s->vn.val, (void*)s->vn.tgt, (void*)s->vn.part})
-    dfree(s, p);
-  s->act = mqe_sim::Actor();
-  s->ppo = mqe_sim::Ppo();
-  s->vn = mqe_sim::Vn();
+  actor_free(s, s->act);
+  for (void* p : {(void*)s->ppo.part, (void*)s->ppo.pst, (void*)s->ppo.moments, (void*)s->ppo.norm, (void*)s->vn.val, (void*)s->vn.tgt, (void*)s->vn.part}) dfree(s, p);
+  s->act = mqe_sim::Actor(); s->ppo = mqe_sim::Ppo(); s->vn = mqe_sim::Vn();
 }
 // value-normalisation scratch of at least `need` floats: made on first use, replaced by a larger one when T grows (both synchronise)
 static int vn_scratch(mqe_sim* s, float** p, size_t* cap, size_t need) {
@@ -1608,8 +1618,8 @@ static int vn_scratch(mqe_sim* s, float** p, size_t* cap, size_t need) {
   *cap = need;
   return 0;
 }
-extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
-  if (!s || !sh) return fail(-1, "mqe_actor_create: null argument");
+// ---- mqe_actor_create, stage by stage as mqe_sim_create: the argument checks, the layout, the device buffers, the initial values -------------
+static int actor_check_args(const mqe_sim* s, const mqe_actor_shape* sh) {
   if (s->step_open) return fail(-8, "mqe_actor_create inside an open step");
   if (s->d.task == MQE_TASK_PLAIN) return fail(-6, "mqe_actor_create: this scene has no task observation (plain / stub wrapper): nothing for an actor to read");
   if (s->d.control_type != MQE_CTRL_C || s->cmd_general)
@@ -1617,72 +1627,62 @@ extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
   if (sh->obs_dim != s->D) return fail(-6, "mqe_actor_create: obs_dim differs from the width of this scene's MQE_T_WRAPPER_OBS");
   if (sh->obs_dim > MQE_ACTOR_MAX_OBS) return fail(-6, "mqe_actor_create: obs_dim above MQE_ACTOR_MAX_OBS (128)");
   if (sh->act_dim != 3) return fail(-6, "mqe_actor_create: act_dim must be 3");
-  const bool vnorm = (sh->activation & MQE_ACTOR_VALUE_NORM) != 0;
-  const bool ln_hidden = (sh->activation & MQE_ACTOR_LAYER_NORM) != 0, ln_feat = (sh->activation & MQE_ACTOR_FEATURE_NORM) != 0;
-  const bool gru = (sh->activation & MQE_ACTOR_RECURRENT) != 0;
   const int kind = sh->activation & ~(MQE_ACTOR_VALUE_NORM | MQE_ACTOR_LAYER_NORM | MQE_ACTOR_FEATURE_NORM | MQE_ACTOR_RECURRENT);
   if (kind != MQE_ACTOR_TANH && kind != MQE_ACTOR_RELU)
     return fail(-6, "mqe_actor_create: activation must be MQE_ACTOR_TANH or MQE_ACTOR_RELU (or-ed with MQE_ACTOR_LAYER_NORM, MQE_ACTOR_FEATURE_NORM, MQE_ACTOR_RECURRENT, MQE_ACTOR_VALUE_NORM or not)");
-  if (vnorm && sh->critic_layers == 0) return fail(-6, "mqe_actor_create: activation: MQE_ACTOR_VALUE_NORM needs a critic (the statistics are those of its targets)");
+  if ((sh->activation & MQE_ACTOR_VALUE_NORM) && sh->critic_layers == 0) return fail(-6, "mqe_actor_create: activation: MQE_ACTOR_VALUE_NORM needs a critic (the statistics are those of its targets)");
   if (not_finite(&sh->action_gain) || std::fabs(sh->action_gain) >= 1e30f) return fail(-6, "mqe_actor_create: action_gain is not finite");
-  mqe_sim::Actor a;
+  return 0;
+}
+// everything but the buffers: the networks against the limits, their offsets (the norm weights noted in `gammas`), the kernel and its LDS.  The last stage that can refuse
+static int actor_layout(const mqe_actor_shape* sh, mqe_sim::Actor* a, std::vector<NormWeight>* gammas) {
+  const bool ln_hidden = (sh->activation & MQE_ACTOR_LAYER_NORM) != 0, ln_feat = (sh->activation & MQE_ACTOR_FEATURE_NORM) != 0;
+  const bool gru = (sh->activation & MQE_ACTOR_RECURRENT) != 0;
   int off = 0, ldh = 0;
-  if (int rc = actor_net_shape("actor", sh->actor_layers, sh->actor_dims, sh->obs_dim, 3, ln_hidden, ln_feat, gru, &a.sh.actor, a.sh.inv_actor, &off, &ldh)) return rc;
+  if (int rc = actor_net_shape("actor", sh->actor_layers, sh->actor_dims, sh->obs_dim, 3, ln_hidden, ln_feat, gru, &a->sh.actor, a->sh.inv_actor, &off, &ldh, gammas)) return rc;
   if (sh->critic_layers != 0)
-    if (int rc = actor_net_shape("critic", sh->critic_layers, sh->critic_dims, sh->obs_dim, 1, ln_hidden, ln_feat, gru, &a.sh.critic, a.sh.inv_critic, &off, &ldh)) return rc;
-  a.log_std_off = off; a.n_params = off + 3; a.ldh = ldh; a.relu = kind == MQE_ACTOR_RELU; a.gain = sh->action_gain; a.vnorm = vnorm;
-  a.sh.hidden = ln_hidden; a.sh.feat = ln_feat;
-  const bool ln = ln_hidden || ln_feat;
-  if (gru) {
-    a.gru = true;
-    a.Ha = a.sh.actor.dims[a.sh.actor.n_layers - 1];
-    a.Hc = a.sh.critic.n_layers ? a.sh.critic.dims[a.sh.critic.n_layers - 1] : 0;
-  }
-  const size_t lds = gru ? actor_gru_lds_bytes(ldh, a.Ha, a.Hc, ln) : ln ? actor_ln_lds_bytes(ldh) : actor_lds_bytes(ldh);
-  if (gru && lds > GRU_LDS_LIMIT)
+    if (int rc = actor_net_shape("critic", sh->critic_layers, sh->critic_dims, sh->obs_dim, 1, ln_hidden, ln_feat, gru, &a->sh.critic, a->sh.inv_critic, &off, &ldh, gammas)) return rc;
+  a->log_std_off = off; a->n_params = off + 3; a->ldh = ldh; a->relu = (sh->activation & MQE_ACTOR_RELU) != 0; a->gain = sh->action_gain;
+  a->vnorm = (sh->activation & MQE_ACTOR_VALUE_NORM) != 0; a->sh.hidden = ln_hidden; a->sh.feat = ln_feat; a->gru = gru;
+  if (gru) { a->Ha = a->sh.actor.dims[a->sh.actor.n_layers - 1]; a->Hc = a->sh.critic.n_layers ? a->sh.critic.dims[a->sh.critic.n_layers - 1] : 0; }
+  a->variant = &ACTOR_VARIANTS[gru][a->ln()];
+  a->lds = a->variant->lds_bytes(ldh, a->Ha, a->Hc);
+  if (gru && a->lds > GRU_LDS_LIMIT)
     return fail(-6, "mqe_actor_create: a hidden width (or obs_dim) too large for MQE_ACTOR_RECURRENT: the two widest layer inputs and the state of both GRU cells "
                     "(2 max width + Ha + Hc + 4, + 32 with a norm, rows of 260 bytes) exceed the 160 KiB of a workgroup");
-  const void* kern = gru ? (ln ? (const void*)k_actor_gru_ln : (const void*)k_actor_gru) : ln ? (const void*)k_actor_ln : (const void*)k_actor;
-  if (lds > 48 * 1024 && hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(-5, gru ? (ln ? "mqe_actor_create: cannot reserve LDS for k_actor_gru_ln" : "mqe_actor_create: cannot reserve LDS for k_actor_gru") : ln ? "mqe_actor_create: cannot reserve LDS for k_actor_ln" : "mqe_actor_create: cannot reserve LDS for k_actor");
-  actor_release(s);
-  if (dalloc(s, &a.params, (size_t)a.n_params + (vnorm ? MQE_VALUE_NORM_STATE : 0)) || dalloc(s, &a.stage, (size_t)s->N * s->Aw * 3) ||
-      (gru && (dalloc(s, &a.hstate, (size_t)s->N * s->Aw * (a.Ha + a.Hc)) || dalloc(s, &a.nets, 1)))) {
-    dfree(s, a.params); dfree(s, a.stage); dfree(s, a.hstate);
-    return fail(-5, "device alloc failed (actor)");
-  }
-  if (gru && hipMemcpy(a.nets, &a.sh, sizeof a.sh, hipMemcpyHostToDevice) != hipSuccess) {
-    dfree(s, a.params); dfree(s, a.stage); dfree(s, a.hstate); dfree(s, a.nets);
-    return fail(-5, "mqe_actor_create: cannot write the shapes of the recurrent actor");
-  }
-  if (vnorm) {                         // (0, 0, 0) and its derived pair (0, 0.1f): sigma is never zero
-    float w[MQE_VALUE_NORM_STATE] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    vn_derive(w[0], w[1], w[2], &w[3], &w[4]);
-    if (hipMemcpy(a.params + a.n_params, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess) {
-      dfree(s, a.params); dfree(s, a.stage); dfree(s, a.hstate); dfree(s, a.nets);
-      return fail(-5, "mqe_actor_create: cannot write the value-normalisation state");
-    }
-  }
-  if (ln) {                            // every gamma starts at 1 (torch.nn.LayerNorm's own start); the rest of the buffer stays zero
-    std::vector<float> ones(MQE_ACTOR_MAX_HIDDEN > MQE_ACTOR_MAX_OBS ? MQE_ACTOR_MAX_HIDDEN : MQE_ACTOR_MAX_OBS, 1.0f);
-    bool ok = true;
-    for (const ActorNet* net : {&a.sh.actor, &a.sh.critic})
-      for (int l = 0; l < net->n_layers; l++)
-        if (l == 0 ? ln_feat : ln_hidden)
-          ok = ok && hipMemcpy(a.params + ln_gamma_off(*net, l), ones.data(), (size_t)net->dims[l] * 4, hipMemcpyHostToDevice) == hipSuccess;
-    if (gru && ln_hidden)              // gru.norm.weight, behind the cell's two biases
-      for (const ActorNet* net : {&a.sh.actor, &a.sh.critic})
-        if (net->n_layers) {
-          const int H = net->dims[net->n_layers - 1];
-          ok = ok && hipMemcpy(a.params + gru_off(*net, 1) + 6 * H * H + 6 * H, ones.data(), (size_t)H * 4, hipMemcpyHostToDevice) == hipSuccess;
-        }
-    if (!ok) {
-      dfree(s, a.params); dfree(s, a.stage); dfree(s, a.hstate); dfree(s, a.nets);
+  if (a->lds > 48 * 1024 && hipFuncSetAttribute(a->variant->kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a->lds) != hipSuccess)
+    return fail(-5, "mqe_actor_create: cannot reserve LDS for %s", a->variant->name);
+  return 0;
+}
+static int actor_buffers(mqe_sim* s, mqe_sim::Actor* a) {
+  const size_t rows = (size_t)s->N * s->Aw;
+  const bool failed = dalloc(s, &a->params, (size_t)a->n_params + (a->vnorm ? MQE_VALUE_NORM_STATE : 0)) || dalloc(s, &a->stage, rows * 3) ||
+                      (a->gru && dalloc(s, &a->hstate, rows * (a->Ha + a->Hc))) || dalloc(s, &a->nets, 1);
+  return failed ? fail(-5, "device alloc failed (actor)") : 0;
+}
+// the buffers come zeroed (the parameters, the recurrent state); what does not start at zero:
+static int actor_initial_values(const mqe_sim::Actor& a, const std::vector<NormWeight>& gammas) {
+  if (hipMemcpy(a.nets, &a.sh, sizeof a.sh, hipMemcpyHostToDevice) != hipSuccess) return fail(-5, "mqe_actor_create: cannot write the shapes of the recurrent actor");
+  float w[MQE_VALUE_NORM_STATE] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};      // (0, 0, 0) and its derived pair (0, 0.1f): sigma is never zero
+  vn_derive(w[0], w[1], w[2], &w[3], &w[4]);
+  if (a.vnorm && hipMemcpy(a.params + a.n_params, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(-5, "mqe_actor_create: cannot write the value-normalisation state");
+  // every gamma starts at 1 (torch.nn.LayerNorm's own start): norm_in.weight, every hidden norm.weight and gru.norm.weight, as the layout noted them
+  const std::vector<float> ones(MQE_ACTOR_MAX_HIDDEN > MQE_ACTOR_MAX_OBS ? MQE_ACTOR_MAX_HIDDEN : MQE_ACTOR_MAX_OBS, 1.0f);
+  for (const NormWeight& g : gammas)
+    if (hipMemcpy(a.params + g.off, ones.data(), (size_t)g.n * 4, hipMemcpyHostToDevice) != hipSuccess)
       return fail(-5, "mqe_actor_create: cannot write the layer norms' weights");
-    }
-  }
-  a.on = true;
-  s->act = a;
+  return 0;
+}
+extern "C" int mqe_actor_create(mqe_sim* s, const mqe_actor_shape* sh) {
+  if (!s || !sh) return fail(-1, "mqe_actor_create: null argument");
+  if (int rc = actor_check_args(s, sh)) return rc;
+  mqe_sim::Actor a; std::vector<NormWeight> gammas;
+  if (int rc = actor_layout(sh, &a, &gammas)) return rc;
+  actor_release(s);                    // behind every check that can refuse: a refused create leaves the previous actor installed
+  int rc = actor_buffers(s, &a); if (rc == 0) rc = actor_initial_values(a, gammas);
+  if (rc) { actor_free(s, a); return rc; }
+  a.on = true; s->act = a;
   return 0;
 }
 extern "C" int mqe_actor_params(mqe_sim* s, mqe_tensor_view* v) {
@@ -1700,15 +1700,11 @@ static void launch_actor(mqe_sim* s, const float* obs, float* actions, float* lo
   k.log_std_off = a.log_std_off;
   k.rows = s->N * s->Aw; k.D = s->D; k.Aw = s->Aw; k.ldh = a.ldh; k.relu = a.relu; k.deterministic = (flags & MQE_ROLLOUT_DETERMINISTIC) ? 1 : 0;
   k.gain = a.gain; k.seed = (uint32_t)s->d.seed; k.genv0 = (uint32_t)s->d.env_id_offset; k.count = MQE_RNG_ACTOR + (uint32_t)s->n_post_steps;
-  const dim3 grid((k.rows + ACT_ROWS - 1) / ACT_ROWS);
-  if (a.gru) {                         // the done bytes of the row the observation comes from sit behind its R' rewards
-    GruArgs g;
-    g.state = a.hstate; g.record = record; g.done = (const uint8_t*)(obs + (size_t)k.rows * (k.D + 1)); g.Ha = a.Ha; g.Hc = a.Hc;
-    hipLaunchKernelGGL(a.ln() ? k_actor_gru_ln : k_actor_gru, grid, dim3(ACT_THREADS), actor_gru_lds_bytes(a.ldh, a.Ha, a.Hc, a.ln()), q, k, g, (const float*)a.params,
-                       (const ActorShapes*)a.nets);
-    return;
-  }
-  hipLaunchKernelGGL(a.ln() ? k_actor_ln : k_actor, grid, dim3(ACT_THREADS), a.ln() ? actor_ln_lds_bytes(a.ldh) : actor_lds_bytes(a.ldh), q, k);
+  GruArgs g = {a.hstate, record, (const uint8_t*)(obs + (size_t)k.rows * (k.D + 1)), a.Ha, a.Hc};      // the done bytes of the row the observation comes from sit behind its R' rewards
+  const float* params = a.params; const ActorShapes* nets = a.nets;
+  // one launch for both signatures: it reads as many entries as its kernel has arguments -- the plain kernels (ActorArgs) one, the recurrent ones all four
+  void* args[] = {&k, &g, &params, &nets};
+  (void)hipLaunchKernel(a.variant->kern, dim3((k.rows + ACT_ROWS - 1) / ACT_ROWS), dim3(ACT_THREADS), args, a.lds, q);      // launched() reports a failure
 }
 extern "C" int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* packed_dev, long long row_stride, float* actions_dev, float* logp_dev,
                            float* value_dev, int flags, void* stream) {
@@ -1810,8 +1806,13 @@ extern "C" int mqe_gae(mqe_sim* s, int T, const float* packed_dev, long long row
 }
 
 // ---- mqe_ppo_grad / mqe_ppo_optimizer / mqe_ppo_adam (include/mqe_hip.h; kernels_ppo.hpp) ------------------------------------------------------
-// the gradient kernel of an actor: with or without the norms, by the row tile its shapes allow
-static auto ppo_grad_kernel(bool ln, int rt) { return ln ? (rt == 64 ? k_ln_grad<64> : k_ln_grad<32>) : (rt == 64 ? k_ppo_grad<64> : k_ppo_grad<32>); }
+// the gradient kernels, [no norm]: symbol per row tile [64, 32], name in a refusal, the refusal of shapes that do not fit.  The first mqe_ppo_grad of an actor picks;
+// nothing else chooses.  Norms first and 64 first: the compiler emits the instances in the order they are named here, and this order keeps the code object as it was
+static const struct PpoGradVariant { ppo_grad_fn_t kern[2]; const char* name; const char* no_fit; } PPO_GRAD_VARIANTS[2] = {
+  {{k_ln_grad<64>, k_ln_grad<32>}, "k_ln_grad",
+   "mqe_ppo_grad: the layer outputs of one network, the widest norm's input and k_ln_grad's statistics do not fit the LDS even at 32 rows"},
+  {{k_ppo_grad<64>, k_ppo_grad<32>}, "k_ppo_grad", "mqe_ppo_grad: the layer outputs of one network do not fit the LDS even at 32 rows"},
+};
 extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long long row_stride, const float* actions_dev, const float* logp_dev,
                             const float* value_dev, const float* adv_dev, const float* ret_dev, const int32_t* index_dev, long long first,
                             long long count, const mqe_ppo_loss* loss, int flags, float* grad_dev, float* stats_dev, void* stream) {
@@ -1852,21 +1853,19 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
                                                {vn_state, MQE_VALUE_NORM_STATE * 4, "the value-normalisation state"}}, 2)) return rc;
   if (vn && (vn_scratch(s, &s->vn.tgt, &s->vn.tgt_cap, n) || (!s->vn.part && dalloc(s, &s->vn.part, (size_t)VN_PART))))
     return fail(-5, "device alloc failed (mqe_ppo_grad value-normalisation scratch)");
-  const bool ln = a.ln();
-  if (!s->ppo.part) {                  // once per actor: the row tile of its shapes, the scratch (hipMalloc synchronises)
+  if (!s->ppo.part) {                  // once per actor: the row tile of its shapes and the kernel of that tile, the scratch (hipMalloc synchronises)
     mqe_sim::Ppo& p = s->ppo;
+    const bool ln = a.ln(); const PpoGradVariant& var = PPO_GRAD_VARIANTS[!ln];
     const int plain_rows = ppo_lds_rows(a.sh.actor, a.sh.critic, s->D);
     p.lds_rows = ln ? ln_lds_rows(a.sh.actor, a.sh.critic, s->D, a.sh.hidden, a.sh.feat) : plain_rows;
     p.uw = ln ? p.lds_rows - plain_rows - LN_STAT - LN_PART : 0;
     p.rt = ppo_lds_bytes(p.lds_rows, 64) <= PPO_LDS_LIMIT ? 64 : 32;
-    const int lds = (int)ppo_lds_bytes(p.lds_rows, p.rt);
-    if (lds > PPO_LDS_LIMIT)
-      return fail(-5, ln ? "mqe_ppo_grad: the layer outputs of one network, the widest norm's input and k_ln_grad's statistics do not fit the LDS even at 32 rows"
-                         : "mqe_ppo_grad: the layer outputs of one network do not fit the LDS even at 32 rows");
-    const hipError_t e = hipFuncSetAttribute((const void*)ppo_grad_kernel(ln, p.rt), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (lds > 48 * 1024 && e != hipSuccess) return fail(-5, ln ? "mqe_ppo_grad: cannot reserve LDS for k_ln_grad" : "mqe_ppo_grad: cannot reserve LDS for k_ppo_grad");
-    if (dalloc(s, &p.pst, (size_t)PPO_MAX_WG * PPO_PST) || dalloc(s, &p.nets, 1) ||
-        hipMemcpy(p.nets, &a.sh, sizeof a.sh, hipMemcpyHostToDevice) != hipSuccess || dalloc(s, &p.part, (size_t)PPO_MAX_WG * a.n_params, 0)) {
+    p.lds = (int)ppo_lds_bytes(p.lds_rows, p.rt);
+    if (p.lds > PPO_LDS_LIMIT) return fail(-5, var.no_fit);
+    p.kern = var.kern[p.rt == 32];
+    const hipError_t e = hipFuncSetAttribute((const void*)p.kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
+    if (p.lds > 48 * 1024 && e != hipSuccess) return fail(-5, "mqe_ppo_grad: cannot reserve LDS for %s", var.name);
+    if (dalloc(s, &p.pst, (size_t)PPO_MAX_WG * PPO_PST) || dalloc(s, &p.part, (size_t)PPO_MAX_WG * a.n_params, 0)) {
       p.part = nullptr;                // the next call tries again; what was allocated is released with the handle
       return fail(-5, "device alloc failed (mqe_ppo_grad scratch)");
     }
@@ -1878,7 +1877,6 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   PpoLoss ls;
   ls.clip = loss->clip_ratio; ls.value_coef = loss->value_coef; ls.entropy_coef = loss->entropy_coef; ls.value_clip = loss->value_clip;
   ls.inv_m = (float)(1.0 / (double)count); ls.clip_value = (flags & MQE_PPO_CLIP_VALUE) ? 1 : 0;
-  const size_t lds = ppo_lds_bytes(s->ppo.lds_rows, rt);
   if (vn) {                            // [update the state from the minibatch's returns,] normalise them into the scratch the loss reads
     const long long per = (long long)VN_THREADS * VN_PER, want = (count + per - 1) / per;
     const int gm = (int)(want < VN_MAX_WG ? want : VN_MAX_WG);
@@ -1891,7 +1889,7 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   PpoTraj tr;
   tr.packed = packed_dev; tr.stride = row_stride; tr.rows = (int)rows; tr.n_total = (long long)n; tr.actions = actions_dev; tr.logp_old = logp_dev;
   tr.value = value_dev; tr.adv = adv_dev; tr.ret = ret_dev; tr.index = index_dev; tr.first = first; tr.count = count;
-  hipLaunchKernelGGL(ppo_grad_kernel(ln, rt), dim3(G), dim3(ACT_THREADS), lds, q, (const float*)a.params, (const ActorShapes*)s->ppo.nets, tr, a.log_std_off,
+  hipLaunchKernelGGL(s->ppo.kern, dim3(G), dim3(ACT_THREADS), s->ppo.lds, q, (const float*)a.params, (const ActorShapes*)a.nets, tr, a.log_std_off,
                      a.n_params, s->D, s->ppo.lds_rows, s->ppo.uw, a.relu, s->ppo.part, s->ppo.pst, ls);
   hipLaunchKernelGGL(k_ppo_reduce, dim3((a.n_params + PPO_REDUCE_THREADS - 1) / PPO_REDUCE_THREADS), dim3(PPO_REDUCE_THREADS), 0, q, (const float*)s->ppo.part,
                      (const double*)s->ppo.pst, G, a.n_params, a.log_std_off, count, ls.value_coef, ls.entropy_coef, (const float*)a.params, grad_dev, stats_dev);

@@ -171,20 +171,21 @@ class FusedTaskWrapper(EmptyWrapper):
         across rollout() calls and zeroes it wherever a step ended an episode; sync_actor() / pull_actor() copy the cells too.  ppo_update()
         refuses such an actor: the learner runs back-propagation through time on the torch twins (rollout(record_hidden=True), then
         RecurrentMLP.evaluate from traj.hidden) and sync_actor()s the result."""
-        from mqe.utils.actor_net import RecurrentMLP, mlp_spec, recurrent_spec
+        from mqe.utils.actor_net import RecurrentMLP, actor_tensors, mlp_spec, recurrent_spec
         D = self.observation_space.shape[0]
         no_norms = {"feature": None, "hidden": []}
-        spec = lambda module, what, out: mlp_spec(module, what, D, out, layer_norm=True) if layer_norm else (*mlp_spec(module, what, D, out), no_norms)
-        a_rnn = c_rnn = None
-        if recurrent:
-            spec = lambda module, what, out: recurrent_spec(module, what, D, out, layer_norm=layer_norm)[:4]
-            a_rnn, c_rnn = actor_module, critic_module
-        else:
+
+        def spec(module, what, out):           # (dims, activation, linears, norms) of a network, whichever of the three forms it comes in
+            if recurrent:
+                return recurrent_spec(module, what, D, out, layer_norm=layer_norm)[:4]
+            found = mlp_spec(module, what, D, out, layer_norm=layer_norm)
+            return found if layer_norm else (*found, no_norms)
+        if not recurrent:
             for what, m in (("actor", actor_module), ("critic", critic_module)):
                 if isinstance(m, RecurrentMLP):
                     raise ValueError(f"{what}: a RecurrentMLP without recurrent=True; the engine evaluates both networks recurrent (set_actor(..., recurrent=True)) or neither")
         a_dims, a_act, a_lin, a_norm = spec(actor_module, "actor", 3)
-        c_dims, c_act, c_lin, c_norm = (None, None, [], a_norm)
+        c_dims, c_act, c_lin, c_norm = (None, None, [], no_norms)
         if critic_module is not None:
             c_dims, c_act, c_lin, c_norm = spec(critic_module, "critic", 1)
             if a_act is not None and c_act is not None and a_act != c_act:
@@ -206,71 +207,38 @@ class FusedTaskWrapper(EmptyWrapper):
         if recurrent:
             norm_kw["recurrent"] = True
         eng.create_actor(a_dims, c_dims, activation=a_act or c_act or "tanh", action_gain=action_gain, value_norm=value_norm, **norm_kw)
-        self._actor_src = (a_lin, c_lin, log_std)
-        self._actor_norms = (a_norm, c_norm if critic_module is not None else no_norms)
-        self._actor_rnns = (a_rnn, c_rnn)
+        a_rnn, c_rnn = (actor_module, critic_module) if recurrent else (None, None)
+        # every tensor the modules share with the engine under the engine's name, the actor's then the critic's; log_std; whether there is a critic
+        self._actor = (actor_tensors("actor", a_lin, a_norm, a_rnn) + actor_tensors("critic", c_lin, c_norm, c_rnn), log_std, critic_module is not None)
         self._recurrent, self._hidden_next, self._hidden_saved = bool(recurrent), "live", "zeros"       # create_actor zeroed the engine's state
         self.sync_actor()
 
     def sync_actor(self):
         """copies the modules' current parameters into the engine's buffer again (after an optimiser step); device to device when the
         modules live on the engine's device, no synchronisation"""
-        if getattr(self, "_actor_src", None) is None:
+        if getattr(self, "_actor", None) is None:
             raise RuntimeError("sync_actor: no actor (set_actor first)")
-        a_lin, c_lin, log_std = self._actor_src
+        tensors, log_std, _ = self._actor
         views = self._rollout_engine("sync_actor").actor_params()
         with torch.no_grad():
-            for who, lin in (("actor", a_lin), ("critic", c_lin)):
-                for l, layer in enumerate(lin):
-                    views[f"{who}.{l}.weight"].copy_(layer.weight.detach(), non_blocking=True)
-                    views[f"{who}.{l}.bias"].copy_(layer.bias.detach(), non_blocking=True)
-            for name, norm in self._norm_modules():
-                views[f"{name}.weight"].copy_(norm.weight.detach(), non_blocking=True)
-                views[f"{name}.bias"].copy_(norm.bias.detach(), non_blocking=True)
-            for name, t in self._gru_tensors():
+            for name, t in tensors:
                 views[name].copy_(t.detach(), non_blocking=True)
             if log_std is None:
                 views["log_std"].zero_()
             else:
                 views["log_std"].copy_(torch.as_tensor(log_std).detach().reshape(3).to(torch.float32), non_blocking=True)
 
-    def _gru_tensors(self):
-        """(the engine's name, the torch tensor) of every GRU cell and its norm that set_actor(recurrent=True) found: <who>.gru.<name>"""
-        for who, m in zip(("actor", "critic"), self._actor_rnns):
-            if m is None:
-                continue
-            for name in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
-                yield f"{who}.gru.{name}", getattr(m.rnn, name + "_l0")
-            if m.norm is not None:
-                yield f"{who}.gru.norm.weight", m.norm.weight
-                yield f"{who}.gru.norm.bias", m.norm.bias
-
-    def _norm_modules(self):
-        """(the engine's name, the torch.nn.LayerNorm) of every norm set_actor(layer_norm=True) found: <who>.norm_in, <who>.<layer>.norm"""
-        for who, norms in zip(("actor", "critic"), self._actor_norms):
-            if norms["feature"] is not None:
-                yield f"{who}.norm_in", norms["feature"]
-            for l, norm in enumerate(norms["hidden"]):
-                yield f"{who}.{l}.norm", norm
-
     def pull_actor(self):
         """the reverse of sync_actor(): the engine's parameter buffer -> the torch modules and log_std given to set_actor, device to device
         when they live on the engine's device, no synchronisation.  After ppo_update() the ENGINE holds the master copy of the parameters:
         pull_actor() brings the modules up to date, and a sync_actor() before it would overwrite the update with the modules' old values"""
         eng = self._rollout_engine("pull_actor")
-        if getattr(self, "_actor_src", None) is None:
+        if getattr(self, "_actor", None) is None:
             raise RuntimeError("pull_actor: no actor (set_actor first)")
-        a_lin, c_lin, log_std = self._actor_src
+        tensors, log_std, _ = self._actor
         views = eng.actor_params()
         with torch.no_grad():
-            for who, lin in (("actor", a_lin), ("critic", c_lin)):
-                for l, layer in enumerate(lin):
-                    layer.weight.copy_(views[f"{who}.{l}.weight"], non_blocking=True)
-                    layer.bias.copy_(views[f"{who}.{l}.bias"], non_blocking=True)
-            for name, norm in self._norm_modules():
-                norm.weight.copy_(views[f"{name}.weight"], non_blocking=True)
-                norm.bias.copy_(views[f"{name}.bias"], non_blocking=True)
-            for name, t in self._gru_tensors():
+            for name, t in tensors:
                 t.copy_(views[name], non_blocking=True)
             if isinstance(log_std, torch.Tensor):
                 log_std.copy_(views["log_std"].reshape(log_std.shape), non_blocking=True)
@@ -284,9 +252,9 @@ class FusedTaskWrapper(EmptyWrapper):
         its returns (reward units) into the running statistics and the value loss compares the critic with the returns normalised by the new
         (mu, sigma): statistics entry 1 (mean L_v) is in normalised units."""
         eng = self._rollout_engine("ppo_update")
-        if getattr(self, "_actor_src", None) is None:
+        if getattr(self, "_actor", None) is None:
             raise RuntimeError("ppo_update: no actor (set_actor first)")
-        if not self._actor_src[1]:
+        if not self._actor[2]:
             raise ValueError("ppo_update: the loss has a value term, and the actor was set without a critic (set_actor(actor, critic))")
         return eng.ppo_update(traj, **kw)
 
@@ -318,9 +286,9 @@ class FusedTaskWrapper(EmptyWrapper):
         if env.has_overrides:
             raise NotImplementedError("rollout runs entirely inside the engine: a Go1 subclass that overrides any of "
                                       + " / ".join(env._PLUGIN_POINTS) + " is stepped through Go1.step()")
-        if getattr(self, "_actor_src", None) is None:
+        if getattr(self, "_actor", None) is None:
             raise RuntimeError("rollout: no actor (set_actor first)")
-        if gamma is not None and not self._actor_src[1]:
+        if gamma is not None and not self._actor[2]:
             raise ValueError("rollout(gamma=...): advantages need values, and the actor was set without a critic (set_actor(actor, critic))")
         obs0 = getattr(self, "_last_obs", None)
         if getattr(self, "_last_obs_epoch", None) != getattr(env, "_obs_epoch", 0):

@@ -86,6 +86,23 @@ def recurrent_spec(module, what, in_dim, out_dim, layer_norm=False):
     return dims, act, linears[:-1] + [head], norms, module
 
 
+def actor_tensors(who, linears, norms, rnn=None):
+    """[(the engine's name, the torch tensor)] of one network, "actor" or "critic", from what mlp_spec / recurrent_spec found for it (its Linear
+    layers, its norms, its RecurrentMLP or None): the names and the order of abi.actor_param_layout, which is the module's own parameters() order."""
+    def both(name, m):
+        return [(f"{who}.{name}weight", m.weight), (f"{who}.{name}bias", m.bias)]
+    out = both("norm_in.", norms["feature"]) if norms["feature"] is not None else []
+    for l, layer in enumerate(linears):
+        if rnn is not None and l + 1 == len(linears):          # the cell's block in front of the output layer
+            out += [(f"{who}.gru.{name}", getattr(rnn.rnn, name + "_l0")) for name in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+            if rnn.norm is not None:
+                out += both("gru.norm.", rnn.norm)
+        out += both(f"{l}.", layer)
+        if l < len(norms["hidden"]):
+            out += both(f"{l}.norm.", norms["hidden"][l])
+    return out
+
+
 def mlp_spec(module, what, in_dim, out_dim, layer_norm=False):
     """(dims, activation, linears) of a torch.nn.Sequential of Linear / Tanh / ReLU: Linear layers with a bias, one activation -- the same
     kind everywhere -- between two of them, a linear output; dims = [in_dim, hidden ..., out_dim], activation "tanh" / "relu" (None for a
