@@ -647,9 +647,27 @@ int mqe_ppo_adam(mqe_sim* s, const float* grad_dev, long long step, float lr, fl
  *   With either flag row_stride >= P4 + R' Hs (still a multiple of 4), -6 naming row_stride otherwise; either flag on a handle without the bit: -6
  *   naming flags.  Without the flags tails are neither read nor written and the rule for row_stride is the old one.  Refusals enqueue nothing.
  * Resets that happen in mqe_step calls between rollouts are not seen by the state: it is masked by the done bytes of trajectory rows only.
- * mqe_gae, mqe_ppo_optimizer, mqe_ppo_adam and mqe_rollout_time_outs work unchanged.  mqe_ppo_grad REFUSES a recurrent handle (-6, nothing enqueued or
- *   written): back-propagation through time is not built in the engine yet -- the next step; until then a learner differentiates the torch twin
- *   (mqe.utils.actor_net.RecurrentMLP) over the recorded trajectory and copies the parameters back, or hands mqe_ppo_adam a gradient in this layout.
+ * mqe_gae, mqe_ppo_optimizer, mqe_ppo_adam and mqe_rollout_time_outs work unchanged.  mqe_ppo_grad on a recurrent handle is back-propagation through time
+ *   over CHUNKS of a trajectory recorded with MQE_ROLLOUT_HIDDEN_RECORD (csrc/kernels_bptt.hpp: k_bptt_grad, k_bptt_ln_grad, k_bptt_expand; OpenRL /
+ *   MAPPO's recurrent generator at data_chunk_length = L).  Three more constants, stated here, defined in csrc/kernels_bptt.hpp, mirrored in
+ *   mqe/engine/abi.py (tests/test_bptt.py holds the three statements together); a C caller passes the numbers:
+ *     MQE_PPO_BPTT = 32   MQE_PPO_CHUNK_SHIFT = 8   MQE_PPO_MAX_CHUNK = 64
+ *   flags = MQE_PPO_BPTT | L << MQE_PPO_CHUNK_SHIFT (bits 8 .. 15 hold L, 1 <= L <= MQE_PPO_MAX_CHUNK), or-ed with the other mqe_ppo_grad flags.  T must
+ *   be a multiple of L.  The trajectory is (T / L) R' chunks, chunk c = (t0 / L) R' + r covering steps t0 .. t0 + L - 1 of row r; index_dev / first /
+ *   count then mean CHUNKS (index values are clamped into [0, (T / L) R')), the minibatch is count L samples and the loss's 1 / M is 1 / (count L); the
+ *   loss, its kinks and the six statistics are those stated at mqe_ppo_grad, over those samples.  Step 0 of a chunk starts both cells from the tail of
+ *   packed row t0 masked by that row's done byte of the row's env (data: no gradient reaches it); step j > 0 starts from the h' computed at step j - 1
+ *   with the CURRENT parameters, masked by packed row t0 + j's done byte: the rule of mqe_rollout above.  The gradient of step j's input state is
+ *   carried to step j - 1 times that mask; the one step 0 produces is dropped.  The same bits on every run.  Under MQE_PPO_VALUE_NORM[_UPDATE] the
+ *   minibatch's returns are those of its count L samples.  -6, naming the argument, nothing enqueued or written: the bit or any of bits 8 .. 15 on a
+ *   handle without MQE_ACTOR_RECURRENT (flags); L = 0 or L > 64 (flags); T not a multiple of L (T); row_stride < P4 + R' Hs (row_stride); first + count
+ *   beyond the chunks when there is no index.  A recurrent handle called WITHOUT the bit stays refused (-6, nothing enqueued or written): its gradient
+ *   is back-propagation through time, which has to be asked for with the chunk length.
+ *   Scratch, made by the first such call, grown when L grows (that call synchronises once, as the other first calls do), released with the actor: the
+ *   workgroups' input states, 256 workgroups x L x max(Ha, Hc) x the row tile (64 or 32 chunks) floats -- 64 steps x 128 units x 64 rows x 4 B x 256 =
+ *   537 MB at the largest, 42 MB in the usual case L = 10, H = 64 -- and, under value normalisation, the count L sample numbers of the minibatch.
+ *   The first call refuses (-5, naming the cell's width) a shape whose LDS need (csrc/kernels_bptt.hpp: k_ln_grad's rows + 7 per unit of the wider
+ *   cell) does not fit 160 KiB at 32 chunks a workgroup; every shape with all widths <= 64 and obs_dim <= 128 fits, with and without the norms.
  * mqe_actor_create refuses (-6, naming the width) a recurrent shape whose LDS need, (2 max layer input + 4 + Ha + Hc, + 32 with a norm) rows of 260
  *   bytes, exceeds the 160 KiB of a workgroup; every shape with all widths and obs_dim <= 128 fits.  A handle created without the bit launches
  *   exactly the kernels it launched before. */

@@ -1,7 +1,7 @@
 // kernels_gru.hpp -- the recurrent actor-critic of an on-device rollout (MQE_ACTOR_RECURRENT; include/mqe_hip.h): the GRU cell, its carried state,
 // its constants and its LDS rule.  The walk of kernels_actor_critic.hpp switches it in at compile time (GRU): k_actor_gru and k_actor_gru_ln are the
-// instantiations with it, and a handle created without the bit never launches them.  There is no gradient kernel yet: mqe_ppo_grad refuses a
-// recurrent handle (back-propagation through time is a kernel of its own).
+// instantiations with it, and a handle created without the bit never launches them.  The gradient is a kernel of its own: back-propagation through
+// time over chunks of the recorded trajectory, k_bptt_grad / k_bptt_ln_grad (kernels_bptt.hpp; mqe_ppo_grad with MQE_PPO_BPTT), built on this file's cell.
 //
 // THE NETWORK, per network of the handle (each has its own cell and its own state; H = the width of the last hidden layer):
 //     hidden layers (with their norms) -> x (H) -> GRU cell H -> H -> [LayerNorm(H) under the hidden norm: ln_rows] -> the output Linear
@@ -82,7 +82,7 @@ __device__ __forceinline__ void gru_store_state(const float* hs, float* __restri
 }
 
 // the three gate chains of GRU_NB units over one operand: acc[j][g] = b[g H + u_j] + sum over k ascending of W[g H + u_j][k] v[k]
-template <bool VEC4>
+template <bool VEC4, int LD = ACT_LD>
 __device__ __forceinline__ void gru_chains(const float* __restrict__ W, const float* __restrict__ b, int H, int u0, const float* v, float (&acc)[GRU_NB][3], int lane) {
   const float* w[GRU_NB][3];
 #pragma unroll
@@ -107,7 +107,7 @@ __device__ __forceinline__ void gru_chains(const float* __restrict__ W, const fl
           wb[j][g] = *reinterpret_cast<const float4*>(__builtin_assume_aligned(w[j][g] + k + 4, 16));
         }
 #pragma unroll
-      for (int q = 0; q < 8; q++) xv[q] = v[(k + q) * ACT_LD + lane];
+      for (int q = 0; q < 8; q++) xv[q] = v[(k + q) * LD + lane];
 #pragma unroll
       for (int j = 0; j < GRU_NB; j++)
 #pragma unroll
@@ -128,7 +128,7 @@ __device__ __forceinline__ void gru_chains(const float* __restrict__ W, const fl
 #pragma unroll
         for (int q = 0; q < 4; q++) wv[j][g][q] = w[j][g][k + q];
 #pragma unroll
-    for (int q = 0; q < 4; q++) xv[q] = v[(k + q) * ACT_LD + lane];
+    for (int q = 0; q < 4; q++) xv[q] = v[(k + q) * LD + lane];
 #pragma unroll
     for (int j = 0; j < GRU_NB; j++)
 #pragma unroll
@@ -137,7 +137,7 @@ __device__ __forceinline__ void gru_chains(const float* __restrict__ W, const fl
         for (int q = 0; q < 4; q++) acc[j][g] = fmaf(wv[j][g][q], xv[q], acc[j][g]);
   }
   for (; k < H; k++) {
-    const float xk = v[k * ACT_LD + lane];
+    const float xk = v[k * LD + lane];
 #pragma unroll
     for (int j = 0; j < GRU_NB; j++)
 #pragma unroll
@@ -148,32 +148,38 @@ __device__ __forceinline__ void gru_chains(const float* __restrict__ W, const fl
 __device__ __forceinline__ float gru_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // the cell for the 64 rows of the workgroup: x, h (LDS, [H][ACT_LD]) -> y = h' (LDS, another buffer: every wavefront reads all of h).  No barrier.
-template <bool VEC4>
-__device__ __forceinline__ void gru_cell(const float* __restrict__ p, int H, const float* x, const float* h, float* y, int lane, int wave) {
+// LD: the LDS row stride (the gradient's 32-row tiles use 33).  gates (the gradient's backward sweep, kernels_bptt.hpp; null: not kept): [4 H][LD], r, z, n, gh_n
+template <bool VEC4, int LD = ACT_LD>
+__device__ __forceinline__ void gru_cell(const float* __restrict__ p, int H, const float* x, const float* h, float* y, int lane, int wave, float* gates = nullptr) {
   const float* Wih = p;
   const float* Whh = p + (size_t)3 * H * H;
   const float* bih = p + (size_t)6 * H * H;
   const float* bhh = bih + 3 * H;
   for (int u0 = wave * GRU_NB; u0 < H; u0 += ACT_WAVES * GRU_NB) {
     float gi[GRU_NB][3], gh[GRU_NB][3];
-    gru_chains<VEC4>(Wih, bih, H, u0, x, gi, lane);
-    gru_chains<VEC4>(Whh, bhh, H, u0, h, gh, lane);
+    gru_chains<VEC4, LD>(Wih, bih, H, u0, x, gi, lane);
+    gru_chains<VEC4, LD>(Whh, bhh, H, u0, h, gh, lane);
 #pragma unroll
     for (int j = 0; j < GRU_NB; j++) {
       const float r = gru_sigmoid(gi[j][0] + gh[j][0]);
       const float z = gru_sigmoid(gi[j][1] + gh[j][1]);
       const float n = tanhf(fmaf(r, gh[j][2], gi[j][2]));
-      const float hp = h[min(u0 + j, H - 1) * ACT_LD + lane];
-      if (u0 + j < H) y[(u0 + j) * ACT_LD + lane] = fmaf(z, hp - n, n);
+      const float hp = h[min(u0 + j, H - 1) * LD + lane];
+      if (u0 + j < H) y[(u0 + j) * LD + lane] = fmaf(z, hp - n, n);
+      if (gates != nullptr && u0 + j < H) {
+        float* gu = gates + (u0 + j) * LD + lane;
+        gu[0] = r; gu[(size_t)H * LD] = z; gu[(size_t)2 * H * LD] = n; gu[(size_t)3 * H * LD] = gh[j][2];
+      }
     }
   }
 }
 // the cell in front of layer l = n_layers - 1 of a network: its block by its offset, and the ONE alignment test that picks the 16-byte loads (both
 // matrices start on the same residue).  -> the offset of gru.norm.weight
+template <int LD = ACT_LD>
 __device__ __forceinline__ int gru_layer(const ActorNet& net, int l, int hidden, const float* __restrict__ params, const float* x, const float* h, float* y, int lane,
-                                         int wave) {
+                                         int wave, float* gates = nullptr) {
   const int H = net.dims[l], off = net.w_off[l] - gru_param_floats(H, hidden != 0);
-  if (((H | off) & 3) == 0) gru_cell<true>(params + off, H, x, h, y, lane, wave);
-  else gru_cell<false>(params + off, H, x, h, y, lane, wave);
+  if (((H | off) & 3) == 0) gru_cell<true, LD>(params + off, H, x, h, y, lane, wave, gates);
+  else gru_cell<false, LD>(params + off, H, x, h, y, lane, wave, gates);
   return off + 6 * H * H + 6 * H;
 }

@@ -111,9 +111,10 @@ __device__ __forceinline__ void ln_again(const float* a, float* u, int n, const 
 }
 
 // backward of one norm: du ([n][LD]) and the stored a, mu, rstd -> the workgroup's partial dgamma / dbeta (gG, gB) and, with DX, delta over a in place.
-// dgamma / dbeta of feature k: the tile's sum over the rows (= lanes) of du * xhat / du by the xor butterfly RT / 2, ..., 1 (k_gae's), in the wavefront
+// DX: 0 the gamma / beta gradients alone (the feature norm), 1 delta = da times the activation derivative of a, 2 da alone (the norm behind the GRU cell:
+// its input is the cell's h', no activation; kernels_bptt.hpp).  dgamma / dbeta of feature k: the tile's sum over the rows (= lanes) of du * xhat / du by the xor butterfly RT / 2, ..., 1 (k_gae's), in the wavefront
 // that owns k; lane j keeps the sums of the chunk's feature j and adds them to the running partial with one load and one store
-template <int LD, int RT, bool DX>
+template <int LD, int RT, int DX>
 __device__ __forceinline__ void ln_back(float* a, const float* du, int n, const float* __restrict__ g, float inv_n, const float* stat, float* part,
                                         float* __restrict__ gG, float* __restrict__ gB, bool first, int relu, int row, int lane, int wave) {
   const int c = (n + ACT_WAVES - 1) / ACT_WAVES;
@@ -158,7 +159,7 @@ __device__ __forceinline__ void ln_back(float* a, const float* du, int n, const 
     const float av = a[k * LD + row];
     const float xh = (av - mu) * rstd;
     const float da = rstd * fmaf(-xh, m2, du[k * LD + row] * g[k] - m1);
-    a[k * LD + row] = relu ? (av > 0.0f ? da : 0.0f) : da * fmaf(-av, av, 1.0f);
+    a[k * LD + row] = DX == 2 ? da : relu ? (av > 0.0f ? da : 0.0f) : da * fmaf(-av, av, 1.0f);
   }
   __syncthreads();
 }

@@ -81,7 +81,6 @@ enum { PROF_GEMM_L0 = 0, PROF_GEMM_REST, PROF_TORQUES, PROF_SIMULATE, PROF_POST,
 struct ShapeRow;
 typedef void (*substeps_fn_t)(const DevModel*, DevState, int, int, PostArgs);
 struct ActorVariant { const void* kern; const char* name; size_t (*lds_bytes)(int ldh, int Ha, int Hc); };      // a row of ACTOR_VARIANTS
-typedef void (*ppo_grad_fn_t)(const float*, const ActorShapes*, PpoTraj, int, int, int, int, int, int, float*, double*, PpoLoss);
 struct mqe_sim {
   mqe_sim_desc d;
   Switches sw;            // the environment switches as mqe_sim_create found them
@@ -160,8 +159,12 @@ struct mqe_sim {
   struct Ppo {
     float* part = nullptr;
     double* pst = nullptr;
-    ppo_grad_fn_t kern = nullptr;          // the gradient kernel of that tile, and the LDS of a launch
+    const void* kern = nullptr;            // the gradient kernel of that tile, and the LDS of a launch
     int rt = 0, lds_rows = 0, uw = 0, lds = 0;      // uw: rows of k_ln_grad's shared buffer of normalised inputs
+    // a recurrent actor under MQE_PPO_BPTT (kernels_bptt.hpp): the workgroups' input states [PPO_MAX_WG][L][max(Ha, Hc)][rt] and the minibatch's
+    // expanded sample list [count L] for the value normalisation; made by the first call that needs them, grown when L (count) grows
+    float* hscr = nullptr; size_t hscr_cap = 0;
+    float* idx = nullptr; size_t idx_cap = 0;      // int32 words, allocated as floats
     float* moments = nullptr;
     double* norm = nullptr;
   } ppo;
@@ -1606,10 +1609,11 @@ static void dfree(mqe_sim* s, void* p) {
 static void actor_free(mqe_sim* s, const mqe_sim::Actor& a) { for (void* p : {(void*)a.params, (void*)a.stage, (void*)a.hstate, (void*)a.nets}) dfree(s, p); }
 static void actor_release(mqe_sim* s) {
   actor_free(s, s->act);
-  for (void* p : {(void*)s->ppo.part, (void*)s->ppo.pst, (void*)s->ppo.moments, (void*)s->ppo.norm, (void*)s->vn.val, (void*)s->vn.tgt, (void*)s->vn.part}) dfree(s, p);
+  for (void* p : {(void*)s->ppo.part, (void*)s->ppo.pst, (void*)s->ppo.moments, (void*)s->ppo.norm, (void*)s->ppo.hscr, (void*)s->ppo.idx, (void*)s->vn.val, (void*)s->vn.tgt, (void*)s->vn.part}) dfree(s, p);
   s->act = mqe_sim::Actor(); s->ppo = mqe_sim::Ppo(); s->vn = mqe_sim::Vn();
 }
-// value-normalisation scratch of at least `need` floats: made on first use, replaced by a larger one when T grows (both synchronise)
+// scratch of at least `need` floats (value normalisation; the recurrent gradient's states and sample list): made on first use, replaced by a larger one when
+// T (L) grows (both synchronise)
 static int vn_scratch(mqe_sim* s, float** p, size_t* cap, size_t need) {
   if (*p && *cap >= need) return 0;
   dfree(s, *p);
@@ -1806,12 +1810,17 @@ extern "C" int mqe_gae(mqe_sim* s, int T, const float* packed_dev, long long row
 }
 
 // ---- mqe_ppo_grad / mqe_ppo_optimizer / mqe_ppo_adam (include/mqe_hip.h; kernels_ppo.hpp) ------------------------------------------------------
-// the gradient kernels, [no norm]: symbol per row tile [64, 32], name in a refusal, the refusal of shapes that do not fit.  The first mqe_ppo_grad of an actor picks;
-// nothing else chooses.  Norms first and 64 first: the compiler emits the instances in the order they are named here, and this order keeps the code object as it was
-static const struct PpoGradVariant { ppo_grad_fn_t kern[2]; const char* name; const char* no_fit; } PPO_GRAD_VARIANTS[2] = {
-  {{k_ln_grad<64>, k_ln_grad<32>}, "k_ln_grad",
-   "mqe_ppo_grad: the layer outputs of one network, the widest norm's input and k_ln_grad's statistics do not fit the LDS even at 32 rows"},
-  {{k_ppo_grad<64>, k_ppo_grad<32>}, "k_ppo_grad", "mqe_ppo_grad: the layer outputs of one network do not fit the LDS even at 32 rows"},
+// the gradient kernels, [recurrent][no norm]: symbol per row tile [64, 32], name in a refusal, the refusal of shapes that do not fit.  The first mqe_ppo_grad of an
+// actor picks; nothing else chooses.  Norms first and 64 first: the compiler emits the instances in the order they are named here, and this order keeps the code
+// object as it was.  One launch for both signatures (launch_actor's way): a kernel reads as many entries of the argument list as it has arguments
+static const struct PpoGradVariant { const void* kern[2]; const char* name; const char* no_fit; } PPO_GRAD_VARIANTS[2][2] = {
+  {{{(const void*)k_ln_grad<64>, (const void*)k_ln_grad<32>}, "k_ln_grad",
+    "mqe_ppo_grad: the layer outputs of one network, the widest norm's input and k_ln_grad's statistics do not fit the LDS even at 32 rows"},
+   {{(const void*)k_ppo_grad<64>, (const void*)k_ppo_grad<32>}, "k_ppo_grad", "mqe_ppo_grad: the layer outputs of one network do not fit the LDS even at 32 rows"}},
+  {{{(const void*)k_bptt_ln_grad<64>, (const void*)k_bptt_ln_grad<32>}, "k_bptt_ln_grad",
+    "mqe_ppo_grad: flags: MQE_PPO_BPTT: the layer outputs of one network, the norms' rows and 7 rows per unit of the wider GRU cell (width %s) do not fit the LDS even at 32 rows"},
+   {{(const void*)k_bptt_grad<64>, (const void*)k_bptt_grad<32>}, "k_bptt_grad",
+    "mqe_ppo_grad: flags: MQE_PPO_BPTT: the layer outputs of one network and 7 rows per unit of the wider GRU cell (width %s) do not fit the LDS even at 32 rows"}},
 };
 extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long long row_stride, const float* actions_dev, const float* logp_dev,
                             const float* value_dev, const float* adv_dev, const float* ret_dev, const int32_t* index_dev, long long first,
@@ -1820,19 +1829,33 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   if (!packed_dev || !actions_dev || !logp_dev || !value_dev || !adv_dev || !ret_dev || !loss || !grad_dev)
     return fail(-1, "mqe_ppo_grad: packed_dev, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, loss and grad_dev are required");
   if (!s->act.on) return fail(-6, "mqe_ppo_grad: no actor (mqe_actor_create)");
-  if (s->act.gru)
-    return fail(-6, "mqe_ppo_grad: the actor was created with MQE_ACTOR_RECURRENT: back-propagation through time is not built in the engine yet "
-                    "(train the torch twin on the recorded trajectory and copy the parameters back)");
+  // MQE_PPO_BPTT (kernels_bptt.hpp): bits 8 .. 15 hold the chunk length L; index_dev / first / count are chunks
+  const bool bptt = (flags & MQE_PPO_BPTT) != 0;
+  const int L = bptt ? (flags >> MQE_PPO_CHUNK_SHIFT) & 0xff : 1;
+  if (!s->act.gru && (flags & (MQE_PPO_BPTT | (0xff << MQE_PPO_CHUNK_SHIFT))))
+    return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_BPTT and a chunk length in bits 8 .. 15 need an actor created with MQE_ACTOR_RECURRENT");
+  if (s->act.gru && !bptt)
+    return fail(-6, "mqe_ppo_grad: the actor was created with MQE_ACTOR_RECURRENT: its gradient is back-propagation through time over chunks of the recorded "
+                    "trajectory: pass flags = MQE_PPO_BPTT | L << MQE_PPO_CHUNK_SHIFT (32 | L << 8, 1 <= L <= 64; index_dev / first / count then mean chunks)");
+  if (bptt && (L < 1 || L > MQE_PPO_MAX_CHUNK))
+    return fail(-6, "mqe_ppo_grad: flags: the chunk length L in bits 8 .. 15 must be 1 .. MQE_PPO_MAX_CHUNK (64)");
+  flags &= ~(MQE_PPO_BPTT | (0xff << MQE_PPO_CHUNK_SHIFT));
   if (s->act.sh.critic.n_layers == 0) return fail(-6, "mqe_ppo_grad: the actor was created without a critic: the loss has a value term");
   TrajShape ts;
   if (int rc = traj_shape(s, "mqe_ppo_grad", T, row_stride, &ts)) return rc;
   if (int rc = check_aligned("mqe_ppo_grad", {{packed_dev, 16}, {actions_dev, 4}, {logp_dev, 4}, {value_dev, 4}, {adv_dev, 4}, {ret_dev, 4}, {index_dev, 4},
                                               {grad_dev, 4}, {stats_dev, 4}}, "packed_dev: 16 bytes, the others: 4")) return rc;
   const size_t rows = ts.rows, n = ts.n, pf = ts.packed_floats;
+  const size_t tail = (pf + 3) / 4 * 4, hs = (size_t)(s->act.Ha + s->act.Hc);
+  if (bptt && T % L != 0) return fail(-6, "mqe_ppo_grad: T must be a multiple of the chunk length L (flags bits 8 .. 15)");
+  if (bptt && row_stride < (long long)(tail + rows * hs))
+    return fail(-6, "mqe_ppo_grad: row_stride: with MQE_PPO_BPTT a row holds the packed length rounded up to a multiple of 4 and the R' (Ha + Hc) recorded state floats behind it");
+  const size_t n_chunks = n / (size_t)L;      // (T / L) R'; without the bit: the samples
   if (count < 1) return fail(-6, "mqe_ppo_grad: count must be at least 1");
   if (first < 0) return fail(-6, "mqe_ppo_grad: first must not be negative");
   if (first > (1LL << 40) || count > (1LL << 40)) return fail(-6, "mqe_ppo_grad: first / count beyond any trajectory");
-  if (!index_dev && first + count > (long long)n) return fail(-6, "mqe_ppo_grad: first + count exceeds the T x R' samples of the trajectory");
+  if (!index_dev && first + count > (long long)n_chunks)
+    return fail(-6, bptt ? "mqe_ppo_grad: first + count exceeds the (T / L) x R' chunks of the trajectory" : "mqe_ppo_grad: first + count exceeds the T x R' samples of the trajectory");
   if (negative_or_not_finite(&loss->clip_ratio)) return fail(-6, "mqe_ppo_grad: clip_ratio must be finite and not negative");
   if (negative_or_not_finite(&loss->value_coef)) return fail(-6, "mqe_ppo_grad: value_coef must be finite and not negative");
   if (negative_or_not_finite(&loss->entropy_coef)) return fail(-6, "mqe_ppo_grad: entropy_coef must be finite and not negative");
@@ -1846,7 +1869,7 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   const mqe_sim::Actor& a = s->act;
   float* vn_state = vn ? a.params + a.n_params : nullptr;
   if (int rc = check_disjoint("mqe_ppo_grad", {{stats_dev, MQE_PPO_STATS * 4, "stats_dev"}, {grad_dev, (size_t)a.n_params * 4, "grad_dev"},
-                                               {packed_dev, ((size_t)T * row_stride + pf) * 4, "packed_dev"}, {actions_dev, n * 12, "actions_dev"},
+                                               {packed_dev, ((size_t)T * row_stride + (bptt ? tail + rows * hs : pf)) * 4, "packed_dev"}, {actions_dev, n * 12, "actions_dev"},
                                                {logp_dev, n * 4, "logp_dev"}, {value_dev, (n + rows) * 4, "value_dev"}, {adv_dev, n * 4, "adv_dev"},
                                                {ret_dev, n * 4, "ret_dev"}, {index_dev, (size_t)(first + count) * 4, "index_dev"},
                                                {a.params, (size_t)a.n_params * 4, "the parameter buffer"},
@@ -1855,15 +1878,17 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
     return fail(-5, "device alloc failed (mqe_ppo_grad value-normalisation scratch)");
   if (!s->ppo.part) {                  // once per actor: the row tile of its shapes and the kernel of that tile, the scratch (hipMalloc synchronises)
     mqe_sim::Ppo& p = s->ppo;
-    const bool ln = a.ln(); const PpoGradVariant& var = PPO_GRAD_VARIANTS[!ln];
-    const int plain_rows = ppo_lds_rows(a.sh.actor, a.sh.critic, s->D);
+    const bool ln = a.ln(); const PpoGradVariant& var = PPO_GRAD_VARIANTS[a.gru][!ln];
+    const int plain_rows = ppo_lds_rows(a.sh.actor, a.sh.critic, s->D), hm = a.Ha > a.Hc ? a.Ha : a.Hc;
     p.lds_rows = ln ? ln_lds_rows(a.sh.actor, a.sh.critic, s->D, a.sh.hidden, a.sh.feat) : plain_rows;
     p.uw = ln ? p.lds_rows - plain_rows - LN_STAT - LN_PART : 0;
-    p.rt = ppo_lds_bytes(p.lds_rows, 64) <= PPO_LDS_LIMIT ? 64 : 32;
-    p.lds = (int)ppo_lds_bytes(p.lds_rows, p.rt);
-    if (p.lds > PPO_LDS_LIMIT) return fail(-5, var.no_fit);
+    if (a.gru) p.lds_rows = bptt_lds_rows(p.lds_rows, hm, ln);
+    const auto bytes = [&](int rt) { return a.gru ? bptt_lds_bytes(p.lds_rows, rt) : ppo_lds_bytes(p.lds_rows, rt); };
+    p.rt = bytes(64) <= PPO_LDS_LIMIT ? 64 : 32;
+    p.lds = (int)bytes(p.rt);
+    if (p.lds > PPO_LDS_LIMIT) return fail(-5, var.no_fit, std::to_string(hm).c_str());
     p.kern = var.kern[p.rt == 32];
-    const hipError_t e = hipFuncSetAttribute((const void*)p.kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
+    const hipError_t e = hipFuncSetAttribute(p.kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
     if (p.lds > 48 * 1024 && e != hipSuccess) return fail(-5, "mqe_ppo_grad: cannot reserve LDS for %s", var.name);
     if (dalloc(s, &p.pst, (size_t)PPO_MAX_WG * PPO_PST) || dalloc(s, &p.part, (size_t)PPO_MAX_WG * a.n_params, 0)) {
       p.part = nullptr;                // the next call tries again; what was allocated is released with the handle
@@ -1874,25 +1899,40 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   const int rt = s->ppo.rt;
   const long long tiles = (count + rt - 1) / rt;
   const int G = (int)(tiles < PPO_MAX_WG ? tiles : PPO_MAX_WG);
+  const long long M = count * L;       // the samples of the minibatch
+  const int hm = a.Ha > a.Hc ? a.Ha : a.Hc;
+  // the recurrent gradient's scratch: made on first use, grown when L (count) grows; that call synchronises once
+  if (bptt && (vn_scratch(s, &s->ppo.hscr, &s->ppo.hscr_cap, (size_t)PPO_MAX_WG * L * hm * rt) || (vn && vn_scratch(s, &s->ppo.idx, &s->ppo.idx_cap, (size_t)M))))
+    return fail(-5, "device alloc failed (mqe_ppo_grad back-propagation-through-time scratch)");
   PpoLoss ls;
   ls.clip = loss->clip_ratio; ls.value_coef = loss->value_coef; ls.entropy_coef = loss->entropy_coef; ls.value_clip = loss->value_clip;
-  ls.inv_m = (float)(1.0 / (double)count); ls.clip_value = (flags & MQE_PPO_CLIP_VALUE) ? 1 : 0;
+  ls.inv_m = (float)(1.0 / (double)M); ls.clip_value = (flags & MQE_PPO_CLIP_VALUE) ? 1 : 0;
   if (vn) {                            // [update the state from the minibatch's returns,] normalise them into the scratch the loss reads
-    const long long per = (long long)VN_THREADS * VN_PER, want = (count + per - 1) / per;
+    const int32_t* vi = index_dev; long long vf = first;
+    if (bptt) {                        // the chunks' samples as a flat list: what the two kernels read as their index
+      const long long we = (M + BPTT_EXPAND_THREADS - 1) / BPTT_EXPAND_THREADS;
+      hipLaunchKernelGGL(k_bptt_expand, dim3((int)(we < 2048 ? we : 2048)), dim3(BPTT_EXPAND_THREADS), 0, q, index_dev, first, count, (long long)n_chunks, (int)rows, L,
+                         (int32_t*)s->ppo.idx);
+      vi = (const int32_t*)s->ppo.idx; vf = 0;
+    }
+    const long long per = (long long)VN_THREADS * VN_PER, want = (M + per - 1) / per;
     const int gm = (int)(want < VN_MAX_WG ? want : VN_MAX_WG);
     if (vn_update)
-      hipLaunchKernelGGL(k_vn_moments, dim3(gm), dim3(VN_THREADS), 0, q, ret_dev, index_dev, first, count, (long long)n, (const float*)vn_state, s->vn.part);
-    hipLaunchKernelGGL(k_vn_apply, dim3((int)(want < 2048 ? want : 2048)), dim3(VN_THREADS), 0, q, ret_dev, index_dev, first, count, (long long)n, vn_state,
+      hipLaunchKernelGGL(k_vn_moments, dim3(gm), dim3(VN_THREADS), 0, q, ret_dev, vi, vf, M, (long long)n, (const float*)vn_state, s->vn.part);
+    hipLaunchKernelGGL(k_vn_apply, dim3((int)(want < 2048 ? want : 2048)), dim3(VN_THREADS), 0, q, ret_dev, vi, vf, M, (long long)n, vn_state,
                        vn_update ? (const double*)s->vn.part : nullptr, gm, s->vn.tgt);
     ret_dev = s->vn.tgt;
   }
   PpoTraj tr;
   tr.packed = packed_dev; tr.stride = row_stride; tr.rows = (int)rows; tr.n_total = (long long)n; tr.actions = actions_dev; tr.logp_old = logp_dev;
   tr.value = value_dev; tr.adv = adv_dev; tr.ret = ret_dev; tr.index = index_dev; tr.first = first; tr.count = count;
-  hipLaunchKernelGGL(s->ppo.kern, dim3(G), dim3(ACT_THREADS), s->ppo.lds, q, (const float*)a.params, (const ActorShapes*)a.nets, tr, a.log_std_off,
-                     a.n_params, s->D, s->ppo.lds_rows, s->ppo.uw, a.relu, s->ppo.part, s->ppo.pst, ls);
+  BpttArgs bt = {(long long)tail, (long long)(rows * (size_t)(s->D + 1)), (long long)n_chunks, L, s->Aw, a.Ha, a.Hc, hm};
+  const float* params = a.params; const ActorShapes* nets = a.nets;
+  int log_std_off = a.log_std_off, n_params = a.n_params, D = s->D, relu = a.relu;
+  void* args[] = {&params, &nets, &tr, &log_std_off, &n_params, &D, &s->ppo.lds_rows, &s->ppo.uw, &relu, &s->ppo.part, &s->ppo.pst, &ls, &bt, &s->ppo.hscr};
+  (void)hipLaunchKernel(s->ppo.kern, dim3(G), dim3(ACT_THREADS), args, s->ppo.lds, q);      // launched() reports a failure
   hipLaunchKernelGGL(k_ppo_reduce, dim3((a.n_params + PPO_REDUCE_THREADS - 1) / PPO_REDUCE_THREADS), dim3(PPO_REDUCE_THREADS), 0, q, (const float*)s->ppo.part,
-                     (const double*)s->ppo.pst, G, a.n_params, a.log_std_off, count, ls.value_coef, ls.entropy_coef, (const float*)a.params, grad_dev, stats_dev);
+                     (const double*)s->ppo.pst, G, a.n_params, a.log_std_off, M, ls.value_coef, ls.entropy_coef, (const float*)a.params, grad_dev, stats_dev);
   return launched();
 }
 

@@ -131,6 +131,10 @@ ACTOR_LAYER_NORM, ACTOR_FEATURE_NORM = 2, 4
 ACTOR_RECURRENT = 16
 ROLLOUT_HIDDEN_IN, ROLLOUT_HIDDEN_RECORD = 2, 4
 ACT_LD, LN_PART, GRU_LDS_LIMIT = 65, 32, 160 * 1024      # csrc/kernels_actor.hpp, kernels_ln.hpp, kernels_gru.hpp: what the LDS rule below is made of
+# the recurrent gradient (include/mqe_hip.h states the values, csrc/kernels_bptt.hpp defines them): mqe_ppo_grad flags bit 5 -- back-propagation through
+# time over chunks; index / first / count are chunks --, the shift of the chunk length L in flags (bits 8 .. 15) and the largest L
+PPO_BPTT, PPO_CHUNK_SHIFT, PPO_MAX_CHUNK = 32, 8, 64
+LN_STAT, BPTT_CELL_ROWS, BPTT_LDS_LIMIT = 8, 7, 160 * 1024      # csrc/kernels_ln.hpp, kernels_bptt.hpp: what the LDS rule of the recurrent gradient is made of
 RNG_ACTOR = 0x70000000          # csrc/mqe_common.hpp MQE_RNG_ACTOR: `count` of the actor's draws = RNG_ACTOR + post-physics steps so far
 
 
@@ -151,6 +155,31 @@ def actor_gru_lds_bytes(actor_dims, critic_dims=None, layer_norm=False, feature_
     ldh = max(int(d) for dims in nets for d in dims[:-1])
     hs = sum(int(dims[-2]) for dims in nets)
     return (2 * ldh + 4 + (LN_PART if layer_norm or feature_norm else 0) + hs) * ACT_LD * 4
+
+
+def bptt_lds_rows(actor_dims, critic_dims, layer_norm=False, feature_norm=False):
+    """LDS rows of k_bptt_grad / k_bptt_ln_grad for a recurrent shape (csrc/kernels_bptt.hpp, THE RULE): the observation, every hidden output of the
+    larger network and 4 output rows (ppo_lds_rows); with a norm the widest normalised vector, LN_STAT statistics and LN_PART partial rows
+    (ln_lds_rows) and 2 rows for the norm behind the cell; BPTT_CELL_ROWS rows per unit of the wider cell."""
+    nets = [[int(d) for d in actor_dims], [int(d) for d in critic_dims]]
+    D = nets[0][0]
+    rows = D + max(sum(dims[1:-1]) for dims in nets) + 4
+    if layer_norm or feature_norm:
+        uw = max([D if feature_norm else 0] + ([w for dims in nets for w in dims[1:-1]] if layer_norm else []))
+        rows += uw + LN_STAT + LN_PART + 2
+    return rows + BPTT_CELL_ROWS * max(dims[-2] for dims in nets)
+
+
+def bptt_lds_bytes(rows, rt):
+    """csrc/kernels_bptt.hpp bptt_lds_bytes: rows of rt + 1 floats, the sample numbers of the step and of the chunks, the done bytes of two steps, the running statistics"""
+    return (rows * (rt + 1) + 2 + 20 * 64) * 4
+
+
+def bptt_row_tile(actor_dims, critic_dims, layer_norm=False, feature_norm=False):
+    """the chunks a workgroup of the recurrent gradient kernel walks at a time: 64 where the LDS rule fits BPTT_LDS_LIMIT, else 32; None where the
+    shape does not fit at 32 either (the first ppo_grad(chunk_length=...) refuses it, naming the cell's width)"""
+    rows = bptt_lds_rows(actor_dims, critic_dims, layer_norm, feature_norm)
+    return next((rt for rt in (64, 32) if bptt_lds_bytes(rows, rt) <= BPTT_LDS_LIMIT), None)
 
 
 def actor_param_layout(actor_dims, critic_dims=None, value_norm=False, layer_norm=False, feature_norm=False, recurrent=False):

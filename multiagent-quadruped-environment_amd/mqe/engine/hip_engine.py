@@ -191,7 +191,8 @@ class HipEngine(EngineBase):
         adam_step and ppo_update work unchanged on such an actor.  recurrent (abi.ACTOR_RECURRENT; csrc/kernels_gru.hpp states the arithmetic): a
         torch.nn.GRU cell H -> H (H = the last hidden width; every network needs a hidden layer) in front of the output layer of both networks,
         followed by a LayerNorm(H) under layer_norm; the engine carries the state across rollout calls, zeroed here and reset wherever a step ended
-        an episode.  rollout, gae and adam_step work on such an actor; ppo_grad and ppo_update refuse it (no back-propagation through time yet)."""
+        an episode.  rollout, gae and adam_step work on such an actor; ppo_grad and ppo_update take it with chunk_length= (back-propagation through time over
+        chunks of a trajectory recorded with rollout(record_hidden=True)) and refuse it without."""
         actor_dims = [int(x) for x in actor_dims]
         critic_dims = [int(x) for x in critic_dims] if critic_dims is not None else []
         for who, dims in (("actor", actor_dims), ("critic", critic_dims)):
@@ -248,10 +249,24 @@ class HipEngine(EngineBase):
             return 0
         return a["actor_dims"][-2] + (a["critic_dims"][-2] if a["critic_dims"] else 0)
 
-    def _recurrent_refusal(self, who):
-        if self._actor is not None and self._actor["recurrent"]:
-            raise NotImplementedError(f"{who}: the actor is recurrent, and back-propagation through time is not built in the engine yet (mqe_ppo_grad refuses it): "
-                                      "train the torch twin (mqe.utils.actor_net.RecurrentMLP.evaluate from traj.hidden) and sync_actor()")
+    def _chunks(self, who, traj, chunk_length):
+        """chunk_length of ppo_grad / ppo_update against the actor and the trajectory: -> L (0: a plain actor, samples), or the refusal"""
+        rec = self._actor is not None and self._actor["recurrent"]
+        if chunk_length is None:
+            if rec:
+                raise NotImplementedError(f"{who}: the actor is recurrent: its gradient is back-propagation through time over chunks of the trajectory, which "
+                                          f"the engine runs when asked for: pass chunk_length=L (T a multiple of L; rollout(record_hidden=True))")
+            return 0
+        L = int(chunk_length)
+        if not rec:
+            raise ValueError(f"{who}: chunk_length= needs a recurrent actor (create_actor(recurrent=True)); a plain actor's minibatches are samples")
+        if not 1 <= L <= abi.PPO_MAX_CHUNK:
+            raise ValueError(f"{who}: chunk_length must be 1 .. {abi.PPO_MAX_CHUNK} (abi.PPO_MAX_CHUNK), got {L}")
+        if traj.hidden is None:
+            raise ValueError(f"{who}: traj.hidden is None: the chunks start from the recorded state (rollout(record_hidden=True))")
+        if int(traj.T) % L != 0:
+            raise ValueError(f"{who}: the trajectory's T = {int(traj.T)} steps are not a multiple of chunk_length = {L}")
+        return L
 
     def rollout(self, T, obs0=None, deterministic=False, out=None, time_outs=False, hidden=None, record_hidden=False):
         """T steps of actor -> step inside the engine, one host call, no synchronisation (mqe_rollout).  obs0: the (N, A', D) observation to
@@ -362,7 +377,7 @@ class HipEngine(EngineBase):
 
     # ---- the PPO update on the engine's own parameters (mqe_ppo_grad / mqe_ppo_optimizer / mqe_ppo_adam; csrc/kernels_ppo.hpp) ---------------
     def ppo_grad(self, traj, index=None, first=0, count=None, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=None, out=None, value_norm=None,
-                 update_value_norm=False):
+                 update_value_norm=False, chunk_length=None):
         """Gradient of rsl_rl's clipped-surrogate PPO loss over one minibatch of a Rollout that HipEngine.gae has filled, with respect to the
         engine's actor-critic parameters (mqe_ppo_grad; csrc/kernels_ppo.hpp states the loss): two launches, no synchronisation (the first
         call after create_actor allocates its scratch and synchronises once), the same bits on every run.  The minibatch is
@@ -373,9 +388,14 @@ class HipEngine(EngineBase):
         value_norm (None: as the actor was created): the value loss compares against the minibatch's returns normalised with the current
         (mu, sigma) (abi.PPO_VALUE_NORM: one more launch; mean L_v is then in normalised units, traj.returns stays as it is);
         update_value_norm: the minibatch's returns are folded into the statistics first (abi.PPO_VALUE_NORM_UPDATE: one more launch) -- the
-        only call that changes actor_params()["value_norm"]."""
+        only call that changes actor_params()["value_norm"].
+        chunk_length=L (a recurrent actor, which is refused without it; abi.PPO_BPTT, csrc/kernels_bptt.hpp): truncated back-propagation through
+        time, OpenRL's recurrent generator at data_chunk_length = L.  The trajectory (rollout(record_hidden=True), T a multiple of L) is cut into
+        (T / L) * N * A' chunks, chunk c = (t0 / L) * N * A' + row covering steps t0 .. t0 + L - 1 of that row; index / first / count are CHUNK
+        numbers, the loss averages over the count * L samples, and a chunk starts from the masked recorded state traj.hidden[t0] (data, no
+        gradient) and carries the state it computes with the current parameters through its steps, reset where traj.done says so."""
         self._need_actor()
-        self._recurrent_refusal("ppo_grad")
+        L = self._chunks("ppo_grad", traj, chunk_length)
         vn = self._value_norm("ppo_grad", value_norm)
         if update_value_norm and not vn:
             raise ValueError("ppo_grad: update_value_norm=True needs value normalisation (an actor created with value_norm=True)")
@@ -391,7 +411,7 @@ class HipEngine(EngineBase):
             _need_f32(f"traj.{name}", getattr(traj, name), shp)
         _need_packed(traj)
         n_params = self.actor_params()["flat"].numel()
-        total = T * N * Aw
+        total = T * N * Aw // max(L, 1)
         if index is not None:
             if not (index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.dim() == 1):
                 raise ValueError("index must be a contiguous one-dimensional int32 device tensor")
@@ -410,7 +430,8 @@ class HipEngine(EngineBase):
         self._invoke("ppo_grad", T, _ptr(traj.packed), int(traj.packed.stride(0)), _ptr(traj.actions), _ptr(traj.logp), _ptr(traj.value),
                      _ptr(traj.advantages), _ptr(traj.returns), _ptr(index), first, count, C.byref(loss),
                      (abi.PPO_CLIP_VALUE if value_clip is not None else 0) | (abi.PPO_VALUE_NORM if vn else 0) |
-                     (abi.PPO_VALUE_NORM_UPDATE if update_value_norm else 0), _ptr(grad), _ptr(stats), self._stream())
+                     (abi.PPO_VALUE_NORM_UPDATE if update_value_norm else 0) | ((abi.PPO_BPTT | L << abi.PPO_CHUNK_SHIFT) if L else 0),
+                     _ptr(grad), _ptr(stats), self._stream())
         return grad, stats
 
     def optimizer_state(self):
@@ -435,21 +456,24 @@ class HipEngine(EngineBase):
                      float(max_grad_norm) if max_grad_norm is not None else 0.0, _ptr(norm_out), self._stream())
 
     def ppo_update(self, traj, epochs, minibatches, lr, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=None, betas=(0.9, 0.999), eps=1e-8,
-                   max_grad_norm=None, generator=None, value_norm=None):
+                   max_grad_norm=None, generator=None, value_norm=None, chunk_length=None):
         """The PPO update of one trajectory inside the engine: per epoch one device permutation of the T x N x A' samples
         (torch.randperm(..., device=..., generator=generator)), cut into `minibatches` equal slices (the last takes the remainder), and per
         slice ppo_grad + adam_step -- 2 to 4 launches, no synchronisation, no copy.  The step count lives on this object (ppo_step) and carries
         over between calls.  -> the (epochs, minibatches, 6) statistics tensor (ppo_grad's, before each step).  Afterwards the engine's buffer
         is the master copy of the parameters.  value_norm (None: as the actor was created): every minibatch first folds its returns into
-        the running statistics, then normalises them with the new (mu, sigma) -- OpenRL's ValueNorm order; 1 or 2 more launches a slice."""
-        self._recurrent_refusal("ppo_update")
+        the running statistics, then normalises them with the new (mu, sigma) -- OpenRL's ValueNorm order; 1 or 2 more launches a slice.
+        chunk_length=L (a recurrent actor, refused without it; ppo_grad's): what is permuted and cut into minibatches are the (T / L) * N * A'
+        chunks, and `minibatches` is bounded by their number; one launch more a slice under value normalisation."""
+        self._need_actor()
+        L = self._chunks("ppo_update", traj, chunk_length)
         vn = self._value_norm("ppo_update", value_norm)
         epochs, minibatches = int(epochs), int(minibatches)
         T = int(traj.T)
         N, Aw, _ = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
-        total = T * N * Aw
+        total = T * N * Aw // max(L, 1)
         if epochs < 1 or minibatches < 1 or minibatches > total:
-            raise ValueError(f"ppo_update: epochs >= 1 and 1 <= minibatches <= {total} samples")
+            raise ValueError(f"ppo_update: epochs >= 1 and 1 <= minibatches <= {total} {'chunks' if L else 'samples'}")
         dev = self.torch_device
         stats = torch.empty(epochs, minibatches, abi.PPO_STATS, dtype=torch.float32, device=dev)
         grad = torch.empty(self.actor_params()["flat"].numel(), dtype=torch.float32, device=dev)
@@ -460,7 +484,7 @@ class HipEngine(EngineBase):
                 first = b * per
                 count = per if b + 1 < minibatches else total - first
                 self.ppo_grad(traj, index=perm, first=first, count=count, clip=clip, value_coef=value_coef, entropy_coef=entropy_coef,
-                              value_clip=value_clip, out=(grad, stats[e, b]), value_norm=vn, update_value_norm=vn)
+                              value_clip=value_clip, out=(grad, stats[e, b]), value_norm=vn, update_value_norm=vn, chunk_length=chunk_length)
                 self.ppo_step += 1
                 self.adam_step(grad, self.ppo_step, lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm)
         return stats

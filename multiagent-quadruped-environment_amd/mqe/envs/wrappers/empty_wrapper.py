@@ -169,8 +169,9 @@ class FusedTaskWrapper(EmptyWrapper):
         other layer.  recurrent=True: both networks are mqe.utils.actor_net.RecurrentMLP (base -> GRU cell -> [LayerNorm] -> head; OpenRL's
         use_recurrent_policy), or the actor alone; a plain Sequential beside a RecurrentMLP is refused.  The engine carries the cells' state
         across rollout() calls and zeroes it wherever a step ended an episode; sync_actor() / pull_actor() copy the cells too.  ppo_update()
-        refuses such an actor: the learner runs back-propagation through time on the torch twins (rollout(record_hidden=True), then
-        RecurrentMLP.evaluate from traj.hidden) and sync_actor()s the result."""
+        trains such an actor with chunk_length=L: back-propagation through time over chunks of a trajectory of rollout(record_hidden=True),
+        inside the engine; without the keyword it refuses it (a learner may still differentiate the torch twins -- RecurrentMLP.evaluate
+        from traj.hidden -- and sync_actor() the result)."""
         from mqe.utils.actor_net import RecurrentMLP, actor_tensors, mlp_spec, recurrent_spec
         D = self.observation_space.shape[0]
         no_norms = {"feature": None, "hidden": []}
@@ -250,7 +251,9 @@ class FusedTaskWrapper(EmptyWrapper):
         Afterwards the engine holds the master copy: the following rollout() uses it as it is, pull_actor() copies it into the torch
         modules, and sync_actor() would overwrite it with the modules' values.  After set_actor(value_norm=True) every minibatch first folds
         its returns (reward units) into the running statistics and the value loss compares the critic with the returns normalised by the new
-        (mu, sigma): statistics entry 1 (mean L_v) is in normalised units."""
+        (mu, sigma): statistics entry 1 (mean L_v) is in normalised units.  After set_actor(recurrent=True): chunk_length=L is required --
+        the trajectory (rollout(record_hidden=True), T a multiple of L) is cut into chunks of L steps per row, the minibatches are sets of chunks
+        and the gradient runs through the GRU cells over each chunk's steps (OpenRL's data_chunk_length; HipEngine.ppo_grad states the rule)."""
         eng = self._rollout_engine("ppo_update")
         if getattr(self, "_actor", None) is None:
             raise RuntimeError("ppo_update: no actor (set_actor first)")

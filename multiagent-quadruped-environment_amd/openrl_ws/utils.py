@@ -59,14 +59,16 @@ class mqe_openrl_wrapper(Wrapper):
         """T steps of step_torch with the engine's own actor in one call (mqe_rollout, action_gain = 0.5): the wrapper's Rollout -- obs
         (T+1, N, A, D), reward (T, N, A), done (T, N) bool, actions (T, N, A, 3) as the actor sampled them, logp, value -- fresh device memory.
         gamma / lam / normalize_advantages: FusedTaskWrapper.rollout's -- time_outs, advantages, returns and adv_stats from the engine (mqe_gae);
-        record_hidden (a recurrent actor): traj.hidden, the state every step started from, for back-propagation through time in torch"""
+        record_hidden (a recurrent actor): traj.hidden, the state every step started from, for back-propagation through time
+        (ppo_update_torch(chunk_length=L), or in torch)"""
         kw = {"record_hidden": True} if record_hidden else {}
         return self.env.rollout(T, deterministic=deterministic, gamma=gamma, lam=lam, normalize_advantages=normalize_advantages, **kw)
 
     def ppo_update_torch(self, traj, **kw):
         """FusedTaskWrapper.ppo_update on a trajectory of rollout_torch(gamma=...): the PPO epochs run inside the engine on its own parameters
         (mqe_ppo_grad / mqe_ppo_adam); -> the (epochs, minibatches, 6) statistics tensor.  pull_actor() of the wrapped env brings the result back
-        into the torch modules"""
+        into the torch modules.  A recurrent actor needs chunk_length=L (OpenRL's data_chunk_length) and a trajectory of
+        rollout_torch(record_hidden=True) whose T is a multiple of L: back-propagation through time runs inside the engine"""
         return self.env.ppo_update(traj, **kw)
 
     def step_dlpack(self, actions):
