@@ -41,7 +41,8 @@ extern "C" {
  * MQE_GAE_VALUE_NORM, MQE_PPO_VALUE_NORM and MQE_PPO_VALUE_NORM_UPDATE (flag bits that were refused as unknown before); layer normalisation:
  * likewise -- MQE_ACTOR_LAYER_NORM and MQE_ACTOR_FEATURE_NORM (bits 2 and 4 of the kind byte of mqe_actor_shape.activation, refused before); the
  * recurrent actor-critic: likewise -- MQE_ACTOR_RECURRENT (bit 16 of the kind byte, refused before), MQE_ROLLOUT_HIDDEN_IN and
- * MQE_ROLLOUT_HIDDEN_RECORD (mqe_rollout flags 2 and 4, ignored before). */
+ * MQE_ROLLOUT_HIDDEN_RECORD (mqe_rollout flags 2 and 4, ignored before); the joint-ratio and dual-clip losses: likewise -- MQE_PPO_JOINT and
+ * MQE_PPO_DUAL_CLIP (mqe_ppo_grad flags 64 and 128, refused as unknown before) and the typedef mqe_ppo_loss_ex. */
 #define MQE_ABI_VERSION 17
 #define MQE_MAX_SPHERES 64    /* feature points of one robot (the capsule model has 32, the exact one 60) */
 #define MQE_MAX_PRIMS 20      /* collision primitives of one robot (Go1: 18) */
@@ -551,6 +552,8 @@ int mqe_gae(mqe_sim* s, int T, const float* packed_dev, long long row_stride, co
  * -1 null handle / grad_dev; -6: no actor, step < 1, a misaligned pointer, lr / max_grad_norm not finite, a beta outside [0, 1), eps negative or
  * not finite, grad_dev or norm_dev overlapping the parameter or moment buffers or each other. */
 typedef struct { float clip_ratio, value_coef, entropy_coef, value_clip; } mqe_ppo_loss;
+/* what `loss` points at under MQE_PPO_DUAL_CLIP (the joint-ratio and dual-clip section below): 32 bytes, the first 16 are mqe_ppo_loss */
+typedef struct { float clip_ratio, value_coef, entropy_coef, value_clip, dual_clip, reserved[3]; } mqe_ppo_loss_ex;
 #define MQE_PPO_CLIP_VALUE 1      /* flags bit 0 */
 #define MQE_PPO_STATS 6
 int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long long row_stride, const float* actions_dev,
@@ -671,6 +674,32 @@ int mqe_ppo_adam(mqe_sim* s, const float* grad_dev, long long step, float lr, fl
  * mqe_actor_create refuses (-6, naming the width) a recurrent shape whose LDS need, (2 max layer input + 4 + Ha + Hc, + 32 with a norm) rows of 260
  *   bytes, exceeds the 160 KiB of a workgroup; every shape with all widths and obs_dim <= 128 fits.  A handle created without the bit launches
  *   exactly the kernels it launched before. */
+
+/* ---- Joint-ratio and dual-clip policy losses in mqe_ppo_grad (csrc/kernels_ppo.hpp: the loss head of the four gradient kernels, k_joint_expand) ----
+ * v17, additive: no export, no prototype and no #define of this header changes; mqe_ppo_loss_ex above is the one new typedef.  OpenRL's
+ * use_joint_action_loss (jrpo.yaml) and dual_clip_ppo / dual_clip_coeff (dppo.yaml).  THE TWO CONSTANTS BELOW ARE NOT #DEFINED BY THIS HEADER
+ * (tests/test_ppo.py pins the exact set of MQE_PPO_* defines).  Their values are stated here, defined under these names in csrc/kernels_ppo.hpp (which
+ * the engine compiles) and mirrored in mqe/engine/abi.py; tests/test_joint_loss.py holds the three statements together.  A C caller passes the
+ * numbers.  Both bits were refused as unknown before.
+ *   MQE_PPO_JOINT = 64   MQE_PPO_DUAL_CLIP = 128
+ * MQE_PPO_JOINT: one importance ratio and one advantage per ENV-STEP instead of one per agent.  With R' = N A' rows a step and sample
+ *   s = t R' + n A' + a, a GROUP is the A' samples of one env-step: g = t N + n, samples g A' + a.  index_dev / first / count are GROUP numbers in
+ *   [0, T N) (index values are clamped into that range); with MQE_PPO_BPTT they are chunk groups (t0 / L) N + n in [0, (T / L) N), each standing for
+ *   the A' chunks of that env.  Per sample d_a = logp_a - logp_old_a (f32, as above); per group, pairwise in the order of the xor butterfly:
+ *     Delta = d_0 (A' = 1), d_0 + d_1 (A' = 2), (d_0 + d_1) + (d_2 + d_3) (A' = 4), ...;   rho = expf(Delta)
+ *     A = (adv_0 + ...) * (float)(1.0 / A'), added in the same order;   L_pi(g) = -min(rho A, clamp(rho, 1 - c, 1 + c) A)
+ *   The policy term of L is the mean of L_pi(g) over the G = count (count L under MQE_PPO_BPTT) groups, 1 / G = (float)(1.0 / G); the value term stays the
+ *   mean over the M = G A' samples, the entropy term is unchanged.  For every agent a of the group dL/dlogp_a = -A rho (1 / G), and 0 when
+ *   (A > 0 and rho > 1 + c) or (A < 0 and rho < 1 - c): every agent of a group sees the same bits of Delta, rho and A, so the group decides a kink once.
+ *   stats_dev[0] is the mean of L_pi over groups, [4] the mean of -Delta over groups, [5] the share of groups with |rho - 1| > c; [1 .. 3] as before.
+ *   At A' = 1 the call has the bits of the call without the flag.  Under MQE_PPO_VALUE_NORM[_UPDATE] the returns are those of the groups' samples.
+ *   One more small launch (k_joint_expand: the groups' flat sample or chunk numbers into engine-owned scratch, made by the first such call and grown with
+ *   count; that call synchronises once).  -6 naming A' on a handle whose A' does not divide 32 (the agents of a group share the lanes of one wavefront).
+ * MQE_PPO_DUAL_CLIP: `loss` points at an mqe_ppo_loss_ex; without the bit nothing beyond the first 16 bytes is read.  With c_d = dual_clip > 1 + c,
+ *   where the advantage is negative  L_pi = -max(min(rho A, clamp(rho) A), c_d A),  and dL/dlogp is additionally 0 when A < 0 and rho > c_d (for
+ *   c_d > 1 + c value for value OpenRL's ratio = min(ratio, c_d) form).  Without MQE_PPO_JOINT rho = ratio and A = adv of the single sample.
+ *   -6 naming dual_clip: not finite, or <= 1 + clip_ratio; -6 naming reserved: a reserved word whose bits are not zero.
+ * Both combine with each other and with every other mqe_ppo_grad flag; every refusal enqueues and writes nothing. */
 
 /* The onboard forward depth camera of LeggedRobotField (legged_robot_field.py:23-93: create_camera_sensor + attach_camera_to_body on the
  * base link, :196-223: get_camera_image_gpu_tensor(IMAGE_DEPTH)) for every robot, from the CURRENT state: out_dev [R][height][width]

@@ -23,6 +23,21 @@
 //     hidden layers:   delta_in = (W^T delta_out) * (1 - y^2) (tanh, from the stored output y) or (y > 0 ? . : 0) (relu)
 // 1 / M is one f32 value, formed on the host as (float)(1.0 / M).
 //
+// THE JOINT RATIO (MQE_PPO_JOINT; OpenRL's use_joint_action_loss, jrpo.yaml).  R' = N A' rows a step, s = t R' + n A' + a.  A GROUP is the A' samples of
+// one env-step: g = t N + n, samples g A' + a; A' divides 32.  THE GROUP IS THE MINIBATCH'S UNIT: index / first / count are group numbers in [0, T N)
+// (a ratio over half an env-step's agents does not exist), k_joint_expand writes the flat list g A' + a, group-major, clamped, and the gradient kernel
+// reads that list as its index with count A' entries -- a group is A' aligned lanes of one tile, wholly valid or wholly padding.  Per sample
+// d_a = logp_a - logp_old_a as above; per group, pairwise in the xor butterfly's order:
+//     Delta = d_0 | d_0 + d_1 | (d_0 + d_1) + (d_2 + d_3) | ...;   rho = exp(Delta);   A = (adv_0 + ...) * (float)(1.0 / A'), the same order
+//     L_pi(g) = -min(rho A, clamp(rho, 1 - c, 1 + c) A);   the policy term of L is the mean over the G = count groups, 1 / G = (float)(1.0 / G)
+//     dL/dlogp_a = 0 when (A > 0 and rho > 1 + c) or (A < 0 and rho < 1 - c), otherwise -A rho (1 / G), for every agent a of the group
+// Every lane of a group holds the same bits of Delta, rho and A, so no two agents decide a kink differently.  The value term stays the mean over the
+// M = G A' samples; the entropy term is unchanged.  Statistics: every lane adds its GROUP's L_pi, -Delta and |rho - 1| > c; k_ppo_reduce divides by M,
+// which is the mean over groups.  At A' = 1 every quantity has the bits of the plain path.
+// THE DUAL CLIP (MQE_PPO_DUAL_CLIP, coefficient c_d > 1 + c; OpenRL's dual_clip_ppo / dual_clip_coeff, dppo.yaml).  Where the advantage is negative,
+//     L_pi = -max(min(rho A, clamp(rho) A), c_d A),   and dL/dlogp is additionally 0 when A < 0 and rho > c_d
+// (for c_d > 1 + c value for value OpenRL's ratio = min(ratio, c_d) form); without the joint ratio rho = ratio and A = adv of the single sample.
+//
 // LAYOUT.  A workgroup is 1024 threads = 16 wavefronts (k_actor's) and walks row tiles of RT samples (kernels_actor_critic.hpp: the tile loop and the
 // order of the phases).  LDS holds, as [k][row] with an odd row stride, the observation and EVERY layer output of ONE network -- the backward pass
 // needs them.  No separate delta buffers: the delta of layer l - 1 overwrites the stored output of layer l - 1 IN PLACE, element by element by
@@ -65,6 +80,27 @@
 #define PPO_REDUCE_THREADS 256
 #define PPO_ADAM_THREADS 256
 #define PPO_NORM_THREADS 1024
+
+// the two loss switches of mqe_ppo_grad's flags: stated in the comment of include/mqe_hip.h in words, defined here (the header's define set is pinned by the
+// tests), mirrored in mqe/engine/abi.py
+#define MQE_PPO_JOINT 64               // index_dev / first / count are groups (THE JOINT RATIO above)
+#define MQE_PPO_DUAL_CLIP 128          // loss points at an mqe_ppo_loss_ex (THE DUAL CLIP above)
+#define JOINT_EXPAND_THREADS 256
+
+// the minibatch's count A' flat numbers g A' + a, group-major (samples; under MQE_PPO_BPTT chunks): what the gradient kernels, k_bptt_expand and
+// k_vn_moments / k_vn_apply read as their index list.  n_groups: T N, or (T / L) N
+__global__ void __launch_bounds__(JOINT_EXPAND_THREADS) k_joint_expand(const int32_t* __restrict__ index, long long first, long long count, long long n_groups, int Aw,
+                                                                       int32_t* __restrict__ out) {
+  for (long long e = (long long)blockIdx.x * JOINT_EXPAND_THREADS + threadIdx.x; e < count * Aw; e += (long long)gridDim.x * JOINT_EXPAND_THREADS) {
+    const long long i = e / Aw;
+    long long g = first + i;
+    if (index != nullptr) {
+      g = index[first + i];
+      g = g < 0 ? 0 : (g > n_groups - 1 ? n_groups - 1 : g);
+    }
+    out[e] = (int32_t)(g * Aw + (e - i * Aw));
+  }
+}
 
 // rows of the LDS image: observation, every hidden output of the larger network, 4 output rows (mean 0 .. 2, value)
 static inline int ppo_lds_rows(const ActorNet& a, const ActorNet& c, int D) {
@@ -160,7 +196,8 @@ __device__ __forceinline__ void ppo_dw(const float* dY, const float* x, int K, i
   }
 }
 
-struct PpoLoss { float clip, value_coef, entropy_coef, value_clip, inv_m; int clip_value; };
+// inv_g, inv_a, group: THE JOINT RATIO above (without the flag inv_g = inv_m, group = 1); dual, dual_clip: THE DUAL CLIP
+struct PpoLoss { float clip, value_coef, entropy_coef, value_clip, inv_m; int clip_value; float inv_g, inv_a, dual_clip; int group, dual; };
 struct PpoTraj {                       // the trajectory and the minibatch of it (THE LOSS above)
   const float* packed; long long stride; int rows; long long n_total;
   const float *actions, *logp_old, *value, *adv, *ret;
@@ -198,7 +235,7 @@ __device__ __forceinline__ void ppo_actor_head(const float* __restrict__ params,
                                                const float* __restrict__ actions, const float* __restrict__ logp_old, const float* __restrict__ adv,
                                                const PpoLoss& ls, PpoSums& S) {
   const long long s = srow[row];
-  const float lpo = logp_old[s], ad = adv[s];
+  const float lpo = logp_old[s];
   float z[3], inv[3], lp = 0.0f;
 #pragma unroll
   for (int j = 0; j < 3; j++) {
@@ -208,18 +245,33 @@ __device__ __forceinline__ void ppo_actor_head(const float* __restrict__ params,
     lp += -0.5f * z[j] * z[j] - lsj;
   }
   lp -= 3.0f * 0.9189385332046727f;       // 3 x 0.5 ln(2 pi)
-  const float ratio = expf(lp - lpo);
+  // the joint ratio: the group's log-ratio and advantage over the xor butterfly 1, 2, ...: a + b is b + a, so every lane of a group holds the same bits
+  // (all 64 lanes are here; a group is `group` aligned lanes of one tile, wholly valid or wholly padding; at 32-row tiles the upper half mirrors the lower)
+  float d = lp - lpo, ad = adv[s];
+  if (ls.group > 1) {
+    for (int m = 1; m < ls.group; m <<= 1) {
+      d += __shfl_xor(d, m);
+      ad += __shfl_xor(ad, m);
+    }
+    ad *= ls.inv_a;
+  }
+  const float ratio = expf(d);
   const float lo = 1.0f - ls.clip, hi = 1.0f + ls.clip;
-  const float Lpi = -fminf(ratio * ad, fminf(fmaxf(ratio, lo), hi) * ad);
-  const bool gate = (ad > 0.0f && ratio > hi) || (ad < 0.0f && ratio < lo);
-  const float dlp = gate ? 0.0f : -ad * ratio * ls.inv_m;
+  float Lpi = -fminf(ratio * ad, fminf(fmaxf(ratio, lo), hi) * ad);
+  bool gate = (ad > 0.0f && ratio > hi) || (ad < 0.0f && ratio < lo);
+  if (ls.dual) {                       // the second bound, where the advantage is negative
+    const float bound = -(ls.dual_clip * ad);
+    Lpi = ad < 0.0f ? fminf(Lpi, bound) : Lpi;
+    gate = gate || (ad < 0.0f && ratio > ls.dual_clip);
+  }
+  const float dlp = gate ? 0.0f : -ad * ratio * ls.inv_g;
   if (lane < RT) {
 #pragma unroll
     for (int j = 0; j < 3; j++) out[j * LD + row] = valid ? dlp * z[j] * inv[j] : 0.0f;
   }
   if (valid) {
     S.Lpi += (double)Lpi;
-    S.Kl += (double)(lpo - lp);
+    S.Kl += (double)(-d);              // lpo - lp of the sample; of the group under the joint ratio
     S.Clip += fabsf(ratio - 1.0f) > ls.clip ? 1.0 : 0.0;
 #pragma unroll
     for (int j = 0; j < 3; j++) S.gls[j] += (double)(dlp * (z[j] * z[j] - 1.0f));

@@ -165,6 +165,8 @@ struct mqe_sim {
     // expanded sample list [count L] for the value normalisation; made by the first call that needs them, grown when L (count) grows
     float* hscr = nullptr; size_t hscr_cap = 0;
     float* idx = nullptr; size_t idx_cap = 0;      // int32 words, allocated as floats
+    // MQE_PPO_JOINT (kernels_ppo.hpp): the minibatch's groups expanded to count A' flat sample (chunk) numbers; made by the first such call, grown with count
+    float* jidx = nullptr; size_t jidx_cap = 0;    // int32 words, allocated as floats
     float* moments = nullptr;
     double* norm = nullptr;
   } ppo;
@@ -1609,7 +1611,7 @@ static void dfree(mqe_sim* s, void* p) {
 static void actor_free(mqe_sim* s, const mqe_sim::Actor& a) { for (void* p : {(void*)a.params, (void*)a.stage, (void*)a.hstate, (void*)a.nets}) dfree(s, p); }
 static void actor_release(mqe_sim* s) {
   actor_free(s, s->act);
-  for (void* p : {(void*)s->ppo.part, (void*)s->ppo.pst, (void*)s->ppo.moments, (void*)s->ppo.norm, (void*)s->ppo.hscr, (void*)s->ppo.idx, (void*)s->vn.val, (void*)s->vn.tgt, (void*)s->vn.part}) dfree(s, p);
+  for (void* p : {(void*)s->ppo.part, (void*)s->ppo.pst, (void*)s->ppo.moments, (void*)s->ppo.norm, (void*)s->ppo.hscr, (void*)s->ppo.idx, (void*)s->ppo.jidx, (void*)s->vn.val, (void*)s->vn.tgt, (void*)s->vn.part}) dfree(s, p);
   s->act = mqe_sim::Actor(); s->ppo = mqe_sim::Ppo(); s->vn = mqe_sim::Vn();
 }
 // scratch of at least `need` floats (value normalisation; the recurrent gradient's states and sample list): made on first use, replaced by a larger one when
@@ -1850,18 +1852,37 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   if (bptt && T % L != 0) return fail(-6, "mqe_ppo_grad: T must be a multiple of the chunk length L (flags bits 8 .. 15)");
   if (bptt && row_stride < (long long)(tail + rows * hs))
     return fail(-6, "mqe_ppo_grad: row_stride: with MQE_PPO_BPTT a row holds the packed length rounded up to a multiple of 4 and the R' (Ha + Hc) recorded state floats behind it");
+  // MQE_PPO_JOINT / MQE_PPO_DUAL_CLIP (kernels_ppo.hpp): index_dev / first / count are groups of A' samples (chunks); loss is an mqe_ppo_loss_ex
+  const bool joint = (flags & MQE_PPO_JOINT) != 0, dual = (flags & MQE_PPO_DUAL_CLIP) != 0;
+  const int Aw = s->Aw;
+  if (joint && 32 % Aw != 0)
+    return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_JOINT: the agents of an env-step share the lanes of one wavefront, so A' must divide 32 (this handle's A' is %s)",
+                std::to_string(Aw).c_str());
   const size_t n_chunks = n / (size_t)L;      // (T / L) R'; without the bit: the samples
+  const size_t n_units = joint ? n_chunks / (size_t)Aw : n_chunks;      // what index_dev / first / count number: under MQE_PPO_JOINT the (T / L) N groups
   if (count < 1) return fail(-6, "mqe_ppo_grad: count must be at least 1");
   if (first < 0) return fail(-6, "mqe_ppo_grad: first must not be negative");
   if (first > (1LL << 40) || count > (1LL << 40)) return fail(-6, "mqe_ppo_grad: first / count beyond any trajectory");
-  if (!index_dev && first + count > (long long)n_chunks)
-    return fail(-6, bptt ? "mqe_ppo_grad: first + count exceeds the (T / L) x R' chunks of the trajectory" : "mqe_ppo_grad: first + count exceeds the T x R' samples of the trajectory");
+  if (!index_dev && first + count > (long long)n_units)
+    return fail(-6, joint ? (bptt ? "mqe_ppo_grad: first + count exceeds the (T / L) x N chunk groups of the trajectory (MQE_PPO_JOINT)"
+                                  : "mqe_ppo_grad: first + count exceeds the T x N groups of the trajectory (MQE_PPO_JOINT)") :
+                    bptt ? "mqe_ppo_grad: first + count exceeds the (T / L) x R' chunks of the trajectory" : "mqe_ppo_grad: first + count exceeds the T x R' samples of the trajectory");
   if (negative_or_not_finite(&loss->clip_ratio)) return fail(-6, "mqe_ppo_grad: clip_ratio must be finite and not negative");
   if (negative_or_not_finite(&loss->value_coef)) return fail(-6, "mqe_ppo_grad: value_coef must be finite and not negative");
   if (negative_or_not_finite(&loss->entropy_coef)) return fail(-6, "mqe_ppo_grad: entropy_coef must be finite and not negative");
   if (negative_or_not_finite(&loss->value_clip)) return fail(-6, "mqe_ppo_grad: value_clip must be finite and not negative");
+  const mqe_ppo_loss_ex* lx = reinterpret_cast<const mqe_ppo_loss_ex*>(loss);      // read past the first 16 bytes under the bit only
+  if (dual) {
+    if (not_finite(&lx->dual_clip) || !(lx->dual_clip > 1.0f + loss->clip_ratio))
+      return fail(-6, "mqe_ppo_grad: dual_clip (MQE_PPO_DUAL_CLIP) must be finite and greater than 1 + clip_ratio");
+    uint32_t rw[3];
+    memcpy(rw, lx->reserved, sizeof rw);
+    if (rw[0] | rw[1] | rw[2]) return fail(-6, "mqe_ppo_grad: the reserved words of mqe_ppo_loss_ex (MQE_PPO_DUAL_CLIP) must be zero");
+  }
+  flags &= ~(MQE_PPO_JOINT | MQE_PPO_DUAL_CLIP);
   if (flags & ~(MQE_PPO_CLIP_VALUE | MQE_PPO_VALUE_NORM | MQE_PPO_VALUE_NORM_UPDATE))
-    return fail(-6, "mqe_ppo_grad: unknown bits in flags (MQE_PPO_CLIP_VALUE, MQE_PPO_VALUE_NORM and MQE_PPO_VALUE_NORM_UPDATE are the only ones)");
+    return fail(-6, "mqe_ppo_grad: unknown bits in flags (MQE_PPO_CLIP_VALUE, MQE_PPO_VALUE_NORM, MQE_PPO_VALUE_NORM_UPDATE, MQE_PPO_JOINT and MQE_PPO_DUAL_CLIP are "
+                    "the only ones)");
   const bool vn = (flags & MQE_PPO_VALUE_NORM) != 0, vn_update = (flags & MQE_PPO_VALUE_NORM_UPDATE) != 0;
   if (vn_update && !vn) return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_VALUE_NORM_UPDATE requires MQE_PPO_VALUE_NORM (the update precedes the normalisation it serves)");
   if (vn)
@@ -1897,6 +1918,12 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   }
   hipStream_t q = (hipStream_t)stream;
   const int rt = s->ppo.rt;
+  const long long groups = count * L;  // under MQE_PPO_JOINT: the groups of the minibatch, the policy term's divisor
+  const int32_t* group_index = index_dev; const long long group_first = first, group_count = count;
+  if (joint) {                         // the groups' samples (chunks) as a flat list, group-major (k_joint_expand below): from here on the minibatch is that list
+    if (vn_scratch(s, &s->ppo.jidx, &s->ppo.jidx_cap, (size_t)(count * Aw))) return fail(-5, "device alloc failed (mqe_ppo_grad joint-ratio scratch)");
+    index_dev = (const int32_t*)s->ppo.jidx; first = 0; count *= Aw;
+  }
   const long long tiles = (count + rt - 1) / rt;
   const int G = (int)(tiles < PPO_MAX_WG ? tiles : PPO_MAX_WG);
   const long long M = count * L;       // the samples of the minibatch
@@ -1907,7 +1934,14 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   PpoLoss ls;
   ls.clip = loss->clip_ratio; ls.value_coef = loss->value_coef; ls.entropy_coef = loss->entropy_coef; ls.value_clip = loss->value_clip;
   ls.inv_m = (float)(1.0 / (double)M); ls.clip_value = (flags & MQE_PPO_CLIP_VALUE) ? 1 : 0;
-  if (vn) {                            // [update the state from the minibatch's returns,] normalise them into the scratch the loss reads
+  ls.inv_g = joint ? (float)(1.0 / (double)groups) : ls.inv_m; ls.inv_a = (float)(1.0 / (double)Aw); ls.group = joint ? Aw : 1;
+  ls.dual = dual ? 1 : 0; ls.dual_clip = dual ? lx->dual_clip : 0.0f;
+  if (joint) {
+    const long long we = (count + JOINT_EXPAND_THREADS - 1) / JOINT_EXPAND_THREADS;
+    hipLaunchKernelGGL(k_joint_expand, dim3((int)(we < 2048 ? we : 2048)), dim3(JOINT_EXPAND_THREADS), 0, q, group_index, group_first, group_count, (long long)n_units,
+                       Aw, (int32_t*)s->ppo.jidx);
+  }
+  if (vn) {                           // [update the state from the minibatch's returns,] normalise them into the scratch the loss reads
     const int32_t* vi = index_dev; long long vf = first;
     if (bptt) {                        // the chunks' samples as a flat list: what the two kernels read as their index
       const long long we = (M + BPTT_EXPAND_THREADS - 1) / BPTT_EXPAND_THREADS;

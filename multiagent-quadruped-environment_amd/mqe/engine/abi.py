@@ -134,6 +134,9 @@ ACT_LD, LN_PART, GRU_LDS_LIMIT = 65, 32, 160 * 1024      # csrc/kernels_actor.hp
 # the recurrent gradient (include/mqe_hip.h states the values, csrc/kernels_bptt.hpp defines them): mqe_ppo_grad flags bit 5 -- back-propagation through
 # time over chunks; index / first / count are chunks --, the shift of the chunk length L in flags (bits 8 .. 15) and the largest L
 PPO_BPTT, PPO_CHUNK_SHIFT, PPO_MAX_CHUNK = 32, 8, 64
+# the joint-ratio and dual-clip losses (include/mqe_hip.h states the values, csrc/kernels_ppo.hpp defines them): mqe_ppo_grad flags bits 6 and 7 -- index /
+# first / count number the groups of A' samples of one env-step; `loss` points at a PpoLossEx
+PPO_JOINT, PPO_DUAL_CLIP = 64, 128
 LN_STAT, BPTT_CELL_ROWS, BPTT_LDS_LIMIT = 8, 7, 160 * 1024      # csrc/kernels_ln.hpp, kernels_bptt.hpp: what the LDS rule of the recurrent gradient is made of
 RNG_ACTOR = 0x70000000          # csrc/mqe_common.hpp MQE_RNG_ACTOR: `count` of the actor's draws = RNG_ACTOR + post-physics steps so far
 
@@ -146,6 +149,11 @@ class ActorShape(C.Structure):
 class PpoLoss(C.Structure):
     """mqe_ppo_loss"""
     _fields_ = [("clip_ratio", f32), ("value_coef", f32), ("entropy_coef", f32), ("value_clip", f32)]
+
+
+class PpoLossEx(C.Structure):
+    """mqe_ppo_loss_ex: what mqe_ppo_grad's `loss` points at under PPO_DUAL_CLIP (passed through ctypes.cast to POINTER(PpoLoss): the prototype stays)"""
+    _fields_ = PpoLoss._fields_ + [("dual_clip", f32), ("reserved", f32 * 3)]
 
 
 def actor_gru_lds_bytes(actor_dims, critic_dims=None, layer_norm=False, feature_norm=False):

@@ -377,7 +377,7 @@ class HipEngine(EngineBase):
 
     # ---- the PPO update on the engine's own parameters (mqe_ppo_grad / mqe_ppo_optimizer / mqe_ppo_adam; csrc/kernels_ppo.hpp) ---------------
     def ppo_grad(self, traj, index=None, first=0, count=None, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=None, out=None, value_norm=None,
-                 update_value_norm=False, chunk_length=None):
+                 update_value_norm=False, chunk_length=None, joint=False, dual_clip=None):
         """Gradient of rsl_rl's clipped-surrogate PPO loss over one minibatch of a Rollout that HipEngine.gae has filled, with respect to the
         engine's actor-critic parameters (mqe_ppo_grad; csrc/kernels_ppo.hpp states the loss): two launches, no synchronisation (the first
         call after create_actor allocates its scratch and synchronises once), the same bits on every run.  The minibatch is
@@ -393,7 +393,12 @@ class HipEngine(EngineBase):
         time, OpenRL's recurrent generator at data_chunk_length = L.  The trajectory (rollout(record_hidden=True), T a multiple of L) is cut into
         (T / L) * N * A' chunks, chunk c = (t0 / L) * N * A' + row covering steps t0 .. t0 + L - 1 of that row; index / first / count are CHUNK
         numbers, the loss averages over the count * L samples, and a chunk starts from the masked recorded state traj.hidden[t0] (data, no
-        gradient) and carries the state it computes with the current parameters through its steps, reset where traj.done says so."""
+        gradient) and carries the state it computes with the current parameters through its steps, reset where traj.done says so.
+        joint=True (abi.PPO_JOINT; OpenRL's use_joint_action_loss): one importance ratio -- the product of the agents' -- and one advantage -- their
+        mean -- per env-step; index / first / count are then GROUP numbers t * N + env (with chunk_length: chunk groups (t0 / L) * N + env), each
+        standing for the A' samples (chunks) of that env-step, and the policy term averages over the groups; one more small launch.
+        dual_clip=c_d (abi.PPO_DUAL_CLIP; OpenRL's dual_clip_ppo / dual_clip_coeff; None: off): where the advantage is negative the surrogate is
+        additionally bounded by c_d * adv; c_d > 1 + clip.  csrc/kernels_ppo.hpp states both."""
         self._need_actor()
         L = self._chunks("ppo_grad", traj, chunk_length)
         vn = self._value_norm("ppo_grad", value_norm)
@@ -411,7 +416,7 @@ class HipEngine(EngineBase):
             _need_f32(f"traj.{name}", getattr(traj, name), shp)
         _need_packed(traj)
         n_params = self.actor_params()["flat"].numel()
-        total = T * N * Aw // max(L, 1)
+        total = T * N * (1 if joint else Aw) // max(L, 1)
         if index is not None:
             if not (index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.dim() == 1):
                 raise ValueError("index must be a contiguous one-dimensional int32 device tensor")
@@ -419,18 +424,21 @@ class HipEngine(EngineBase):
         first = int(first)
         count = total - first if count is None else int(count)
         if index is not None and (first < 0 or count < 1 or first + count > total):
-            raise ValueError(f"index holds {total} samples: first={first}, count={count} reach outside it")
+            what = ("chunk groups" if L else "groups") if joint else ("chunks" if L else "samples")
+            raise ValueError(f"index holds {total} {what}: first={first}, count={count} reach outside it")
         grad, stats = out if out is not None else (None, None)
         for what, t, shp in (("out[0] (grad)", grad, (n_params,)), ("out[1] (stats)", stats, (abi.PPO_STATS,))):
             if t is not None:
                 _need_f32(what, t, shp)
         grad = grad if grad is not None else torch.empty(n_params, dtype=torch.float32, device=dev)
         stats = stats if stats is not None else torch.empty(abi.PPO_STATS, dtype=torch.float32, device=dev)
-        loss = abi.PpoLoss(float(clip), float(value_coef), float(entropy_coef), float(value_clip) if value_clip is not None else 0.0)
+        loss = abi.PpoLossEx(float(clip), float(value_coef), float(entropy_coef), float(value_clip) if value_clip is not None else 0.0,
+                             float(dual_clip) if dual_clip is not None else 0.0)
         self._invoke("ppo_grad", T, _ptr(traj.packed), int(traj.packed.stride(0)), _ptr(traj.actions), _ptr(traj.logp), _ptr(traj.value),
-                     _ptr(traj.advantages), _ptr(traj.returns), _ptr(index), first, count, C.byref(loss),
+                     _ptr(traj.advantages), _ptr(traj.returns), _ptr(index), first, count, C.cast(C.pointer(loss), C.POINTER(abi.PpoLoss)),
                      (abi.PPO_CLIP_VALUE if value_clip is not None else 0) | (abi.PPO_VALUE_NORM if vn else 0) |
-                     (abi.PPO_VALUE_NORM_UPDATE if update_value_norm else 0) | ((abi.PPO_BPTT | L << abi.PPO_CHUNK_SHIFT) if L else 0),
+                     (abi.PPO_VALUE_NORM_UPDATE if update_value_norm else 0) | ((abi.PPO_BPTT | L << abi.PPO_CHUNK_SHIFT) if L else 0) |
+                     (abi.PPO_JOINT if joint else 0) | (abi.PPO_DUAL_CLIP if dual_clip is not None else 0),
                      _ptr(grad), _ptr(stats), self._stream())
         return grad, stats
 
@@ -456,7 +464,7 @@ class HipEngine(EngineBase):
                      float(max_grad_norm) if max_grad_norm is not None else 0.0, _ptr(norm_out), self._stream())
 
     def ppo_update(self, traj, epochs, minibatches, lr, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=None, betas=(0.9, 0.999), eps=1e-8,
-                   max_grad_norm=None, generator=None, value_norm=None, chunk_length=None):
+                   max_grad_norm=None, generator=None, value_norm=None, chunk_length=None, joint=False, dual_clip=None):
         """The PPO update of one trajectory inside the engine: per epoch one device permutation of the T x N x A' samples
         (torch.randperm(..., device=..., generator=generator)), cut into `minibatches` equal slices (the last takes the remainder), and per
         slice ppo_grad + adam_step -- 2 to 4 launches, no synchronisation, no copy.  The step count lives on this object (ppo_step) and carries
@@ -464,16 +472,18 @@ class HipEngine(EngineBase):
         is the master copy of the parameters.  value_norm (None: as the actor was created): every minibatch first folds its returns into
         the running statistics, then normalises them with the new (mu, sigma) -- OpenRL's ValueNorm order; 1 or 2 more launches a slice.
         chunk_length=L (a recurrent actor, refused without it; ppo_grad's): what is permuted and cut into minibatches are the (T / L) * N * A'
-        chunks, and `minibatches` is bounded by their number; one launch more a slice under value normalisation."""
+        chunks, and `minibatches` is bounded by their number; one launch more a slice under value normalisation.
+        joint, dual_clip: ppo_grad's (OpenRL's use_joint_action_loss; dual_clip_ppo with dual_clip_coeff).  With joint what is permuted and cut are
+        the T * N groups (the (T / L) * N chunk groups), `minibatches` is bounded by their number, and a slice costs one launch more."""
         self._need_actor()
         L = self._chunks("ppo_update", traj, chunk_length)
         vn = self._value_norm("ppo_update", value_norm)
         epochs, minibatches = int(epochs), int(minibatches)
         T = int(traj.T)
         N, Aw, _ = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
-        total = T * N * Aw // max(L, 1)
+        total = T * N * (1 if joint else Aw) // max(L, 1)
         if epochs < 1 or minibatches < 1 or minibatches > total:
-            raise ValueError(f"ppo_update: epochs >= 1 and 1 <= minibatches <= {total} {'chunks' if L else 'samples'}")
+            raise ValueError(f"ppo_update: epochs >= 1 and 1 <= minibatches <= {total} {('chunk groups' if L else 'groups') if joint else 'chunks' if L else 'samples'}")
         dev = self.torch_device
         stats = torch.empty(epochs, minibatches, abi.PPO_STATS, dtype=torch.float32, device=dev)
         grad = torch.empty(self.actor_params()["flat"].numel(), dtype=torch.float32, device=dev)
@@ -484,7 +494,8 @@ class HipEngine(EngineBase):
                 first = b * per
                 count = per if b + 1 < minibatches else total - first
                 self.ppo_grad(traj, index=perm, first=first, count=count, clip=clip, value_coef=value_coef, entropy_coef=entropy_coef,
-                              value_clip=value_clip, out=(grad, stats[e, b]), value_norm=vn, update_value_norm=vn, chunk_length=chunk_length)
+                              value_clip=value_clip, out=(grad, stats[e, b]), value_norm=vn, update_value_norm=vn, chunk_length=chunk_length, joint=joint,
+                              dual_clip=dual_clip)
                 self.ppo_step += 1
                 self.adam_step(grad, self.ppo_step, lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm)
         return stats

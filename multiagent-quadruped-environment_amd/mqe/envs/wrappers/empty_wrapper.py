@@ -253,7 +253,9 @@ class FusedTaskWrapper(EmptyWrapper):
         its returns (reward units) into the running statistics and the value loss compares the critic with the returns normalised by the new
         (mu, sigma): statistics entry 1 (mean L_v) is in normalised units.  After set_actor(recurrent=True): chunk_length=L is required --
         the trajectory (rollout(record_hidden=True), T a multiple of L) is cut into chunks of L steps per row, the minibatches are sets of chunks
-        and the gradient runs through the GRU cells over each chunk's steps (OpenRL's data_chunk_length; HipEngine.ppo_grad states the rule)."""
+        and the gradient runs through the GRU cells over each chunk's steps (OpenRL's data_chunk_length; HipEngine.ppo_grad states the rule).
+        joint=True is OpenRL's use_joint_action_loss (jrpo.yaml): one ratio and one advantage per env-step, the minibatches are sets of env-steps;
+        dual_clip=c_d is dual_clip_ppo with dual_clip_coeff = c_d (dppo.yaml)."""
         eng = self._rollout_engine("ppo_update")
         if getattr(self, "_actor", None) is None:
             raise RuntimeError("ppo_update: no actor (set_actor first)")

@@ -68,7 +68,9 @@ class mqe_openrl_wrapper(Wrapper):
         """FusedTaskWrapper.ppo_update on a trajectory of rollout_torch(gamma=...): the PPO epochs run inside the engine on its own parameters
         (mqe_ppo_grad / mqe_ppo_adam); -> the (epochs, minibatches, 6) statistics tensor.  pull_actor() of the wrapped env brings the result back
         into the torch modules.  A recurrent actor needs chunk_length=L (OpenRL's data_chunk_length) and a trajectory of
-        rollout_torch(record_hidden=True) whose T is a multiple of L: back-propagation through time runs inside the engine"""
+        rollout_torch(record_hidden=True) whose T is a multiple of L: back-propagation through time runs inside the engine.  Beside use_valuenorm (set_actor) the loss switches of
+        OpenRL's configs are keywords here: joint=True is use_joint_action_loss (jrpo.yaml), dual_clip=c_d is dual_clip_ppo with dual_clip_coeff = c_d
+        (dppo.yaml)"""
         return self.env.ppo_update(traj, **kw)
 
     def step_dlpack(self, actions):

@@ -6,6 +6,8 @@ learner it replaces, on the same tensors: go1gate 4096 envs x 2 agents, T = 200,
              the same loss, backward, clip_grad_norm_(1), torch.optim.Adam.step, and at the end of the epoch env.sync_actor()
 Both are warmed up, alternated --rounds times and timed with HIP events around the whole epoch.  The parameters are restored before every window, so
 every window does the same work.  The plain paths and bench.py against a library of the parent commit are tools/actor_ab.py --parent LIB --kinds plain,norms.
+--loss plain,joint,dual,joint+dual: the engine's epoch under each policy-loss head (MQE_PPO_JOINT, MQE_PPO_DUAL_CLIP at c_d = 3; under the joint loss the
+minibatches are sets of chunk groups), alternated in the same way, without the torch path.
 --out FILE: the printed lines go to that file as well (profiles/bptt.txt keeps one run)."""
 import argparse
 import math
@@ -61,6 +63,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--minibatches", type=int, default=4)
     ap.add_argument("--hidden", type=int, default=64)
+    ap.add_argument("--loss", default="plain", type=lambda s: s.split(","),
+                    help="comma list out of plain, joint, dual, joint+dual (c_d = 3): with more than plain, the engine's epoch per loss, alternated, no torch path")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -110,6 +114,10 @@ def main():
         paths = {"engine": lambda: env.ppo_update(traj, epochs=1, minibatches=mb, lr=1e-4, max_grad_norm=1.0, chunk_length=L,
                                                   generator=torch.Generator(device=dev).manual_seed(1), **kw),
                  "torch": lambda: torch_epoch(env, traj, actor, critic, log_std, opt, perm, mb, L, kw)}
+        if a.loss != ["plain"]:                # the loss heads of csrc/kernels_ppo.hpp against each other: the engine's epoch alone
+            heads = {"plain": {}, "joint": dict(joint=True), "dual": dict(dual_clip=3.0), "joint+dual": dict(joint=True, dual_clip=3.0)}
+            paths = {n: (lambda lkw=heads[n]: env.ppo_update(traj, epochs=1, minibatches=mb, lr=1e-4, max_grad_norm=1.0, chunk_length=L,
+                                                             generator=torch.Generator(device=dev).manual_seed(1), **kw, **lkw)) for n in a.loss}
         ms = {n: [] for n in paths}
         for n, fn in paths.items():            # warm-up: the first engine call allocates its scratch and synchronises once
             restore()
@@ -121,6 +129,9 @@ def main():
         for n, v in ms.items():
             say(f"ppo_update epoch, {kind:9s} {n:6s} median {statistics.median(v):10.3f} ms  min {min(v):10.3f}  max {max(v):10.3f}  (spread {spread(v):.1f} %) "
                 f"over {len(v)} windows")
+        if a.loss != ["plain"]:
+            env.close()
+            continue
         e, t = statistics.median(ms["engine"]), statistics.median(ms["torch"])
         say(f"ppo_update epoch, {kind:9s} engine / torch = {e / t:.3f}" + ("" if e <= t else "  (the engine's update is SLOWER than the torch learner)"))
         env.close()

@@ -10,8 +10,15 @@ paths are warmed up.  Then the per-kernel times: each of the four kernels alone,
 single call would time the launch), on a 1/4 minibatch, with the arithmetic floor of DESIGN 3.5 beside k_ppo_grad.  Prints median / min /
 max per path and the ratio of the medians.  --grad-only: warm-up and seven ppo_grad + adam_step calls and nothing else, the run to put under
 `rocprofv3 --kernel-trace --stats -- python tools/ppo_ab.py --grad-only`.  --out FILE: the printed lines go to that file as well
-(profiles/ppo.txt keeps one run, with the tests' figures)."""
+(profiles/ppo.txt keeps one run, with the tests' figures).
+--loss plain,joint,dual,joint+dual (default plain): the policy-loss heads to time (csrc/kernels_ppo.hpp: MQE_PPO_JOINT, MQE_PPO_DUAL_CLIP at c_d = 3).
+With more than `plain` the windows are one ppo_update epoch per loss, alternated in this one process, each against the plain median; the torch path
+and the per-kernel times are left out.  Every run but a --grad-only one first prints PPO_DIGEST {loss: sha256}: the bytes of the gradient and
+statistics of one ppo_grad call per loss on the fresh handle with a fixed index list, before anything is timed or updated -- run once more with
+MQE_HIP_LIB=<a build of the parent commit> and --loss plain, the line must be the same (profiles/joint_loss.txt keeps one such session)."""
 import argparse
+import hashlib
+import json
 import math
 import os
 import statistics
@@ -24,6 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "multiagent-quadruped-environment_amd")]
 from mqe.envs.utils import make_mqe_env, custom_cfg      # noqa: E402
 from mqe.utils.helpers import finish_args                # noqa: E402
+from mqe.engine import abi                               # noqa: E402
 
 LN2PI = math.log(2 * math.pi)
 
@@ -48,6 +56,7 @@ def main():
     ap.add_argument("--minibatches", type=int, default=4)
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--grad-only", action="store_true")
+    ap.add_argument("--loss", default="plain", help="comma-separated: plain, joint, dual, joint+dual")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = []
@@ -72,7 +81,8 @@ def main():
     kw = dict(clip=0.2, value_coef=1.0, entropy_coef=0.01, value_clip=0.2)
     lr, max_norm = 1e-3, 1.0
     traj = env.rollout(T, gamma=0.99, lam=0.95, normalize_advantages=True)
-    total = T * a.envs * 2
+    Aw = int(eng.tensor(abi.T_WRAPPER_OBS).shape[1])
+    total = T * a.envs * Aw
     per = total // mb
 
     def timed(fn):
@@ -96,6 +106,17 @@ def main():
         env.close()
         return
 
+    losses = {"plain": {}, "joint": dict(joint=True), "dual": dict(dual_clip=3.0), "joint+dual": dict(joint=True, dual_clip=3.0)}
+    losses = {n: losses[n] for n in a.loss.split(",")}
+    digest = {}
+    for n, lkw in losses.items():           # before anything is timed or updated: the handle as created, fixed seeds, a fixed index list
+        units = total // Aw if lkw.get("joint") else total
+        idx = torch.randperm(units, generator=torch.Generator().manual_seed(5)).to(torch.int32).to(dev)
+        g, st = eng.ppo_grad(traj, index=idx, first=0, count=units // mb, **kw, **lkw)
+        torch.cuda.synchronize()
+        digest[n] = hashlib.sha256(g.cpu().numpy().tobytes() + st.cpu().numpy().tobytes()).hexdigest()
+    print("PPO_DIGEST " + json.dumps(digest), flush=True)
+
     params = list(actor.parameters()) + list(critic.parameters()) + [log_std]
     opt = torch.optim.Adam(params, lr=lr)
     flat = lambda x, *tail: x.reshape(total, *tail)
@@ -118,6 +139,26 @@ def main():
 
     say(f"go1gate {a.envs} envs x 2 agents, T = {T}: {total} samples, {mb} minibatches of {per}, hidden {H} x {H} tanh, {torch.cuda.get_device_name(0)}")
     paths = {"(a) ppo_update": engine_epoch, "(b) torch autograd + Adam + sync_actor": torch_epoch}
+    if list(losses) != ["plain"]:
+        say(f"library {os.environ.get('MQE_HIP_LIB', 'in-tree')}; PPO_DIGEST {json.dumps(digest)}")
+        paths = {f"ppo_update, {n}": (lambda lkw=lkw: eng.ppo_update(traj, epochs=1, minibatches=mb, lr=lr, max_grad_norm=max_norm, **kw, **lkw)) for n, lkw in losses.items()}
+        ms = {n: [] for n in paths}
+        for _ in range(2):
+            for fn in paths.values():
+                fn()
+        for _ in range(a.rounds):
+            for n, fn in paths.items():
+                ms[n].append(timed(fn))
+        base = statistics.median(ms[next(iter(ms))])
+        for n, v in ms.items():
+            m = statistics.median(v)
+            say(f"{n:26s} median {m:9.3f} ms per epoch  min {min(v):9.3f}  max {max(v):9.3f}  (spread {(max(v) - min(v)) / m * 100:.1f} %) over {len(v)} windows"
+                f"  = {m / base:.4f} x {next(iter(ms))}")
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        env.close()
+        return
     ms = {n: [] for n in paths}
     for _ in range(2):
         for fn in paths.values():
@@ -130,6 +171,7 @@ def main():
         med[n] = statistics.median(v)
         say(f"{n:42s} median {med[n]:9.3f} ms per epoch  min {min(v):9.3f}  max {max(v):9.3f}  (spread {(max(v) - min(v)) / med[n] * 100:.1f} %) over {len(v)} windows")
     ra, rb = med["(a) ppo_update"], med["(b) torch autograd + Adam + sync_actor"]
+    say(f"library {os.environ.get('MQE_HIP_LIB', 'in-tree')}; PPO_DIGEST {json.dumps(digest)}")
     say(f"torch / engine (medians): {rb / ra:.2f} x  ({'the engine is faster' if rb > ra else 'TORCH IS FASTER'})")
     # the kernels alone
     grad = torch.empty(eng.actor_params()["flat"].numel(), device=dev)
