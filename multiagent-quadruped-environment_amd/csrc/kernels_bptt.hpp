@@ -5,8 +5,8 @@
 // kernels_ppo.hpp's, unchanged: what is new is WHICH samples a lane walks and the state that links them.
 //
 // CHUNKS (OpenRL / MAPPO's recurrent generator at data_chunk_length = L).  A trajectory of T steps over R' rows is T / L chunks per row; chunk
-// c = (t0 / L) R' + r covers steps t0 .. t0 + L - 1 of row r, 0 <= c < (T / L) R'.  A minibatch is `count` chunks -- index[first .. first + count)
-// clamped into the chunk range, or the contiguous range -- and M = count L samples: 1 / M = (float)(1.0 / (count L)).  A LANE IS A CHUNK: tile i of
+// c = (t0 / L) R' + r covers steps t0 .. t0 + L - 1 of row r, 0 <= c < (T / L) R'.  A minibatch is `count` chunks -- THE SELECTION of kernels_ppo.hpp
+// with the chunk as its unit -- and M = count L samples: 1 / M = (float)(1.0 / (count L)).  A LANE IS A CHUNK: tile i of
 // the minibatch is chunks i RT .. i RT + RT - 1, and workgroup b of G = min(tiles, PPO_MAX_WG) walks tiles b, b + G, ... (the fixed grid of k_ppo_grad).
 // STATE.  Step 0 of a chunk starts both cells from the recorded tail of packed row t0 (offset P4, row r: the actor's Ha floats, then the critic's
 // Hc), masked by row t0's done byte of the row's env: data, no gradient.  Step j > 0 starts from the h' this kernel computed at step j - 1 with the
@@ -68,19 +68,18 @@ struct BpttArgs {
   int L, Aw, Ha, Hc, Hm;
 };
 
+// THE CHUNK ADDRESSING: the flat sample number of step 0 of chunk c; step j of it lies j rows further (bptt_load_step, k_bptt_expand)
+__device__ __forceinline__ long long bptt_first_sample(long long c, int rows, int L) {
+  const long long tc = c / rows, r = c - tc * rows;
+  return tc * L * rows + r;
+}
 // the first sample number of the tile's chunks (past the end of the minibatch the last one again)
 template <int RT>
 __device__ __forceinline__ void bptt_chunks(long long* crow, const PpoTraj& tr, const BpttArgs& b, long long tile, int tid) {
   if (tid < RT) {
     long long i = tile * RT + tid;
     if (i > tr.count - 1) i = tr.count - 1;
-    long long c = tr.first + i;
-    if (tr.index != nullptr) {
-      c = tr.index[tr.first + i];
-      c = c < 0 ? 0 : (c > b.n_chunks - 1 ? b.n_chunks - 1 : c);
-    }
-    const long long tc = c / tr.rows, r = c - tc * tr.rows;
-    crow[tid] = tc * b.L * tr.rows + r;
+    crow[tid] = bptt_first_sample(ppo_unit(tr.index, tr.first, i, b.n_chunks), tr.rows, b.L);
   }
 }
 // step j of the tile's chunks: its sample numbers, its done bytes (dn: one int per row) and its observations -> LDS [k][row].  The caller's barrier follows
@@ -174,12 +173,6 @@ __global__ void __launch_bounds__(BPTT_EXPAND_THREADS) k_bptt_expand(const int32
   for (long long e = (long long)blockIdx.x * BPTT_EXPAND_THREADS + threadIdx.x; e < count * L; e += (long long)gridDim.x * BPTT_EXPAND_THREADS) {
     const long long i = e / L;
     const int j = (int)(e - i * L);
-    long long c = first + i;
-    if (index != nullptr) {
-      c = index[first + i];
-      c = c < 0 ? 0 : (c > n_chunks - 1 ? n_chunks - 1 : c);
-    }
-    const long long tc = c / rows, r = c - tc * rows;
-    out[e] = (int32_t)((tc * L + j) * rows + r);
+    out[e] = (int32_t)(bptt_first_sample(ppo_unit(index, first, i, n_chunks), rows, L) + (long long)j * rows);
   }
 }

@@ -5,9 +5,11 @@
 //
 // THE LOSS.  A sample is a flat index s = t * R' + r into a trajectory in mqe_rollout's layout, 0 <= s < T * R': its observation is the D
 // floats at packed + t * row_stride + r * D; actions[s][3], logp_old[s], v_old = value[s] (the first T rows of the [T + 1][R'] array), adv[s],
-// ret[s].  A minibatch is M = count samples: index[first .. first + count) when an int32 index list is given (a slice of a device
-// permutation; a value outside [0, T R') is the caller's error -- the kernel clamps it, so that it cannot read outside the trajectory),
-// otherwise the contiguous range first .. first + count.  Per sample, all f32:
+// ret[s].  THE SELECTION (ppo_unit below, the one statement of it).  A minibatch is `count` UNITS out of the trajectory's n: unit i is
+// index[first + i] when an int32 index list is given (a slice of a device permutation; a value outside [0, n) is the caller's error -- the kernel
+// clamps it, so that it cannot read outside the trajectory), otherwise first + i.  The units are samples (n = T R') here, groups under THE JOINT
+// RATIO below (n = T N), chunks under MQE_PPO_BPTT (kernels_bptt.hpp: n = (T / L) R', with both flags chunk groups, n = (T / L) N); M is the
+// minibatch's number of samples.  Per sample, all f32:
 //     mean = actor(obs), v = critic(obs)        the fmaf chains of k_actor (kernels_actor.hpp: actor_layer, unchanged)
 //     z_j  = (a_j - mean_j) * exp(-log_std_j)
 //     logp = sum_j (-0.5 z_j^2 - log_std_j) - 1.5 ln(2 pi)        (j ascending, from 0, as k_actor);   ratio = exp(logp - logp_old)
@@ -87,17 +89,24 @@
 #define MQE_PPO_DUAL_CLIP 128          // loss points at an mqe_ppo_loss_ex (THE DUAL CLIP above)
 #define JOINT_EXPAND_THREADS 256
 
+// THE SELECTION: unit i of a minibatch out of n.  No __restrict__ and this statement order: what the gradient kernels were compiled from before
+// the rule had a name (a second no-alias scope moves their schedules: the comment above ppo_grad_body, kernels_actor_critic.hpp)
+__device__ __forceinline__ long long ppo_unit(const int32_t* index, long long first, long long i, long long n) {
+  long long u = first + i;
+  if (index != nullptr) {
+    u = index[first + i];
+    u = u < 0 ? 0 : (u > n - 1 ? n - 1 : u);
+  }
+  return u;
+}
+
 // the minibatch's count A' flat numbers g A' + a, group-major (samples; under MQE_PPO_BPTT chunks): what the gradient kernels, k_bptt_expand and
 // k_vn_moments / k_vn_apply read as their index list.  n_groups: T N, or (T / L) N
 __global__ void __launch_bounds__(JOINT_EXPAND_THREADS) k_joint_expand(const int32_t* __restrict__ index, long long first, long long count, long long n_groups, int Aw,
                                                                        int32_t* __restrict__ out) {
   for (long long e = (long long)blockIdx.x * JOINT_EXPAND_THREADS + threadIdx.x; e < count * Aw; e += (long long)gridDim.x * JOINT_EXPAND_THREADS) {
     const long long i = e / Aw;
-    long long g = first + i;
-    if (index != nullptr) {
-      g = index[first + i];
-      g = g < 0 ? 0 : (g > n_groups - 1 ? n_groups - 1 : g);
-    }
+    const long long g = ppo_unit(index, first, i, n_groups);
     out[e] = (int32_t)(g * Aw + (e - i * Aw));
   }
 }
@@ -212,12 +221,7 @@ __device__ __forceinline__ void ppo_load_tile(float* lds, long long* srow, const
   if (tid < RT) {
     long long i = tile * RT + tid;
     if (i > count - 1) i = count - 1;
-    long long s = first + i;
-    if (index != nullptr) {
-      s = index[first + i];
-      s = s < 0 ? 0 : (s > n_total - 1 ? n_total - 1 : s);
-    }
-    srow[tid] = s;
+    srow[tid] = ppo_unit(index, first, i, n_total);
   }
   __syncthreads();
   for (int e = tid; e < RT * D; e += ACT_THREADS) {

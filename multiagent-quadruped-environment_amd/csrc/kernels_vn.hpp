@@ -8,7 +8,7 @@
 //   derived pair, a pure function of the STORED f32 (m, q, d), evaluated in f64 and rounded once each:
 //     dc = max(d, eps);  mu = (float)(m / dc);  sigma = (float)sqrt(max(q / dc - (m / dc)^2, var_min))
 //   (0, 0, 0) gives (0, 0.1f): sigma is never zero.
-//   update over a minibatch of M returns x_i -- the samples k_ppo_grad reads: index[first + i] clamped into [0, T R'), or first + i:
+//   update over a minibatch of M returns x_i -- the samples the gradient kernel reads (THE SELECTION of kernels_ppo.hpp, ppo_unit):
 //     S1 = sum x_i;  S2 = sum x_i^2 (f64 fma);  bm = S1 / M;  bq = S2 / M
 //     m' = (float)(beta m + (1 - beta) bm);  q' = (float)(beta q + (1 - beta) bq);  d' = (float)(beta d + (1 - beta))
 //   then the derived pair from the rounded (m', q', d').
@@ -31,6 +31,7 @@
 // No scratch memory; static LDS: 64 bytes in k_vn_moments, 2 KiB (the pairs) in k_vn_apply.
 #pragma once
 #include "mqe_common.hpp"
+#include "kernels_ppo.hpp"
 
 // the constants of the value-normalisation section of include/mqe_hip.h: stated there in words, defined here (the header's ACTOR / GAE / PPO define
 // sets are pinned by the tests), mirrored in mqe/engine/abi.py; tests/test_value_norm.py compares the three
@@ -58,13 +59,6 @@ __host__ __device__ inline void vn_derive(float m, float q, float d, float* mu, 
   *sigma = (float)sqrt(var > (double)VN_VAR_MIN ? var : (double)VN_VAR_MIN);
 }
 
-// sample i of the minibatch as k_ppo_grad reads it
-__device__ inline long long vn_sample(const int32_t* __restrict__ index, long long first, long long i, long long n_total) {
-  if (index == nullptr) return first + i;
-  const long long s = index[first + i];
-  return s < 0 ? 0 : (s > n_total - 1 ? n_total - 1 : s);
-}
-
 // out[i] = fmaf(v[i], sigma, mu), i < n = (T + 1) R'
 __global__ void __launch_bounds__(VN_THREADS) k_vn_denorm(const float* __restrict__ v, const float* __restrict__ state, float* __restrict__ out, long long n) {
   const float mu = state[3], sigma = state[4];
@@ -83,7 +77,7 @@ __global__ void __launch_bounds__(VN_THREADS) k_vn_moments(const float* __restri
 #pragma unroll
     for (int j = 0; j < VN_PER; j++) {
       const long long i = i0 + j * stride;
-      smp[j] = vn_sample(index, first, i < count ? i : count - 1, n_total);
+      smp[j] = ppo_unit(index, first, i < count ? i : count - 1, n_total);
     }
 #pragma unroll
     for (int j = 0; j < VN_PER; j++) x[j] = ret[smp[j]];
@@ -155,7 +149,7 @@ __global__ void __launch_bounds__(VN_THREADS) k_vn_apply(const float* __restrict
 #pragma unroll
     for (int j = 0; j < VN_PER; j++) {
       const long long i = i0 + j * stride;
-      smp[j] = vn_sample(index, first, i < count ? i : count - 1, n_total);
+      smp[j] = ppo_unit(index, first, i < count ? i : count - 1, n_total);
     }
 #pragma unroll
     for (int j = 0; j < VN_PER; j++) x[j] = ret[smp[j]];

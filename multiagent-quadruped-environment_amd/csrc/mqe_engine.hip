@@ -138,6 +138,7 @@ struct mqe_sim {
     // MQE_ACTOR_RECURRENT (kernels_gru.hpp): the widths of the two GRU cells and the live state [N A'][Ha + Hc], made zeroed with the actor and
     // released with it; selects the recurrent kernels.  The actor's, like Adam's moments: never in state_bufs
     bool gru = false; int Ha = 0, Hc = 0;
+    int Hm() const { return Ha > Hc ? Ha : Hc; }      // the wider cell: what the recurrent gradient's LDS rows and state scratch are sized by
     float* hstate = nullptr;
     ActorShapes* nets = nullptr;      // `sh` on the device, THE image of every actor: the recurrent rollout kernels and the gradient kernels read it
   } act;
@@ -164,9 +165,9 @@ struct mqe_sim {
     // a recurrent actor under MQE_PPO_BPTT (kernels_bptt.hpp): the workgroups' input states [PPO_MAX_WG][L][max(Ha, Hc)][rt] and the minibatch's
     // expanded sample list [count L] for the value normalisation; made by the first call that needs them, grown when L (count) grows
     float* hscr = nullptr; size_t hscr_cap = 0;
-    float* idx = nullptr; size_t idx_cap = 0;      // int32 words, allocated as floats
+    int32_t* idx = nullptr; size_t idx_cap = 0;
     // MQE_PPO_JOINT (kernels_ppo.hpp): the minibatch's groups expanded to count A' flat sample (chunk) numbers; made by the first such call, grown with count
-    float* jidx = nullptr; size_t jidx_cap = 0;    // int32 words, allocated as floats
+    int32_t* jidx = nullptr; size_t jidx_cap = 0;
     float* moments = nullptr;
     double* norm = nullptr;
   } ppo;
@@ -210,6 +211,8 @@ static int upload(mqe_sim* s, const float** dst, const float* src, size_t n) {
   return 0;
 }
 static inline int rup(int v, int m) { return (v + m - 1) / m * m; }
+// workgroups of a grid-stride launch: one per `per` items of `work`, `cap` at most
+static inline int capped_grid(long long work, long long per, long long cap = 2048) { const long long want = (work + per - 1) / per; return (int)(want < cap ? want : cap); }
 
 // W (out,in) row-major host -> Wt [Kpad][Npad] device at column offset; rows remapped by `rowmap` (-1 = zero row)
 static int make_layer(mqe_sim* s, GemmLayer* L, int K, int N) {
@@ -1522,12 +1525,14 @@ extern "C" int mqe_step_end(mqe_sim* s, void* stream) {
 
 // ---- host checks the training entry points share (mqe_actor_create, mqe_rollout, mqe_gae, mqe_ppo_grad, mqe_ppo_adam): each stated once; `fn`
 // is the entry point, the prefix of its refusals.  First: (T, row_stride) of a trajectory in mqe_rollout's layout against the handle
-struct TrajShape { size_t rows, n, packed_floats; };      // R' = N x A'; T x R' samples; floats of one packed row
+// R' = N x A'; T x R' samples; floats of one packed row; its tail (kernels_gru.hpp): the packed length rounded up to a multiple of 4, R' (Ha + Hc) state floats
+struct TrajShape { size_t rows, n, packed_floats, tail, hfloats; };
 static int traj_shape(const mqe_sim* s, const char* fn, int T, long long row_stride, TrajShape* t) {
   if (T <= 0 || T > MQE_ROLLOUT_MAX_STEPS) return fail(-6, "%s: T must be 1 .. MQE_ROLLOUT_MAX_STEPS (4096)", fn);
   t->packed_floats = packed_floats(s);
   if (row_stride < (long long)t->packed_floats || row_stride % 4 != 0) return fail(-6, "%s: row_stride must be a multiple of 4 and at least the MQE_T_WRAPPER_PACKED length", fn);
   t->rows = (size_t)s->N * s->Aw; t->n = (size_t)T * t->rows;
+  t->tail = (t->packed_floats + 3) / 4 * 4; t->hfloats = t->rows * (size_t)(s->act.Ha + s->act.Hc);
   return 0;
 }
 struct Aligned { const void* p; unsigned bytes; };
@@ -1614,9 +1619,10 @@ static void actor_release(mqe_sim* s) {
   for (void* p : {(void*)s->ppo.part, (void*)s->ppo.pst, (void*)s->ppo.moments, (void*)s->ppo.norm, (void*)s->ppo.hscr, (void*)s->ppo.idx, (void*)s->ppo.jidx, (void*)s->vn.val, (void*)s->vn.tgt, (void*)s->vn.part}) dfree(s, p);
   s->act = mqe_sim::Actor(); s->ppo = mqe_sim::Ppo(); s->vn = mqe_sim::Vn();
 }
-// scratch of at least `need` floats (value normalisation; the recurrent gradient's states and sample list): made on first use, replaced by a larger one when
-// T (L) grows (both synchronise)
-static int vn_scratch(mqe_sim* s, float** p, size_t* cap, size_t need) {
+// grow-only scratch of at least `need` elements (value normalisation; the recurrent gradient's states and sample list; the joint ratio's list): made on
+// first use, replaced by a larger one when T (L, count) grows (both synchronise)
+template <typename T>
+static int grow_scratch(mqe_sim* s, T** p, size_t* cap, size_t need) {
   if (*p && *cap >= need) return 0;
   dfree(s, *p);
   *p = nullptr; *cap = 0;
@@ -1723,9 +1729,8 @@ extern "C" int mqe_rollout(mqe_sim* s, int T, const float* obs0_dev, float* pack
   if (int rc = check_aligned("mqe_rollout", {{packed_dev, 16}, {obs0_dev, 4}, {actions_dev, 4}, {logp_dev, 4}, {value_dev, 4}}, "packed_dev: 16 bytes, the others: 4")) return rc;
   if (value_dev && s->act.sh.critic.n_layers == 0) return fail(-6, "mqe_rollout: value_dev given, but the actor was created without a critic");
   if (s->to_rec && T > s->to_rec_cap) return fail(-6, "mqe_rollout: T exceeds capacity_steps of the registered time-out record (mqe_rollout_time_outs)");
-  // the recurrent state (kernels_gru.hpp): the tail of a packed row is the R' Hs floats behind the packed length rounded up to a multiple of 4
   const bool gru = s->act.gru, h_in = (flags & MQE_ROLLOUT_HIDDEN_IN) != 0, h_rec = (flags & MQE_ROLLOUT_HIDDEN_RECORD) != 0;
-  const size_t tail = (ts.packed_floats + 3) / 4 * 4, hfloats = ts.rows * (size_t)(s->act.Ha + s->act.Hc);
+  const size_t tail = ts.tail, hfloats = ts.hfloats;      // the recurrent state (kernels_gru.hpp) in the tail of a packed row
   if ((h_in || h_rec) && !gru)
     return fail(-6, "mqe_rollout: flags: MQE_ROLLOUT_HIDDEN_IN / MQE_ROLLOUT_HIDDEN_RECORD need an actor created with MQE_ACTOR_RECURRENT (its state is what they read and write)");
   if ((h_in || h_rec) && row_stride < (long long)(tail + hfloats))
@@ -1792,22 +1797,19 @@ extern "C" int mqe_gae(mqe_sim* s, int T, const float* packed_dev, long long row
   if (norm && !s->gae_part) {          // once per handle: dalloc's memset synchronises
     if (dalloc(s, &s->gae_part, (size_t)2 * nblk)) return fail(-5, "device alloc failed (mqe_gae scratch)");
   }
-  if (vn && vn_scratch(s, &s->vn.val, &s->vn.val_cap, n + rows)) return fail(-5, "device alloc failed (mqe_gae value-normalisation scratch)");
+  if (vn && grow_scratch(s, &s->vn.val, &s->vn.val_cap, n + rows)) return fail(-5, "device alloc failed (mqe_gae value-normalisation scratch)");
   hipStream_t q = (hipStream_t)stream;
   const long long rew_off = (long long)rows * s->D;
   double* part = norm ? s->gae_part : nullptr;
   if (vn) {                            // the recursion reads de-normalised values: fmaf(v, sigma, mu) of all (T + 1) R'
-    const long long nv = (long long)(n + rows), per = (long long)VN_THREADS * VN_PER, want = (nv + per - 1) / per;
-    hipLaunchKernelGGL(k_vn_denorm, dim3((int)(want < 2048 ? want : 2048)), dim3(VN_THREADS), 0, q, value_dev, vn_state, s->vn.val, nv);
+    const long long nv = (long long)(n + rows);
+    hipLaunchKernelGGL(k_vn_denorm, dim3(capped_grid(nv, (long long)VN_THREADS * VN_PER)), dim3(VN_THREADS), 0, q, value_dev, vn_state, s->vn.val, nv);
     value_dev = s->vn.val;
   }
   hipLaunchKernelGGL(time_outs_dev ? k_gae<true> : k_gae<false>, dim3(nblk), dim3(GAE_THREADS), 0, q, packed_dev, row_stride, rew_off, value_dev, time_outs_dev, gamma, lam, T, (int)rows, s->N, s->Aw, adv_dev, ret_dev, part);
-  if (norm) {
-    const long long per = (long long)GAE_NORM_THREADS * 8;       // ~8 values per thread
-    const long long want = ((long long)n + per - 1) / per;
-    const int nb = (int)(want < 2048 ? want : 2048);
-    hipLaunchKernelGGL(k_gae_normalize, dim3(nb), dim3(GAE_NORM_THREADS), 0, q, adv_dev, (long long)n, (const double*)part, nblk, stats_dev);
-  }
+  if (norm)                            // ~8 values per thread
+    hipLaunchKernelGGL(k_gae_normalize, dim3(capped_grid((long long)n, (long long)GAE_NORM_THREADS * 8)), dim3(GAE_NORM_THREADS), 0, q, adv_dev, (long long)n,
+                       (const double*)part, nblk, stats_dev);
   return launched();
 }
 
@@ -1824,6 +1826,161 @@ static const struct PpoGradVariant { const void* kern[2]; const char* name; cons
    {{(const void*)k_bptt_grad<64>, (const void*)k_bptt_grad<32>}, "k_bptt_grad",
     "mqe_ppo_grad: flags: MQE_PPO_BPTT: the layer outputs of one network and 7 rows per unit of the wider GRU cell (width %s) do not fit the LDS even at 32 rows"}},
 };
+// ---- mqe_ppo_grad, stage by stage as mqe_actor_create: the checks in the order of their refusals, the once-per-actor plan, this call's scratch, the
+// launches.  PpoCall: what the flags, the handle and the arguments make of one call; each check fills what it has decided, nothing behind the checks reads
+// `flags`.  The minibatch is a PpoTraj (kernels_ppo.hpp): the caller's selection at first, the joint expansion's list once that is enqueued
+struct PpoCall {
+  bool bptt, joint, dual, clip_value, vn, vn_update;
+  int L, Aw;                      // the chunk length (1 without MQE_PPO_BPTT); the agents of a group
+  size_t n_chunks;                // (T / L) R'; without MQE_PPO_BPTT: the samples
+  size_t n_units; const char* units;      // what index_dev / first / count number -- the chunks, under MQE_PPO_JOINT the (T / L) N groups -- and their name in a refusal
+  long long M, groups;            // the samples of the minibatch; count L: under MQE_PPO_JOINT the groups, the policy term's divisor
+  TrajShape ts;
+};
+// MQE_PPO_BPTT (kernels_bptt.hpp): bits 8 .. 15 hold the chunk length L; index_dev / first / count are chunks
+static int ppo_check_actor(const mqe_sim* s, int flags, PpoCall* c) {
+  c->bptt = (flags & MQE_PPO_BPTT) != 0; c->L = c->bptt ? (flags >> MQE_PPO_CHUNK_SHIFT) & 0xff : 1;
+  if (!s->act.gru && (flags & (MQE_PPO_BPTT | (0xff << MQE_PPO_CHUNK_SHIFT))))
+    return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_BPTT and a chunk length in bits 8 .. 15 need an actor created with MQE_ACTOR_RECURRENT");
+  if (s->act.gru && !c->bptt)
+    return fail(-6, "mqe_ppo_grad: the actor was created with MQE_ACTOR_RECURRENT: its gradient is back-propagation through time over chunks of the recorded "
+                    "trajectory: pass flags = MQE_PPO_BPTT | L << MQE_PPO_CHUNK_SHIFT (32 | L << 8, 1 <= L <= 64; index_dev / first / count then mean chunks)");
+  if (c->bptt && (c->L < 1 || c->L > MQE_PPO_MAX_CHUNK))
+    return fail(-6, "mqe_ppo_grad: flags: the chunk length L in bits 8 .. 15 must be 1 .. MQE_PPO_MAX_CHUNK (64)");
+  if (s->act.sh.critic.n_layers == 0) return fail(-6, "mqe_ppo_grad: the actor was created without a critic: the loss has a value term");
+  return 0;
+}
+// (T, row_stride) and the pointers against the handle; fills the trajectory's half of `tr`.  MQE_PPO_JOINT (kernels_ppo.hpp): index_dev / first / count are groups
+static int ppo_check_traj(const mqe_sim* s, int T, int flags, PpoTraj* tr, const float* grad_dev, const float* stats_dev, PpoCall* c) {
+  if (int rc = traj_shape(s, "mqe_ppo_grad", T, tr->stride, &c->ts)) return rc;
+  if (int rc = check_aligned("mqe_ppo_grad", {{tr->packed, 16}, {tr->actions, 4}, {tr->logp_old, 4}, {tr->value, 4}, {tr->adv, 4}, {tr->ret, 4}, {tr->index, 4},
+                                              {grad_dev, 4}, {stats_dev, 4}}, "packed_dev: 16 bytes, the others: 4")) return rc;
+  if (c->bptt && T % c->L != 0) return fail(-6, "mqe_ppo_grad: T must be a multiple of the chunk length L (flags bits 8 .. 15)");
+  if (c->bptt && tr->stride < (long long)(c->ts.tail + c->ts.hfloats))
+    return fail(-6, "mqe_ppo_grad: row_stride: with MQE_PPO_BPTT a row holds the packed length rounded up to a multiple of 4 and the R' (Ha + Hc) recorded state floats behind it");
+  c->joint = (flags & MQE_PPO_JOINT) != 0; c->Aw = s->Aw;
+  if (c->joint && 32 % c->Aw != 0)
+    return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_JOINT: the agents of an env-step share the lanes of one wavefront, so A' must divide 32 (this handle's A' is %s)",
+                std::to_string(c->Aw).c_str());
+  c->n_chunks = c->ts.n / (size_t)c->L; c->n_units = c->joint ? c->n_chunks / (size_t)c->Aw : c->n_chunks;
+  c->units = c->joint ? (c->bptt ? "(T / L) x N chunk groups" : "T x N groups") : (c->bptt ? "(T / L) x R' chunks" : "T x R' samples");
+  tr->rows = (int)c->ts.rows; tr->n_total = (long long)c->ts.n;
+  return 0;
+}
+static int ppo_check_selection(const PpoTraj& tr, PpoCall* c) {
+  if (tr.count < 1) return fail(-6, "mqe_ppo_grad: count must be at least 1");
+  if (tr.first < 0) return fail(-6, "mqe_ppo_grad: first must not be negative");
+  if (tr.first > (1LL << 40) || tr.count > (1LL << 40)) return fail(-6, "mqe_ppo_grad: first / count beyond any trajectory");
+  if (!tr.index && tr.first + tr.count > (long long)c->n_units)
+    return fail(-6, "mqe_ppo_grad: first + count exceeds the %s of the trajectory%s", c->units, c->joint ? " (MQE_PPO_JOINT)" : "");
+  c->groups = tr.count * c->L; c->M = c->groups * (c->joint ? c->Aw : 1);
+  return 0;
+}
+// the loss's floats (MQE_PPO_DUAL_CLIP, kernels_ppo.hpp: `loss` is an mqe_ppo_loss_ex, read past its first 16 bytes under the bit only), then the rest of the flags
+static int ppo_check_loss(const mqe_sim* s, const mqe_ppo_loss* loss, int flags, PpoCall* c) {
+  if (negative_or_not_finite(&loss->clip_ratio)) return fail(-6, "mqe_ppo_grad: clip_ratio must be finite and not negative");
+  if (negative_or_not_finite(&loss->value_coef)) return fail(-6, "mqe_ppo_grad: value_coef must be finite and not negative");
+  if (negative_or_not_finite(&loss->entropy_coef)) return fail(-6, "mqe_ppo_grad: entropy_coef must be finite and not negative");
+  if (negative_or_not_finite(&loss->value_clip)) return fail(-6, "mqe_ppo_grad: value_clip must be finite and not negative");
+  c->dual = (flags & MQE_PPO_DUAL_CLIP) != 0;
+  if (c->dual) {
+    const mqe_ppo_loss_ex* lx = reinterpret_cast<const mqe_ppo_loss_ex*>(loss);
+    if (not_finite(&lx->dual_clip) || !(lx->dual_clip > 1.0f + loss->clip_ratio))
+      return fail(-6, "mqe_ppo_grad: dual_clip (MQE_PPO_DUAL_CLIP) must be finite and greater than 1 + clip_ratio");
+    uint32_t rw[3];
+    memcpy(rw, lx->reserved, sizeof rw);
+    if (rw[0] | rw[1] | rw[2]) return fail(-6, "mqe_ppo_grad: the reserved words of mqe_ppo_loss_ex (MQE_PPO_DUAL_CLIP) must be zero");
+  }
+  if (flags & ~(MQE_PPO_BPTT | (0xff << MQE_PPO_CHUNK_SHIFT) | MQE_PPO_JOINT | MQE_PPO_DUAL_CLIP | MQE_PPO_CLIP_VALUE | MQE_PPO_VALUE_NORM | MQE_PPO_VALUE_NORM_UPDATE))
+    return fail(-6, "mqe_ppo_grad: unknown bits in flags (MQE_PPO_CLIP_VALUE, MQE_PPO_VALUE_NORM, MQE_PPO_VALUE_NORM_UPDATE, MQE_PPO_JOINT and MQE_PPO_DUAL_CLIP are "
+                    "the only ones)");
+  c->clip_value = (flags & MQE_PPO_CLIP_VALUE) != 0; c->vn = (flags & MQE_PPO_VALUE_NORM) != 0; c->vn_update = (flags & MQE_PPO_VALUE_NORM_UPDATE) != 0;
+  if (c->vn_update && !c->vn) return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_VALUE_NORM_UPDATE requires MQE_PPO_VALUE_NORM (the update precedes the normalisation it serves)");
+  return c->vn ? need_value_norm(s, "mqe_ppo_grad", "MQE_PPO_VALUE_NORM") : 0;
+}
+// what the call writes against everything it reads
+static int ppo_check_ranges(const mqe_sim* s, int T, const PpoTraj& tr, const float* grad_dev, const float* stats_dev, const PpoCall& c) {
+  const mqe_sim::Actor& a = s->act;
+  const size_t n = c.ts.n, last_row = c.bptt ? c.ts.tail + c.ts.hfloats : c.ts.packed_floats;
+  return check_disjoint("mqe_ppo_grad", {{stats_dev, MQE_PPO_STATS * 4, "stats_dev"}, {grad_dev, (size_t)a.n_params * 4, "grad_dev"},
+                                         {tr.packed, ((size_t)T * tr.stride + last_row) * 4, "packed_dev"}, {tr.actions, n * 12, "actions_dev"},
+                                         {tr.logp_old, n * 4, "logp_dev"}, {tr.value, (n + c.ts.rows) * 4, "value_dev"}, {tr.adv, n * 4, "adv_dev"},
+                                         {tr.ret, n * 4, "ret_dev"}, {tr.index, (size_t)(tr.first + tr.count) * 4, "index_dev"},
+                                         {a.params, (size_t)a.n_params * 4, "the parameter buffer"},
+                                         {c.vn ? a.params + a.n_params : nullptr, MQE_VALUE_NORM_STATE * 4, "the value-normalisation state"}}, 2);
+}
+// once per actor: the row tile its shapes allow, the kernel of that tile and its LDS, the workgroups' partials (hipMalloc synchronises)
+static int ppo_plan(mqe_sim* s) {
+  if (s->ppo.part) return 0;
+  const mqe_sim::Actor& a = s->act; mqe_sim::Ppo& p = s->ppo;
+  const bool ln = a.ln(); const PpoGradVariant& var = PPO_GRAD_VARIANTS[a.gru][!ln];
+  const int plain_rows = ppo_lds_rows(a.sh.actor, a.sh.critic, s->D);
+  p.lds_rows = ln ? ln_lds_rows(a.sh.actor, a.sh.critic, s->D, a.sh.hidden, a.sh.feat) : plain_rows;
+  p.uw = ln ? p.lds_rows - plain_rows - LN_STAT - LN_PART : 0;
+  if (a.gru) p.lds_rows = bptt_lds_rows(p.lds_rows, a.Hm(), ln);
+  const auto bytes = [&](int rt) { return a.gru ? bptt_lds_bytes(p.lds_rows, rt) : ppo_lds_bytes(p.lds_rows, rt); };
+  p.rt = bytes(64) <= PPO_LDS_LIMIT ? 64 : 32; p.lds = (int)bytes(p.rt);
+  if (p.lds > PPO_LDS_LIMIT) return fail(-5, var.no_fit, std::to_string(a.Hm()).c_str());
+  p.kern = var.kern[p.rt == 32];
+  const hipError_t e = hipFuncSetAttribute(p.kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
+  if (p.lds > 48 * 1024 && e != hipSuccess) return fail(-5, "mqe_ppo_grad: cannot reserve LDS for %s", var.name);
+  if (dalloc(s, &p.pst, (size_t)PPO_MAX_WG * PPO_PST) || dalloc(s, &p.part, (size_t)PPO_MAX_WG * a.n_params, 0)) {
+    p.part = nullptr;                  // the next call tries again; what was allocated is released with the handle
+    return fail(-5, "device alloc failed (mqe_ppo_grad scratch)");
+  }
+  return 0;
+}
+// what this call's flags need beside the plan: made on first use, grown when T, L or count grow; such a call synchronises once
+static int ppo_scratch(mqe_sim* s, const PpoCall& c) {
+  mqe_sim::Ppo& p = s->ppo;
+  if (c.vn && (grow_scratch(s, &s->vn.tgt, &s->vn.tgt_cap, c.ts.n) || (!s->vn.part && dalloc(s, &s->vn.part, (size_t)VN_PART))))
+    return fail(-5, "device alloc failed (mqe_ppo_grad value-normalisation scratch)");
+  if (c.joint && grow_scratch(s, &p.jidx, &p.jidx_cap, (size_t)(c.M / c.L))) return fail(-5, "device alloc failed (mqe_ppo_grad joint-ratio scratch)");
+  if (c.bptt && (grow_scratch(s, &p.hscr, &p.hscr_cap, (size_t)PPO_MAX_WG * c.L * s->act.Hm() * p.rt) || (c.vn && grow_scratch(s, &p.idx, &p.idx_cap, (size_t)c.M))))
+    return fail(-5, "device alloc failed (mqe_ppo_grad back-propagation-through-time scratch)");
+  return 0;
+}
+// k_joint_expand: the groups' samples (chunks) as a flat list, group-major -> the minibatch everything behind it reads
+static PpoTraj launch_joint_expand(mqe_sim* s, const PpoCall& c, PpoTraj tr, hipStream_t q) {
+  const long long flat = tr.count * c.Aw;
+  hipLaunchKernelGGL(k_joint_expand, dim3(capped_grid(flat, JOINT_EXPAND_THREADS)), dim3(JOINT_EXPAND_THREADS), 0, q, tr.index, tr.first, tr.count,
+                     (long long)c.n_units, c.Aw, s->ppo.jidx);
+  tr.index = s->ppo.jidx; tr.first = 0; tr.count = flat;
+  return tr;
+}
+// [k_bptt_expand: the chunks' samples as a flat list, what the two kernels read as their index;] [k_vn_moments: the state updated from the minibatch's
+// returns;] k_vn_apply: the returns normalised -> the scratch the loss reads as its targets
+static const float* launch_value_norm(mqe_sim* s, const PpoCall& c, const PpoTraj& tr, hipStream_t q) {
+  const int32_t* index = tr.index; long long first = tr.first;
+  if (c.bptt) {
+    hipLaunchKernelGGL(k_bptt_expand, dim3(capped_grid(c.M, BPTT_EXPAND_THREADS)), dim3(BPTT_EXPAND_THREADS), 0, q, tr.index, tr.first, tr.count,
+                       (long long)c.n_chunks, tr.rows, c.L, s->ppo.idx);
+    index = s->ppo.idx; first = 0;
+  }
+  float* state = s->act.params + s->act.n_params;
+  const long long per = (long long)VN_THREADS * VN_PER; const int gm = capped_grid(c.M, per, VN_MAX_WG);
+  if (c.vn_update) hipLaunchKernelGGL(k_vn_moments, dim3(gm), dim3(VN_THREADS), 0, q, tr.ret, index, first, c.M, tr.n_total, (const float*)state, s->vn.part);
+  hipLaunchKernelGGL(k_vn_apply, dim3(capped_grid(c.M, per)), dim3(VN_THREADS), 0, q, tr.ret, index, first, c.M, tr.n_total, state,
+                     c.vn_update ? (const double*)s->vn.part : nullptr, gm, s->vn.tgt);
+  return s->vn.tgt;
+}
+// the gradient kernel of the plan over the minibatch's tiles, then k_ppo_reduce over the workgroups' partials
+static void launch_grad(mqe_sim* s, const PpoCall& c, PpoTraj tr, const mqe_ppo_loss* loss, float* grad_dev, float* stats_dev, hipStream_t q) {
+  const mqe_sim::Actor& a = s->act; mqe_sim::Ppo& p = s->ppo;
+  PpoLoss ls;
+  ls.clip = loss->clip_ratio; ls.value_coef = loss->value_coef; ls.entropy_coef = loss->entropy_coef; ls.value_clip = loss->value_clip;
+  ls.inv_m = (float)(1.0 / (double)c.M); ls.clip_value = c.clip_value ? 1 : 0;
+  ls.inv_g = c.joint ? (float)(1.0 / (double)c.groups) : ls.inv_m; ls.inv_a = (float)(1.0 / (double)c.Aw); ls.group = c.joint ? c.Aw : 1;
+  ls.dual = c.dual ? 1 : 0; ls.dual_clip = c.dual ? reinterpret_cast<const mqe_ppo_loss_ex*>(loss)->dual_clip : 0.0f;
+  BpttArgs bt = {(long long)c.ts.tail, (long long)(c.ts.rows * (size_t)(s->D + 1)), (long long)c.n_chunks, c.L, c.Aw, a.Ha, a.Hc, a.Hm()};
+  const int G = capped_grid(tr.count, p.rt, PPO_MAX_WG);
+  const float* params = a.params; const ActorShapes* nets = a.nets;
+  int log_std_off = a.log_std_off, n_params = a.n_params, D = s->D, relu = a.relu;
+  void* args[] = {&params, &nets, &tr, &log_std_off, &n_params, &D, &p.lds_rows, &p.uw, &relu, &p.part, &p.pst, &ls, &bt, &p.hscr};
+  (void)hipLaunchKernel(p.kern, dim3(G), dim3(ACT_THREADS), args, p.lds, q);      // launched() reports a failure
+  hipLaunchKernelGGL(k_ppo_reduce, dim3((a.n_params + PPO_REDUCE_THREADS - 1) / PPO_REDUCE_THREADS), dim3(PPO_REDUCE_THREADS), 0, q, (const float*)p.part,
+                     (const double*)p.pst, G, a.n_params, a.log_std_off, c.M, ls.value_coef, ls.entropy_coef, (const float*)a.params, grad_dev, stats_dev);
+}
 extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long long row_stride, const float* actions_dev, const float* logp_dev,
                             const float* value_dev, const float* adv_dev, const float* ret_dev, const int32_t* index_dev, long long first,
                             long long count, const mqe_ppo_loss* loss, int flags, float* grad_dev, float* stats_dev, void* stream) {
@@ -1831,142 +1988,19 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   if (!packed_dev || !actions_dev || !logp_dev || !value_dev || !adv_dev || !ret_dev || !loss || !grad_dev)
     return fail(-1, "mqe_ppo_grad: packed_dev, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, loss and grad_dev are required");
   if (!s->act.on) return fail(-6, "mqe_ppo_grad: no actor (mqe_actor_create)");
-  // MQE_PPO_BPTT (kernels_bptt.hpp): bits 8 .. 15 hold the chunk length L; index_dev / first / count are chunks
-  const bool bptt = (flags & MQE_PPO_BPTT) != 0;
-  const int L = bptt ? (flags >> MQE_PPO_CHUNK_SHIFT) & 0xff : 1;
-  if (!s->act.gru && (flags & (MQE_PPO_BPTT | (0xff << MQE_PPO_CHUNK_SHIFT))))
-    return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_BPTT and a chunk length in bits 8 .. 15 need an actor created with MQE_ACTOR_RECURRENT");
-  if (s->act.gru && !bptt)
-    return fail(-6, "mqe_ppo_grad: the actor was created with MQE_ACTOR_RECURRENT: its gradient is back-propagation through time over chunks of the recorded "
-                    "trajectory: pass flags = MQE_PPO_BPTT | L << MQE_PPO_CHUNK_SHIFT (32 | L << 8, 1 <= L <= 64; index_dev / first / count then mean chunks)");
-  if (bptt && (L < 1 || L > MQE_PPO_MAX_CHUNK))
-    return fail(-6, "mqe_ppo_grad: flags: the chunk length L in bits 8 .. 15 must be 1 .. MQE_PPO_MAX_CHUNK (64)");
-  flags &= ~(MQE_PPO_BPTT | (0xff << MQE_PPO_CHUNK_SHIFT));
-  if (s->act.sh.critic.n_layers == 0) return fail(-6, "mqe_ppo_grad: the actor was created without a critic: the loss has a value term");
-  TrajShape ts;
-  if (int rc = traj_shape(s, "mqe_ppo_grad", T, row_stride, &ts)) return rc;
-  if (int rc = check_aligned("mqe_ppo_grad", {{packed_dev, 16}, {actions_dev, 4}, {logp_dev, 4}, {value_dev, 4}, {adv_dev, 4}, {ret_dev, 4}, {index_dev, 4},
-                                              {grad_dev, 4}, {stats_dev, 4}}, "packed_dev: 16 bytes, the others: 4")) return rc;
-  const size_t rows = ts.rows, n = ts.n, pf = ts.packed_floats;
-  const size_t tail = (pf + 3) / 4 * 4, hs = (size_t)(s->act.Ha + s->act.Hc);
-  if (bptt && T % L != 0) return fail(-6, "mqe_ppo_grad: T must be a multiple of the chunk length L (flags bits 8 .. 15)");
-  if (bptt && row_stride < (long long)(tail + rows * hs))
-    return fail(-6, "mqe_ppo_grad: row_stride: with MQE_PPO_BPTT a row holds the packed length rounded up to a multiple of 4 and the R' (Ha + Hc) recorded state floats behind it");
-  // MQE_PPO_JOINT / MQE_PPO_DUAL_CLIP (kernels_ppo.hpp): index_dev / first / count are groups of A' samples (chunks); loss is an mqe_ppo_loss_ex
-  const bool joint = (flags & MQE_PPO_JOINT) != 0, dual = (flags & MQE_PPO_DUAL_CLIP) != 0;
-  const int Aw = s->Aw;
-  if (joint && 32 % Aw != 0)
-    return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_JOINT: the agents of an env-step share the lanes of one wavefront, so A' must divide 32 (this handle's A' is %s)",
-                std::to_string(Aw).c_str());
-  const size_t n_chunks = n / (size_t)L;      // (T / L) R'; without the bit: the samples
-  const size_t n_units = joint ? n_chunks / (size_t)Aw : n_chunks;      // what index_dev / first / count number: under MQE_PPO_JOINT the (T / L) N groups
-  if (count < 1) return fail(-6, "mqe_ppo_grad: count must be at least 1");
-  if (first < 0) return fail(-6, "mqe_ppo_grad: first must not be negative");
-  if (first > (1LL << 40) || count > (1LL << 40)) return fail(-6, "mqe_ppo_grad: first / count beyond any trajectory");
-  if (!index_dev && first + count > (long long)n_units)
-    return fail(-6, joint ? (bptt ? "mqe_ppo_grad: first + count exceeds the (T / L) x N chunk groups of the trajectory (MQE_PPO_JOINT)"
-                                  : "mqe_ppo_grad: first + count exceeds the T x N groups of the trajectory (MQE_PPO_JOINT)") :
-                    bptt ? "mqe_ppo_grad: first + count exceeds the (T / L) x R' chunks of the trajectory" : "mqe_ppo_grad: first + count exceeds the T x R' samples of the trajectory");
-  if (negative_or_not_finite(&loss->clip_ratio)) return fail(-6, "mqe_ppo_grad: clip_ratio must be finite and not negative");
-  if (negative_or_not_finite(&loss->value_coef)) return fail(-6, "mqe_ppo_grad: value_coef must be finite and not negative");
-  if (negative_or_not_finite(&loss->entropy_coef)) return fail(-6, "mqe_ppo_grad: entropy_coef must be finite and not negative");
-  if (negative_or_not_finite(&loss->value_clip)) return fail(-6, "mqe_ppo_grad: value_clip must be finite and not negative");
-  const mqe_ppo_loss_ex* lx = reinterpret_cast<const mqe_ppo_loss_ex*>(loss);      // read past the first 16 bytes under the bit only
-  if (dual) {
-    if (not_finite(&lx->dual_clip) || !(lx->dual_clip > 1.0f + loss->clip_ratio))
-      return fail(-6, "mqe_ppo_grad: dual_clip (MQE_PPO_DUAL_CLIP) must be finite and greater than 1 + clip_ratio");
-    uint32_t rw[3];
-    memcpy(rw, lx->reserved, sizeof rw);
-    if (rw[0] | rw[1] | rw[2]) return fail(-6, "mqe_ppo_grad: the reserved words of mqe_ppo_loss_ex (MQE_PPO_DUAL_CLIP) must be zero");
-  }
-  flags &= ~(MQE_PPO_JOINT | MQE_PPO_DUAL_CLIP);
-  if (flags & ~(MQE_PPO_CLIP_VALUE | MQE_PPO_VALUE_NORM | MQE_PPO_VALUE_NORM_UPDATE))
-    return fail(-6, "mqe_ppo_grad: unknown bits in flags (MQE_PPO_CLIP_VALUE, MQE_PPO_VALUE_NORM, MQE_PPO_VALUE_NORM_UPDATE, MQE_PPO_JOINT and MQE_PPO_DUAL_CLIP are "
-                    "the only ones)");
-  const bool vn = (flags & MQE_PPO_VALUE_NORM) != 0, vn_update = (flags & MQE_PPO_VALUE_NORM_UPDATE) != 0;
-  if (vn_update && !vn) return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_VALUE_NORM_UPDATE requires MQE_PPO_VALUE_NORM (the update precedes the normalisation it serves)");
-  if (vn)
-    if (int rc = need_value_norm(s, "mqe_ppo_grad", "MQE_PPO_VALUE_NORM")) return rc;
-  const mqe_sim::Actor& a = s->act;
-  float* vn_state = vn ? a.params + a.n_params : nullptr;
-  if (int rc = check_disjoint("mqe_ppo_grad", {{stats_dev, MQE_PPO_STATS * 4, "stats_dev"}, {grad_dev, (size_t)a.n_params * 4, "grad_dev"},
-                                               {packed_dev, ((size_t)T * row_stride + (bptt ? tail + rows * hs : pf)) * 4, "packed_dev"}, {actions_dev, n * 12, "actions_dev"},
-                                               {logp_dev, n * 4, "logp_dev"}, {value_dev, (n + rows) * 4, "value_dev"}, {adv_dev, n * 4, "adv_dev"},
-                                               {ret_dev, n * 4, "ret_dev"}, {index_dev, (size_t)(first + count) * 4, "index_dev"},
-                                               {a.params, (size_t)a.n_params * 4, "the parameter buffer"},
-                                               {vn_state, MQE_VALUE_NORM_STATE * 4, "the value-normalisation state"}}, 2)) return rc;
-  if (vn && (vn_scratch(s, &s->vn.tgt, &s->vn.tgt_cap, n) || (!s->vn.part && dalloc(s, &s->vn.part, (size_t)VN_PART))))
-    return fail(-5, "device alloc failed (mqe_ppo_grad value-normalisation scratch)");
-  if (!s->ppo.part) {                  // once per actor: the row tile of its shapes and the kernel of that tile, the scratch (hipMalloc synchronises)
-    mqe_sim::Ppo& p = s->ppo;
-    const bool ln = a.ln(); const PpoGradVariant& var = PPO_GRAD_VARIANTS[a.gru][!ln];
-    const int plain_rows = ppo_lds_rows(a.sh.actor, a.sh.critic, s->D), hm = a.Ha > a.Hc ? a.Ha : a.Hc;
-    p.lds_rows = ln ? ln_lds_rows(a.sh.actor, a.sh.critic, s->D, a.sh.hidden, a.sh.feat) : plain_rows;
-    p.uw = ln ? p.lds_rows - plain_rows - LN_STAT - LN_PART : 0;
-    if (a.gru) p.lds_rows = bptt_lds_rows(p.lds_rows, hm, ln);
-    const auto bytes = [&](int rt) { return a.gru ? bptt_lds_bytes(p.lds_rows, rt) : ppo_lds_bytes(p.lds_rows, rt); };
-    p.rt = bytes(64) <= PPO_LDS_LIMIT ? 64 : 32;
-    p.lds = (int)bytes(p.rt);
-    if (p.lds > PPO_LDS_LIMIT) return fail(-5, var.no_fit, std::to_string(hm).c_str());
-    p.kern = var.kern[p.rt == 32];
-    const hipError_t e = hipFuncSetAttribute(p.kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
-    if (p.lds > 48 * 1024 && e != hipSuccess) return fail(-5, "mqe_ppo_grad: cannot reserve LDS for %s", var.name);
-    if (dalloc(s, &p.pst, (size_t)PPO_MAX_WG * PPO_PST) || dalloc(s, &p.part, (size_t)PPO_MAX_WG * a.n_params, 0)) {
-      p.part = nullptr;                // the next call tries again; what was allocated is released with the handle
-      return fail(-5, "device alloc failed (mqe_ppo_grad scratch)");
-    }
-  }
+  PpoCall c = {};
+  PpoTraj tr = {packed_dev, row_stride, 0, 0, actions_dev, logp_dev, value_dev, adv_dev, ret_dev, index_dev, first, count};      // the caller's selection
+  if (int rc = ppo_check_actor(s, flags, &c)) return rc;                                // the BPTT bits and L against the actor; the critic
+  if (int rc = ppo_check_traj(s, T, flags, &tr, grad_dev, stats_dev, &c)) return rc;    // T, row_stride, alignment; T % L and the recorded tail; JOINT's A'
+  if (int rc = ppo_check_selection(tr, &c)) return rc;                                  // first / count against the units
+  if (int rc = ppo_check_loss(s, loss, flags, &c)) return rc;                           // the loss's floats, mqe_ppo_loss_ex; unknown bits; the value-norm flags
+  if (int rc = ppo_check_ranges(s, T, tr, grad_dev, stats_dev, c)) return rc;           // grad_dev / stats_dev overlap nothing the call reads
+  if (int rc = ppo_plan(s)) return rc;
+  if (int rc = ppo_scratch(s, c)) return rc;
   hipStream_t q = (hipStream_t)stream;
-  const int rt = s->ppo.rt;
-  const long long groups = count * L;  // under MQE_PPO_JOINT: the groups of the minibatch, the policy term's divisor
-  const int32_t* group_index = index_dev; const long long group_first = first, group_count = count;
-  if (joint) {                         // the groups' samples (chunks) as a flat list, group-major (k_joint_expand below): from here on the minibatch is that list
-    if (vn_scratch(s, &s->ppo.jidx, &s->ppo.jidx_cap, (size_t)(count * Aw))) return fail(-5, "device alloc failed (mqe_ppo_grad joint-ratio scratch)");
-    index_dev = (const int32_t*)s->ppo.jidx; first = 0; count *= Aw;
-  }
-  const long long tiles = (count + rt - 1) / rt;
-  const int G = (int)(tiles < PPO_MAX_WG ? tiles : PPO_MAX_WG);
-  const long long M = count * L;       // the samples of the minibatch
-  const int hm = a.Ha > a.Hc ? a.Ha : a.Hc;
-  // the recurrent gradient's scratch: made on first use, grown when L (count) grows; that call synchronises once
-  if (bptt && (vn_scratch(s, &s->ppo.hscr, &s->ppo.hscr_cap, (size_t)PPO_MAX_WG * L * hm * rt) || (vn && vn_scratch(s, &s->ppo.idx, &s->ppo.idx_cap, (size_t)M))))
-    return fail(-5, "device alloc failed (mqe_ppo_grad back-propagation-through-time scratch)");
-  PpoLoss ls;
-  ls.clip = loss->clip_ratio; ls.value_coef = loss->value_coef; ls.entropy_coef = loss->entropy_coef; ls.value_clip = loss->value_clip;
-  ls.inv_m = (float)(1.0 / (double)M); ls.clip_value = (flags & MQE_PPO_CLIP_VALUE) ? 1 : 0;
-  ls.inv_g = joint ? (float)(1.0 / (double)groups) : ls.inv_m; ls.inv_a = (float)(1.0 / (double)Aw); ls.group = joint ? Aw : 1;
-  ls.dual = dual ? 1 : 0; ls.dual_clip = dual ? lx->dual_clip : 0.0f;
-  if (joint) {
-    const long long we = (count + JOINT_EXPAND_THREADS - 1) / JOINT_EXPAND_THREADS;
-    hipLaunchKernelGGL(k_joint_expand, dim3((int)(we < 2048 ? we : 2048)), dim3(JOINT_EXPAND_THREADS), 0, q, group_index, group_first, group_count, (long long)n_units,
-                       Aw, (int32_t*)s->ppo.jidx);
-  }
-  if (vn) {                           // [update the state from the minibatch's returns,] normalise them into the scratch the loss reads
-    const int32_t* vi = index_dev; long long vf = first;
-    if (bptt) {                        // the chunks' samples as a flat list: what the two kernels read as their index
-      const long long we = (M + BPTT_EXPAND_THREADS - 1) / BPTT_EXPAND_THREADS;
-      hipLaunchKernelGGL(k_bptt_expand, dim3((int)(we < 2048 ? we : 2048)), dim3(BPTT_EXPAND_THREADS), 0, q, index_dev, first, count, (long long)n_chunks, (int)rows, L,
-                         (int32_t*)s->ppo.idx);
-      vi = (const int32_t*)s->ppo.idx; vf = 0;
-    }
-    const long long per = (long long)VN_THREADS * VN_PER, want = (M + per - 1) / per;
-    const int gm = (int)(want < VN_MAX_WG ? want : VN_MAX_WG);
-    if (vn_update)
-      hipLaunchKernelGGL(k_vn_moments, dim3(gm), dim3(VN_THREADS), 0, q, ret_dev, vi, vf, M, (long long)n, (const float*)vn_state, s->vn.part);
-    hipLaunchKernelGGL(k_vn_apply, dim3((int)(want < 2048 ? want : 2048)), dim3(VN_THREADS), 0, q, ret_dev, vi, vf, M, (long long)n, vn_state,
-                       vn_update ? (const double*)s->vn.part : nullptr, gm, s->vn.tgt);
-    ret_dev = s->vn.tgt;
-  }
-  PpoTraj tr;
-  tr.packed = packed_dev; tr.stride = row_stride; tr.rows = (int)rows; tr.n_total = (long long)n; tr.actions = actions_dev; tr.logp_old = logp_dev;
-  tr.value = value_dev; tr.adv = adv_dev; tr.ret = ret_dev; tr.index = index_dev; tr.first = first; tr.count = count;
-  BpttArgs bt = {(long long)tail, (long long)(rows * (size_t)(s->D + 1)), (long long)n_chunks, L, s->Aw, a.Ha, a.Hc, hm};
-  const float* params = a.params; const ActorShapes* nets = a.nets;
-  int log_std_off = a.log_std_off, n_params = a.n_params, D = s->D, relu = a.relu;
-  void* args[] = {&params, &nets, &tr, &log_std_off, &n_params, &D, &s->ppo.lds_rows, &s->ppo.uw, &relu, &s->ppo.part, &s->ppo.pst, &ls, &bt, &s->ppo.hscr};
-  (void)hipLaunchKernel(s->ppo.kern, dim3(G), dim3(ACT_THREADS), args, s->ppo.lds, q);      // launched() reports a failure
-  hipLaunchKernelGGL(k_ppo_reduce, dim3((a.n_params + PPO_REDUCE_THREADS - 1) / PPO_REDUCE_THREADS), dim3(PPO_REDUCE_THREADS), 0, q, (const float*)s->ppo.part,
-                     (const double*)s->ppo.pst, G, a.n_params, a.log_std_off, M, ls.value_coef, ls.entropy_coef, (const float*)a.params, grad_dev, stats_dev);
+  if (c.joint) tr = launch_joint_expand(s, c, tr, q);
+  if (c.vn) tr.ret = launch_value_norm(s, c, tr, q);
+  launch_grad(s, c, tr, loss, grad_dev, stats_dev, q);
   return launched();
 }
 

@@ -376,6 +376,11 @@ class HipEngine(EngineBase):
         return traj
 
     # ---- the PPO update on the engine's own parameters (mqe_ppo_grad / mqe_ppo_optimizer / mqe_ppo_adam; csrc/kernels_ppo.hpp) ---------------
+    def _ppo_units(self, T, L, joint):
+        """(how many, their noun): the units a minibatch of this trajectory is made of -- what index / first / count number (csrc/kernels_ppo.hpp)"""
+        N, Aw, _ = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
+        return T * N * (1 if joint else Aw) // max(L, 1), ("chunk groups" if L else "groups") if joint else ("chunks" if L else "samples")
+
     def ppo_grad(self, traj, index=None, first=0, count=None, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=None, out=None, value_norm=None,
                  update_value_norm=False, chunk_length=None, joint=False, dual_clip=None):
         """Gradient of rsl_rl's clipped-surrogate PPO loss over one minibatch of a Rollout that HipEngine.gae has filled, with respect to the
@@ -416,7 +421,7 @@ class HipEngine(EngineBase):
             _need_f32(f"traj.{name}", getattr(traj, name), shp)
         _need_packed(traj)
         n_params = self.actor_params()["flat"].numel()
-        total = T * N * (1 if joint else Aw) // max(L, 1)
+        total, what = self._ppo_units(T, L, joint)
         if index is not None:
             if not (index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.dim() == 1):
                 raise ValueError("index must be a contiguous one-dimensional int32 device tensor")
@@ -424,7 +429,6 @@ class HipEngine(EngineBase):
         first = int(first)
         count = total - first if count is None else int(count)
         if index is not None and (first < 0 or count < 1 or first + count > total):
-            what = ("chunk groups" if L else "groups") if joint else ("chunks" if L else "samples")
             raise ValueError(f"index holds {total} {what}: first={first}, count={count} reach outside it")
         grad, stats = out if out is not None else (None, None)
         for what, t, shp in (("out[0] (grad)", grad, (n_params,)), ("out[1] (stats)", stats, (abi.PPO_STATS,))):
@@ -479,11 +483,9 @@ class HipEngine(EngineBase):
         L = self._chunks("ppo_update", traj, chunk_length)
         vn = self._value_norm("ppo_update", value_norm)
         epochs, minibatches = int(epochs), int(minibatches)
-        T = int(traj.T)
-        N, Aw, _ = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
-        total = T * N * (1 if joint else Aw) // max(L, 1)
+        total, what = self._ppo_units(int(traj.T), L, joint)
         if epochs < 1 or minibatches < 1 or minibatches > total:
-            raise ValueError(f"ppo_update: epochs >= 1 and 1 <= minibatches <= {total} {('chunk groups' if L else 'groups') if joint else 'chunks' if L else 'samples'}")
+            raise ValueError(f"ppo_update: epochs >= 1 and 1 <= minibatches <= {total} {what}")
         dev = self.torch_device
         stats = torch.empty(epochs, minibatches, abi.PPO_STATS, dtype=torch.float32, device=dev)
         grad = torch.empty(self.actor_params()["flat"].numel(), dtype=torch.float32, device=dev)

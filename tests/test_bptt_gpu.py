@@ -1,7 +1,7 @@
 """-m gpu: the recurrent PPO update inside the engine (mqe_ppo_grad with MQE_PPO_BPTT; csrc/kernels_bptt.hpp: k_bptt_grad, k_bptt_ln_grad,
 k_bptt_expand; HipEngine.ppo_grad / ppo_update(chunk_length=)): (1) the gradient against the float64 twin within K_GPU 2^-24 S_n (tests/bptt_ref.py)
 over cell widths, depths, norms, chunk lengths, chunk counts at the tile edges, an index list and a range; (2) more tiles than workgroups; (3) value
-normalisation; (4) determinism, every element written, refusals; (5) a real rollout end to end.  go1gate, D = 16, A' = 2.
+normalisation, and chunk numbers outside the trajectory, which both paths clamp; (4) determinism, every element written, refusals; (5) a real rollout end to end.  go1gate, D = 16, A' = 2.
 
 THE STATISTICS' BOUNDS (derived; e_p and e_v are the largest per-sample deviations of the float32 torch twin's logp and value from float64 on the same
 chunks, the yardstick of tests/gru_ref.py, and the kernel is allowed 4 x them): the clip share is exact on kink-free inputs; the approximate KL is a
@@ -189,6 +189,61 @@ def test_value_normalisation_with_update():
     src = dict(s, ret=s["ret"].clone())
     src["ret"][tt, r[None, :]] = torch.as_tensor(np.asarray(vnref.normalise32(x.numpy(), after[3], after[4]), dtype=np.float32))
     check(s, t, chunks, L, ref.CFG, "value_norm + update tanh9x5_6x7_both L=5", src=src)
+    assert same_bits(t["ret"].cpu(), raw), "the caller's returns stay as they are"
+
+
+# ---- 3a. chunk numbers outside the trajectory ------------------------------------------------------------------------------------------------------------------
+def clamped_selection():
+    """the smallest recurrent shape (16 chunks of L = 5, one tile) with an index list that holds numbers below 0, numbers past the last chunk and one chunk
+    twice -> (s with that list, L, first, count, the chunks the kernels must read: the list clipped into [0, n_chunks)).  synth() makes every chunk
+    kink-free on its own, so a selection out of existing chunks is kink-free too: held here with the float64 twin, at synth()'s own margins"""
+    L = 5
+    s = synth("tanh9x5_6x7_both", 4, 10, L)
+    s = dict(s, index=torch.tensor([7, -3, 5, 16, 5, 1000, 2, 15, -2 ** 31, 2 ** 31 - 1, 9, 11], dtype=torch.int32))
+    first, count = 1, 10
+    chunks = np.clip(s["index"][first:first + count].numpy().astype(np.int64), 0, s["n_chunks"] - 1)
+    assert chunks.min() == 0 and chunks.max() == s["n_chunks"] - 1 and len(set(chunks.tolist())) < count
+    a64, c64 = gru_ref.doubles(*s["nets"][:2])
+    kinked = ref._kinked(s, (a64, c64, s["nets"][2]), chunks, L, dict(clip=ref.CLIP, value_clip=ref.VALUE_CLIP))[0]
+    assert not bool(kinked.any()), "the clipped selection keeps every sample the kink margin away from the loss's kinks"
+    return s, L, first, count, chunks
+
+
+def test_chunk_numbers_outside_the_trajectory_are_clamped():
+    """a chunk number outside [0, (T / L) R') is the caller's error and the kernel clamps it (bptt_chunks): the gradient and the statistics are those of
+    the clipped list, a duplicate counted twice"""
+    s, L, first, count, chunks = clamped_selection()
+    eng = handle(4)
+    install(eng, s)
+    t = upload(s, eng.torch_device)
+    rc = call(eng, s, t, L, first, count, True)
+    assert rc == 0, eng.lib.mqe_last_error().decode()
+    check(s, t, chunks, L, ref.CFG, f"clamped chunk numbers tanh9x5_6x7_both L={L} chunks={count}")
+    assert torch.equal(t["index"].cpu(), s["index"]), "the list is read only"
+
+
+def test_clamped_chunk_numbers_under_value_normalisation_with_update():
+    """the same selection under MQE_PPO_VALUE_NORM | _UPDATE (k_bptt_expand clamps, k_vn_moments / k_vn_apply read its list): the statistics fold in the
+    returns of the clipped chunks' count L samples, a duplicated chunk's as often as it occurs, and the loss reads them normalised"""
+    s, L, first, count, chunks = clamped_selection()
+    eng = handle(4)
+    views = install(eng, s, value_norm=True)
+    state = vnref.k_state()
+    views["value_norm"].copy_(torch.from_numpy(state))
+    raw = (s["ret"].double() * float(state[4]) + float(state[3])).float()
+    tt, r = ref.chunk_steps(s, chunks, L)
+    x = raw[tt, r[None, :]]
+    assert x.numel() == count * L
+    t = upload(s, eng.torch_device, ret=raw)
+    rc = call(eng, s, t, L, first, count, True, flags=abi.PPO_CLIP_VALUE | abi.PPO_VALUE_NORM | abi.PPO_VALUE_NORM_UPDATE | abi.PPO_BPTT | L << abi.PPO_CHUNK_SHIFT)
+    assert rc == 0, eng.lib.mqe_last_error().decode()
+    after = views["value_norm"].cpu().numpy().copy()
+    want = vnref.update(state, x.numpy())
+    for got, w, tol in zip(after[:3], want, vnref.tol_update(state, x.numpy())):
+        assert abs(float(got) - float(w)) <= tol, "the statistics fold in the returns of the clipped chunks' count L samples"
+    src = dict(s, ret=s["ret"].clone())
+    src["ret"][tt, r[None, :]] = torch.as_tensor(np.asarray(vnref.normalise32(x.numpy(), after[3], after[4]), dtype=np.float32))
+    check(s, t, chunks, L, ref.CFG, "clamped chunk numbers, value_norm + update tanh9x5_6x7_both L=5", src=src)
     assert same_bits(t["ret"].cpu(), raw), "the caller's returns stay as they are"
 
 

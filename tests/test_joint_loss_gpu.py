@@ -206,6 +206,45 @@ def test_layer_norm_handle():
 
 
 # ---- 5. a recurrent handle -------------------------------------------------------------------------------------------------------------------------
+def recurrent_call(eng, s, L, cfg, gindex, count, groups, what):
+    """mqe_ppo_grad(MQE_PPO_BPTT | MQE_PPO_JOINT ...) over gindex[0 .. count) on a recurrent handle, against the float64 twin over the chunk groups `groups`;
+    the statistics as test_bptt_gpu bounds them, with a group's A' log-probabilities"""
+    t = B.upload(dict(s, index=gindex), eng.torch_device)
+    lx = abi.PpoLossEx(cfg["clip"], cfg["value_coef"], cfg["entropy_coef"], cfg["value_clip"], cfg["dual_clip"] or 0.0)
+    rc = eng.lib.mqe_ppo_grad(eng.h, s["T"], t["packed"].data_ptr(), s["stride"], t["actions"].data_ptr(), t["logp_old"].data_ptr(), t["value"].data_ptr(),
+                              t["adv"].data_ptr(), t["ret"].data_ptr(), t["index"].data_ptr(), 0, count, C.cast(C.pointer(lx), C.POINTER(abi.PpoLoss)),
+                              flags_of(cfg) | abi.PPO_BPTT | L << abi.PPO_CHUNK_SHIFT, t["grad"].data_ptr(), t["stats"].data_ptr(), eng._stream())
+    torch.cuda.synchronize()
+    assert rc == 0, eng.lib.mqe_last_error().decode()
+    grad, stats = B.outputs(s, t)
+    g64, st64, S = ref.bptt_manual(s, groups, L, cfg)
+    got = {n: grad[o:o + int(np.prod(shp))].reshape(shp).numpy() for n, (o, shp) in
+           abi.actor_param_layout(s["a_dims"], s["c_dims"], False, s["hidden"], s["feat"], recurrent=True).items()}
+    worst, at = bptt_ref.ratio_to_bound(got, g64, S)
+    chunks = ref.chunks_of(groups, 2)
+    with torch.no_grad():
+        a32, c32, ls = s["nets"]
+        a64, c64 = gru_ref.doubles(a32, c32)
+        m64, v64 = bptt_ref.twin_outputs(a64, c64, s, chunks, L, torch.float64)
+        m32, v32 = bptt_ref.twin_outputs(a32, c32, s, chunks, L, torch.float32)
+    b = bptt_ref.sample_data(s, chunks, L)
+    logp = lambda m: ((-0.5 * ((b["actions"] - m.double()) * torch.exp(-ls.double())) ** 2 - ls.double()).sum(-1) - 1.5 * ref.LN2PI)
+    e_p = 2 * (4 * float((logp(m32) - logp(m64)).abs().max()) + 2.0 ** -22)           # a group's Delta adds two of them
+    e_v = 4 * float((v32.double() - v64).abs().max()) + 2.0 ** -22
+    d = (logp(m64) - b["logp_old"]).reshape(-1)
+    rho, A = torch.exp(ref.pair(d, 2)), ref.pair(b["adv"].reshape(-1), 2) * 0.5
+    dv = torch.maximum((v64 - b["ret"]).abs(), (b["v_old"] - b["ret"]).abs() + cfg["value_clip"])
+    tol = [float((A.abs() * rho).mean()) * math.expm1(e_p), float((2 * dv + e_v).mean()) * e_v, 0.0, 0.0, e_p, 0.0]
+    tol[3] = tol[0] + cfg["value_coef"] * tol[1]
+    tol = [x + 2.0 ** -22 * (1 + abs(float(st64[i]))) for i, x in enumerate(tol)]
+    dev_s = np.abs(stats.double().numpy() - st64)
+    print(f"joint_kernel_bptt {what}: gradient {worst:.2f} x 2^-24 S at {at} (bound {ref.K_GPU['bptt']:.0f}); statistics / their bounds " +
+          " ".join(f"{x / y:.2f}" for x, y in zip(dev_s[:5], tol[:5])))
+    assert worst <= ref.K_GPU["bptt"], (worst, at)
+    assert stats[5].item() == np.float32(st64[5]), "kink-free groups: the same clip count"
+    assert all(dev_s[i] <= tol[i] for i in range(5)), (dev_s, tol)
+
+
 @pytest.mark.parametrize("name", ["tanh64x64_both", "tanh7_5"])
 def test_recurrent_handle(name):
     """64-unit cells with both norms (k_bptt_ln_grad) and the smallest plain pair (k_bptt_grad): L = 4, T = 8, N = 5, so 10 chunk groups of two chunks;
@@ -214,45 +253,23 @@ def test_recurrent_handle(name):
     s = _SYNTH.setdefault(("bptt", name), ref.bptt_synth(name, 5, 8, L))
     eng = B.handle(5)
     B.install(eng, s)
-    dev = eng.torch_device
     for loss in ("joint", "joint+dual"):
         cfg = dict(ref.CFG, **ref.LOSSES[loss])
         for count in (1, 10):
-            t = B.upload(dict(s, index=s["gindex"]), dev)
-            lx = abi.PpoLossEx(cfg["clip"], cfg["value_coef"], cfg["entropy_coef"], cfg["value_clip"], cfg["dual_clip"] or 0.0)
-            rc = eng.lib.mqe_ppo_grad(eng.h, s["T"], t["packed"].data_ptr(), s["stride"], t["actions"].data_ptr(), t["logp_old"].data_ptr(), t["value"].data_ptr(),
-                                      t["adv"].data_ptr(), t["ret"].data_ptr(), t["index"].data_ptr(), 0, count, C.cast(C.pointer(lx), C.POINTER(abi.PpoLoss)),
-                                      flags_of(cfg) | abi.PPO_BPTT | L << abi.PPO_CHUNK_SHIFT, t["grad"].data_ptr(), t["stats"].data_ptr(), eng._stream())
-            torch.cuda.synchronize()
-            assert rc == 0, eng.lib.mqe_last_error().decode()
-            groups = s["gindex"][:count].numpy()
-            grad, stats = B.outputs(s, t)
-            g64, st64, S = ref.bptt_manual(s, groups, L, cfg)
-            got = {n: grad[o:o + int(np.prod(shp))].reshape(shp).numpy() for n, (o, shp) in
-                   abi.actor_param_layout(s["a_dims"], s["c_dims"], False, s["hidden"], s["feat"], recurrent=True).items()}
-            worst, at = bptt_ref.ratio_to_bound(got, g64, S)
-            chunks = ref.chunks_of(groups, 2)
-            with torch.no_grad():
-                a32, c32, ls = s["nets"]
-                a64, c64 = gru_ref.doubles(a32, c32)
-                m64, v64 = bptt_ref.twin_outputs(a64, c64, s, chunks, L, torch.float64)
-                m32, v32 = bptt_ref.twin_outputs(a32, c32, s, chunks, L, torch.float32)
-            b = bptt_ref.sample_data(s, chunks, L)
-            logp = lambda m: ((-0.5 * ((b["actions"] - m.double()) * torch.exp(-ls.double())) ** 2 - ls.double()).sum(-1) - 1.5 * ref.LN2PI)
-            e_p = 2 * (4 * float((logp(m32) - logp(m64)).abs().max()) + 2.0 ** -22)           # a group's Delta adds two of them
-            e_v = 4 * float((v32.double() - v64).abs().max()) + 2.0 ** -22
-            d = (logp(m64) - b["logp_old"]).reshape(-1)
-            rho, A = torch.exp(ref.pair(d, 2)), ref.pair(b["adv"].reshape(-1), 2) * 0.5
-            dv = torch.maximum((v64 - b["ret"]).abs(), (b["v_old"] - b["ret"]).abs() + cfg["value_clip"])
-            tol = [float((A.abs() * rho).mean()) * math.expm1(e_p), float((2 * dv + e_v).mean()) * e_v, 0.0, 0.0, e_p, 0.0]
-            tol[3] = tol[0] + cfg["value_coef"] * tol[1]
-            tol = [x + 2.0 ** -22 * (1 + abs(float(st64[i]))) for i, x in enumerate(tol)]
-            dev_s = np.abs(stats.double().numpy() - st64)
-            print(f"joint_kernel_bptt {name} {loss} chunk groups={count}: gradient {worst:.2f} x 2^-24 S at {at} (bound {ref.K_GPU['bptt']:.0f}); statistics / their bounds " +
-                  " ".join(f"{x / y:.2f}" for x, y in zip(dev_s[:5], tol[:5])))
-            assert worst <= ref.K_GPU["bptt"], (worst, at)
-            assert stats[5].item() == np.float32(st64[5]), "kink-free groups: the same clip count"
-            assert all(dev_s[i] <= tol[i] for i in range(5)), (dev_s, tol)
+            recurrent_call(eng, s, L, cfg, s["gindex"], count, s["gindex"][:count].numpy(), f"{name} {loss} chunk groups={count}")
+
+
+def test_recurrent_handle_clamps_chunk_group_numbers():
+    """chunk-group numbers outside [0, (T / L) N) are clamped, not followed (k_joint_expand, with (T / L) N as its range), and a group may come twice: the
+    smallest recurrent shape, N = 4, T = 10, L = 5, so 8 chunk groups.  design() makes every group kink-free on its own, so any list of existing groups is"""
+    L = 5
+    s = _SYNTH.setdefault(("bptt", "tanh9x5_6x7_both", 4), ref.bptt_synth("tanh9x5_6x7_both", 4, 10, L))
+    eng = B.handle(4)
+    B.install(eng, s)
+    gindex = torch.tensor([-4, 3, 8, 3, 2 ** 31 - 1, 6, -2 ** 31, 1], dtype=torch.int32)
+    groups = np.clip(gindex.numpy().astype(np.int64), 0, s["n_groups"] - 1)
+    assert s["n_groups"] == 8 and groups.min() == 0 and groups.max() == 7
+    recurrent_call(eng, s, L, dict(ref.CFG, **ref.LOSSES["joint+dual"]), gindex, len(gindex), groups, "tanh9x5_6x7_both joint+dual clamped chunk groups")
 
 
 # ---- 6. determinism, guards, inputs ----------------------------------------------------------------------------------------------------------------

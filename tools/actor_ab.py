@@ -6,13 +6,16 @@ T = 200, two 64 x 64 tanh networks.  --kinds: a comma list out of
               rollout(T) per step, every kind: the physics launches are the same on every handle, so a difference of medians is a difference of the
                   rollout kernels (+ the recorded tails, for "recorded");
               one ppo_update epoch (--minibatches slices), the kinds without a cell: per slice the gradient pair of launches + k_ppo_reduce + Adam;
-              rollout(T, record_hidden=True) per step, the kinds with a cell.
+              rollout(T, record_hidden=True) per step, the kinds with a cell;
+              one ppo_update(chunk_length=--chunk, value_norm=True) epoch on the gru handle, whose actor also keeps value normalisation: per slice
+                  k_bptt_expand, k_vn_moments, k_vn_apply, the recurrent gradient pair and Adam.
   --parent LIB   starts NO GPU work itself: alternates child processes --parent-rounds times -- this tool with the same --kinds and `bench.py --gpus 1` --
               once with the in-tree library and once with MQE_HIP_LIB=LIB (a build of the parent commit), stops at the first child that does not exit 0,
               and prints per kind whether the digests are equal and per path the medians of both and the parent's own min .. max over the alternated blocks.
 Every measuring child first prints ACTOR_DIGEST {kind: sha256}, taken before any timing while the handle is as created (fixed seeds): the bytes of the
-first rollout's actions, logp and value; without a cell also one ppo_grad on it (grad, stats); with a cell the rollout is a recorded one and traj.hidden
-is covered too.  The same bits out, which the tests' float64 bounds do not show.
+first rollout's actions, logp and value and one ppo_grad on it (grad, stats); with a cell the rollout is a recorded one, traj.hidden is covered too and
+the gradient is ppo_grad(chunk_length=--chunk); the gru handle adds a second call over a reversed chunk list with value_norm and update_value_norm, and
+the bytes of actor_params()["value_norm"] behind it.  The same bits out, which the tests' float64 bounds do not show.
   --trace-only KIND   that handle alone, warm-up and then two rollouts of T steps and, without a cell, nine gradient calls: the run to put under
               `rocprofv3 --kernel-trace --stats -- python tools/actor_ab.py --trace-only KIND` for the kernels' own times.
 Every figure is a HIP-event time (events recorded on the stream around a window, synchronised after it); all paths are warmed up.
@@ -30,6 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "multiagent-quadruped-environment_amd")]
 
 KINDS = {"plain": (False, False), "norms": (True, False), "gru": (False, True), "gru_norms": (True, True)}      # (both norms, a GRU cell)
+VN_KIND = "gru"      # the handle whose actor also keeps value normalisation (only the flagged calls below read or change it)
 
 
 def networks(D, H, norms, recurrent, dev):
@@ -66,13 +70,19 @@ def measure(a, say):
         norms, recurrent = KINDS[kind]
         env = make_mqe_env("go1gate", margs, custom_cfg(margs))[0]
         actor, critic = networks(env.observation_space.shape[0], a.hidden, norms, recurrent, dev)
-        env.set_actor(actor, critic, log_std=torch.full((3,), -0.5, device=dev), **({"layer_norm": True} if norms else {}), **({"recurrent": True} if recurrent else {}))
+        env.set_actor(actor, critic, log_std=torch.full((3,), -0.5, device=dev), **({"layer_norm": True} if norms else {}), **({"recurrent": True} if recurrent else {}),
+                      **({"value_norm": True} if kind == VN_KIND else {}))
         env.reset()
         eng = env.env.engine
         # the first rollout of a fresh handle [and one gradient on it]: before anything is timed or updated
         if recurrent:
-            traj = eng.rollout(T, record_hidden=True)
-            covered = (traj.actions, traj.logp, traj.value, traj.hidden)
+            traj = eng.gae(eng.rollout(T, record_hidden=True, time_outs=True), 0.99, 0.95, normalize=True, value_norm=False)
+            chunks = total // a.chunk
+            covered = (traj.actions, traj.logp, traj.value, traj.hidden, *eng.ppo_grad(traj, first=0, count=chunks // mb, chunk_length=a.chunk, value_norm=False, **kw))
+            if kind == VN_KIND:
+                last_first = torch.arange(chunks - 1, -1, -1, device=dev, dtype=torch.int32)
+                covered += (*eng.ppo_grad(traj, index=last_first, first=3, count=chunks // mb, chunk_length=a.chunk, value_norm=True, update_value_norm=True, **kw),
+                            eng.actor_params()["value_norm"])
         else:
             traj = eng.gae(eng.rollout(T, time_outs=True), 0.99, 0.95, normalize=True)
             covered = (traj.actions, traj.logp, traj.value, *eng.ppo_grad(traj, first=0, count=total // mb, **kw))
@@ -113,6 +123,9 @@ def measure(a, say):
                 plain = eng.rollout(T)
                 paths[f"rollout per step, {kind}"] = (lambda eng=eng, plain=plain: eng.rollout(T, out=plain), 1e3 / T, "us")
                 paths[f"rollout per step, {kind}, recorded"] = (lambda eng=eng, traj=traj: eng.rollout(T, out=traj, record_hidden=True), 1e3 / T, "us")
+                if kind == VN_KIND:
+                    paths[f"ppo_update epoch, {kind}, value_norm"] = (lambda eng=eng, traj=traj: eng.ppo_update(
+                        traj, epochs=1, minibatches=mb, lr=1e-4, max_grad_norm=1.0, chunk_length=a.chunk, value_norm=True, **kw), 1.0, "ms")
             else:
                 paths[f"rollout per step, {kind}"] = (lambda eng=eng, traj=traj: eng.rollout(T, out=traj), 1e3 / T, "us")
                 paths[f"ppo_update epoch, {kind}"] = (lambda eng=eng, traj=traj: eng.ppo_update(traj, epochs=1, minibatches=mb, lr=1e-4, max_grad_norm=1.0, **kw), 1.0, "ms")
@@ -135,7 +148,7 @@ def measure(a, say):
 def against_parent(a, say):
     """child processes only: the in-tree library and the parent's, alternated"""
     jobs = {"tool": [sys.executable, os.path.abspath(__file__), "--kinds", ",".join(a.kinds), "--envs", str(a.envs), "--T", str(a.T), "--rounds", str(a.rounds),
-                     "--minibatches", str(a.minibatches), "--hidden", str(a.hidden)],
+                     "--minibatches", str(a.minibatches), "--hidden", str(a.hidden), "--chunk", str(a.chunk)],
             "bench": [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(a.bench_steps), "--warmup", "50", "--no_cpu_baseline",
                       "--no_strict_f32", "--no_configs"]}
     got, digests = {}, {}
@@ -183,6 +196,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--minibatches", type=int, default=4)
     ap.add_argument("--hidden", type=int, default=64)
+    ap.add_argument("--chunk", type=int, default=8, help="the chunk length of the recurrent gradient calls; divides --T")
     ap.add_argument("--trace-only", default=None, metavar="KIND", choices=list(KINDS))
     ap.add_argument("--parent", default=None, metavar="LIB")
     ap.add_argument("--parent-rounds", type=int, default=3)
