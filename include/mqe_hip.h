@@ -675,6 +675,41 @@ int mqe_ppo_adam(mqe_sim* s, const float* grad_dev, long long step, float lr, fl
  *   bytes, exceeds the 160 KiB of a workgroup; every shape with all widths and obs_dim <= 128 fits.  A handle created without the bit launches
  *   exactly the kernels it launched before. */
 
+/* ---- Multi-agent transformer policy in the rollout: MAT's encoder and decoder evaluated by the engine (csrc/kernels_mat.hpp: k_actor_mat) ----
+ * v17, additive: no export, no prototype, no struct and no #define of this header changes.  OpenRL's `--algo mat` (cfgs/mat.yaml; MATNet) at the
+ * defaults the file leaves untouched: n_block = 1, n_head = 1, n_embd = E = 64, dec_actor = False, continuous actions.  THE CONSTANT BELOW IS NOT
+ * #DEFINED BY THIS HEADER (tests/test_rollout.py pins the exact set of MQE_ACTOR_* defines).  Its value is stated here, defined under this name in
+ * csrc/kernels_mat.hpp (which the engine compiles) and mirrored in mqe/engine/abi.py; tests/test_mat.py holds the three statements together.  A C
+ * caller passes the number.  The bit was refused as unknown before.
+ *   MQE_ACTOR_TRANSFORMER = 32
+ * A bit of the KIND BYTE of mqe_actor_shape.activation.  With it actor_layers = critic_layers = 2, actor_dims = {D, E, 3}, critic_dims = {D, E, 1}
+ *   with the same E: the "actor" is MAT's decoder, the "critic" the value head its encoder always carries (there is no such handle without one).
+ *   MQE_ACTOR_TANH is the only accepted kind (GELU is implied); MQE_ACTOR_VALUE_NORM combines with it (mat.yaml: use_valuenorm).
+ * The network, with LN = LayerNorm(eps = 1e-5, weight and bias), GELU the exact erf form, every Linear with a bias, A' the agents of an env:
+ *     Attn(key, value, query; masked): k = Wk key + bk, v = Wv value + bv, q = Wq query + bq;  s_ij = (q_i . k_j) / sqrt(E), masked: only j <= i;
+ *                                      p = softmax_j(s);  y_i = sum_j p_ij v_j;  out = Wp y + bp
+ *     Encoder  x = LN_E(GELU(Linear_{D->E}(LN_D(obs))));  x = LN_E(x + Attn(x, x, x; unmasked));  rep = LN_E(x + Linear(GELU(Linear(x))))
+ *              value_a = Linear_{E->1}(LN_E(GELU(Linear_{E->E}(rep_a))))
+ *     Decoder  s_0 = 0, s_a = the action of agent a - 1 as sampled (raw: before action_gain, unclipped);  x = LN_E(GELU(Linear_{3->E}(s)))
+ *              x = LN_E(x + Attn(x, x, x; masked));  x = LN_E(rep + Attn(key = x, value = x, query = rep; masked));  x = LN_E(x + Linear(GELU(Linear(x))))
+ *              mean_a = Linear_{E->3}(LN_E(GELU(Linear_{E->E}(x_a))))
+ *     Head     sigma_j = 0.5 sigmoid(log_std_j) (MAT's, not exp(log_std));  a = mean + sigma z;  logp = sum_j (-0.5 z_j^2 - ln sigma_j) - 1.5 ln(2 pi)
+ *   Acting is autoregressive inside one launch: agent a's mean is conditioned on the sampled actions of agents 0 .. a - 1; its bits are those of one
+ *   parallel decoder pass over the final s (csrc/kernels_mat.hpp, EVALUATION ORDER), which is what a learner evaluates.  z is the draw of the plain
+ *   actor, keyed (seed, global env id, MQE_RNG_ACTOR + n, agent * 3 + j): shards and checkpoints continue as they do there.  MQE_ROLLOUT_DETERMINISTIC: z = 0.
+ * Parameter buffer: every Linear weight (out, in) row-major then bias, every norm weight -- created as 1 -- then bias, in the order the operators run:
+ *   the encoder (obs_norm, obs_fc, ln, attn.key / .query / .value / .proj, ln1, mlp0, mlp1, ln2, head0, head_ln), the decoder (act_fc, ln, attn1.*, ln1,
+ *   attn2.*, ln2, mlp0, mlp1, ln3, head0, head_ln), then value_out (E -> 1), mean_out (E -> 3), log_std[3] and the value-normalisation state:
+ *   2 D + D E + 18 E^2 + 45 E + 7 trainable floats.  mqe_ppo_optimizer and mqe_ppo_adam cover them like any weight.
+ * mqe_rollout, mqe_gae, mqe_rollout_time_outs, mqe_ppo_optimizer and mqe_ppo_adam work unchanged on such a handle; there is no carried state.
+ *   mqe_ppo_grad refuses it (-6, nothing enqueued or written): the gradient through the attention is not in the engine; a learner differentiates the
+ *   torch twin and steps the buffer with mqe_ppo_adam or copies its parameters back.
+ * -6 naming the field: the bit with MQE_ACTOR_LAYER_NORM, MQE_ACTOR_FEATURE_NORM or MQE_ACTOR_RECURRENT (activation); the relu kind (activation);
+ *   actor_layers / critic_layers other than 2; critic_dims[1] != actor_dims[1] (critic_dims); E < 4 or E % 4 != 0 (actor_dims); an E whose LDS need,
+ *   obs_dim + 6 E + 43 rows of 260 bytes, exceeds the 160 KiB of a workgroup (actor_dims; E = 64 fits for every obs_dim <= 128); an A' that does not
+ *   divide the 64 rows of a tile (A').  A handle created without the bit launches exactly the kernels it launched before.
+ * Not built: the on-device gradient, n_block > 1, n_head > 1, dec_actor, discrete actions. */
+
 /* ---- Joint-ratio and dual-clip policy losses in mqe_ppo_grad (csrc/kernels_ppo.hpp: the loss head of the four gradient kernels, k_joint_expand) ----
  * v17, additive: no export, no prototype and no #define of this header changes; mqe_ppo_loss_ex above is the one new typedef.  OpenRL's
  * use_joint_action_loss (jrpo.yaml) and dual_clip_ppo / dual_clip_coeff (dppo.yaml).  THE TWO CONSTANTS BELOW ARE NOT #DEFINED BY THIS HEADER

@@ -26,6 +26,7 @@
 #include "kernels_ln.hpp"
 #include "kernels_gru.hpp"
 #include "kernels_actor_critic.hpp"
+#include "kernels_mat.hpp"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, const char* a = "", const char* b = "", const char* c = "") {      // fmt: up to three %s
@@ -138,6 +139,7 @@ struct mqe_sim {
     // MQE_ACTOR_RECURRENT (kernels_gru.hpp): the widths of the two GRU cells and the live state [N A'][Ha + Hc], made zeroed with the actor and
     // released with it; selects the recurrent kernels.  The actor's, like Adam's moments: never in state_bufs
     bool gru = false; int Ha = 0, Hc = 0;
+    bool mat = false;             // MQE_ACTOR_TRANSFORMER (kernels_mat.hpp): sh.actor.dims = {D, E, 3}, the parameters are the transformer's; selects k_actor_mat
     int Hm() const { return Ha > Hc ? Ha : Hc; }      // the wider cell: what the recurrent gradient's LDS rows and state scratch are sized by
     float* hstate = nullptr;
     ActorShapes* nets = nullptr;      // `sh` on the device, THE image of every actor: the recurrent rollout kernels and the gradient kernels read it
@@ -1573,12 +1575,14 @@ static void view_1d_f32(mqe_tensor_view* v, float* p, int n) {
 }
 
 // ---- on-device rollouts: mqe_actor_create / mqe_actor_params / mqe_rollout (include/mqe_hip.h) ---------------------------------
-// the four rollout kernels, [recurrent][any norm]: symbol, name in a refusal, LDS rule.  mqe_actor_create picks an actor's row; nothing else chooses
-static const ActorVariant ACTOR_VARIANTS[2][2] = {
+// the rollout kernels, [recurrent; 2: transformer][any norm]: symbol, name in a refusal, LDS rule.  mqe_actor_create picks an actor's row; nothing else chooses
+#define MAT_VARIANT {(const void*)k_actor_mat, "k_actor_mat", [](int D, int E, int) { return actor_mat_lds_bytes(D, E); }}      // its rule reads (obs_dim, n_embd)
+static const ActorVariant ACTOR_VARIANTS[3][2] = {
   {{(const void*)k_actor, "k_actor", [](int ldh, int, int) { return actor_lds_bytes(ldh); }},
    {(const void*)k_actor_ln, "k_actor_ln", [](int ldh, int, int) { return actor_ln_lds_bytes(ldh); }}},
   {{(const void*)k_actor_gru, "k_actor_gru", [](int ldh, int Ha, int Hc) { return actor_gru_lds_bytes(ldh, Ha, Hc, false); }},
    {(const void*)k_actor_gru_ln, "k_actor_gru_ln", [](int ldh, int Ha, int Hc) { return actor_gru_lds_bytes(ldh, Ha, Hc, true); }}},
+  {MAT_VARIANT, MAT_VARIANT},
 };
 struct NormWeight { int off, n; };      // a norm's weight in the flat parameter buffer: the n floats that start at 1
 // one network's dims[] against the limits; fills its offsets into the flat parameter buffer from *off on and notes every norm weight it passes
@@ -1630,6 +1634,27 @@ static int grow_scratch(mqe_sim* s, T** p, size_t* cap, size_t need) {
   *cap = need;
   return 0;
 }
+// MQE_ACTOR_TRANSFORMER (kernels_mat.hpp): what mqe_actor_shape must say with the bit, each refusal naming its field
+static int mat_check_args(const mqe_sim* s, const mqe_actor_shape* sh, int kind) {
+  if (sh->activation & (MQE_ACTOR_LAYER_NORM | MQE_ACTOR_FEATURE_NORM | MQE_ACTOR_RECURRENT))
+    return fail(-6, "mqe_actor_create: activation: MQE_ACTOR_TRANSFORMER does not combine with MQE_ACTOR_LAYER_NORM, MQE_ACTOR_FEATURE_NORM or MQE_ACTOR_RECURRENT "
+                    "(the transformer has its own norms and no state)");
+  if (kind != MQE_ACTOR_TANH) return fail(-6, "mqe_actor_create: activation: MQE_ACTOR_TRANSFORMER takes the kind MQE_ACTOR_TANH only (GELU is implied)");
+  if (sh->actor_layers != 2) return fail(-6, "mqe_actor_create: actor_layers: MQE_ACTOR_TRANSFORMER takes actor_layers = 2, actor_dims = {obs_dim, E, 3}");
+  if (sh->critic_layers != 2)
+    return fail(-6, "mqe_actor_create: critic_layers: MQE_ACTOR_TRANSFORMER takes critic_layers = 2, critic_dims = {obs_dim, E, 1} (the encoder always carries the value head)");
+  const int E = sh->actor_dims[1];
+  if (sh->actor_dims[0] != sh->obs_dim || sh->actor_dims[2] != 3) return fail(-6, "mqe_actor_create: actor_dims: MQE_ACTOR_TRANSFORMER takes {obs_dim, E, 3}");
+  if (sh->critic_dims[0] != sh->obs_dim || sh->critic_dims[2] != 1) return fail(-6, "mqe_actor_create: critic_dims: MQE_ACTOR_TRANSFORMER takes {obs_dim, E, 1}");
+  if (sh->critic_dims[1] != E) return fail(-6, "mqe_actor_create: critic_dims: MQE_ACTOR_TRANSFORMER has one width E: critic_dims[1] must equal actor_dims[1]");
+  if (E < 4 || E % 4 != 0) return fail(-6, "mqe_actor_create: actor_dims: the transformer's width E = actor_dims[1] must be a positive multiple of 4");
+  if (actor_mat_lds_bytes(sh->obs_dim, E) > MAT_LDS_LIMIT)
+    return fail(-6, "mqe_actor_create: actor_dims: the transformer's width E = %s (with obs_dim) is too large: obs_dim + 6 E + 43 rows of 260 bytes exceed the 160 KiB of a workgroup",
+                std::to_string(E).c_str());
+  if (ACT_ROWS % s->Aw != 0)
+    return fail(-6, "mqe_actor_create: MQE_ACTOR_TRANSFORMER: the agents of an env share one tile of 64 rows, so A' must divide 64 (this handle's A' is %s)", std::to_string(s->Aw).c_str());
+  return 0;
+}
 // ---- mqe_actor_create, stage by stage as mqe_sim_create: the argument checks, the layout, the device buffers, the initial values -------------
 static int actor_check_args(const mqe_sim* s, const mqe_actor_shape* sh) {
   if (s->step_open) return fail(-8, "mqe_actor_create inside an open step");
@@ -1639,15 +1664,41 @@ static int actor_check_args(const mqe_sim* s, const mqe_actor_shape* sh) {
   if (sh->obs_dim != s->D) return fail(-6, "mqe_actor_create: obs_dim differs from the width of this scene's MQE_T_WRAPPER_OBS");
   if (sh->obs_dim > MQE_ACTOR_MAX_OBS) return fail(-6, "mqe_actor_create: obs_dim above MQE_ACTOR_MAX_OBS (128)");
   if (sh->act_dim != 3) return fail(-6, "mqe_actor_create: act_dim must be 3");
-  const int kind = sh->activation & ~(MQE_ACTOR_VALUE_NORM | MQE_ACTOR_LAYER_NORM | MQE_ACTOR_FEATURE_NORM | MQE_ACTOR_RECURRENT);
+  const int kind = sh->activation & ~(MQE_ACTOR_VALUE_NORM | MQE_ACTOR_LAYER_NORM | MQE_ACTOR_FEATURE_NORM | MQE_ACTOR_RECURRENT | MQE_ACTOR_TRANSFORMER);
   if (kind != MQE_ACTOR_TANH && kind != MQE_ACTOR_RELU)
     return fail(-6, "mqe_actor_create: activation must be MQE_ACTOR_TANH or MQE_ACTOR_RELU (or-ed with MQE_ACTOR_LAYER_NORM, MQE_ACTOR_FEATURE_NORM, MQE_ACTOR_RECURRENT, MQE_ACTOR_VALUE_NORM or not)");
+  if (sh->activation & MQE_ACTOR_TRANSFORMER)
+    if (int rc = mat_check_args(s, sh, kind)) return rc;
   if ((sh->activation & MQE_ACTOR_VALUE_NORM) && sh->critic_layers == 0) return fail(-6, "mqe_actor_create: activation: MQE_ACTOR_VALUE_NORM needs a critic (the statistics are those of its targets)");
   if (not_finite(&sh->action_gain) || std::fabs(sh->action_gain) >= 1e30f) return fail(-6, "mqe_actor_create: action_gain is not finite");
   return 0;
 }
+// MQE_ACTOR_TRANSFORMER (kernels_mat.hpp): the layout of a transformer handle -- the two ActorNet hold the dims alone; the parameters follow the program
+static int mat_layout(const mqe_actor_shape* sh, mqe_sim::Actor* a, std::vector<NormWeight>* gammas) {
+  const int D = sh->obs_dim, E = sh->actor_dims[1];
+  for (ActorNet* net : {&a->sh.actor, &a->sh.critic}) { net->n_layers = 2; net->dims[0] = D; net->dims[1] = E; net->w_off[0] = net->w_off[1] = 0; }
+  a->sh.actor.dims[2] = 3; a->sh.critic.dims[2] = 1;
+  a->sh.inv_actor[0] = a->sh.inv_critic[0] = (float)(1.0 / (double)D); a->sh.inv_actor[1] = a->sh.inv_critic[1] = (float)(1.0 / (double)E);
+  a->sh.inv_actor[2] = (float)(1.0 / std::sqrt((double)E));      // c of the attention's scores
+  int off = 0;                                                   // every norm's weight, by the walk the kernel does
+  for (const auto& prog : {std::make_pair(MAT_ENC_HOST, MAT_ENC_N), std::make_pair(MAT_DEC_HOST, MAT_DEC_N)})
+    for (int i = 0; i < prog.second; i++) {
+      const MatOp& op = prog.first[i];
+      if (op.kind == MAT_LN) gammas->push_back({off, mat_width(op.kin, D, E)});
+      off += mat_op_floats(op, D, E);
+    }
+  if (off != mat_enc_floats(D, E) + mat_dec_floats(E)) return fail(-100, "mqe_actor_create: the transformer's program and its closed parameter count disagree");
+  a->n_params = mat_param_floats(D, E); a->log_std_off = a->n_params - 3; a->ldh = D > E ? D : E; a->relu = 0; a->gain = sh->action_gain;
+  a->vnorm = (sh->activation & MQE_ACTOR_VALUE_NORM) != 0; a->mat = true;
+  a->variant = &ACTOR_VARIANTS[2][0];
+  a->lds = a->variant->lds_bytes(D, E, 0);
+  if (a->lds > 48 * 1024 && hipFuncSetAttribute(a->variant->kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a->lds) != hipSuccess)
+    return fail(-5, "mqe_actor_create: cannot reserve LDS for %s", a->variant->name);
+  return 0;
+}
 // everything but the buffers: the networks against the limits, their offsets (the norm weights noted in `gammas`), the kernel and its LDS.  The last stage that can refuse
 static int actor_layout(const mqe_actor_shape* sh, mqe_sim::Actor* a, std::vector<NormWeight>* gammas) {
+  if (sh->activation & MQE_ACTOR_TRANSFORMER) return mat_layout(sh, a, gammas);
   const bool ln_hidden = (sh->activation & MQE_ACTOR_LAYER_NORM) != 0, ln_feat = (sh->activation & MQE_ACTOR_FEATURE_NORM) != 0;
   const bool gru = (sh->activation & MQE_ACTOR_RECURRENT) != 0;
   int off = 0, ldh = 0;
@@ -1839,6 +1890,9 @@ struct PpoCall {
 };
 // MQE_PPO_BPTT (kernels_bptt.hpp): bits 8 .. 15 hold the chunk length L; index_dev / first / count are chunks
 static int ppo_check_actor(const mqe_sim* s, int flags, PpoCall* c) {
+  if (s->act.mat)
+    return fail(-6, "mqe_ppo_grad: the actor was created with MQE_ACTOR_TRANSFORMER: the gradient through the attention is not in the engine yet; differentiate the "
+                    "torch twin (mqe.utils.actor_net.MATNet.evaluate on the trajectory) and step with mqe_ppo_adam or copy the parameters back");
   c->bptt = (flags & MQE_PPO_BPTT) != 0; c->L = c->bptt ? (flags >> MQE_PPO_CHUNK_SHIFT) & 0xff : 1;
   if (!s->act.gru && (flags & (MQE_PPO_BPTT | (0xff << MQE_PPO_CHUNK_SHIFT))))
     return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_BPTT and a chunk length in bits 8 .. 15 need an actor created with MQE_ACTOR_RECURRENT");

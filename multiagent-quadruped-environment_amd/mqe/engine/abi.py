@@ -138,6 +138,10 @@ PPO_BPTT, PPO_CHUNK_SHIFT, PPO_MAX_CHUNK = 32, 8, 64
 # first / count number the groups of A' samples of one env-step; `loss` points at a PpoLossEx
 PPO_JOINT, PPO_DUAL_CLIP = 64, 128
 LN_STAT, BPTT_CELL_ROWS, BPTT_LDS_LIMIT = 8, 7, 160 * 1024      # csrc/kernels_ln.hpp, kernels_bptt.hpp: what the LDS rule of the recurrent gradient is made of
+# the Multi-Agent Transformer policy (include/mqe_hip.h states the value, csrc/kernels_mat.hpp defines it): a bit of the kind byte of
+# mqe_actor_shape.activation -- actor_dims = (D, E, 3) and critic_dims = (D, E, 1) then describe MAT's encoder and decoder --, and what its LDS rule is made of
+ACTOR_TRANSFORMER = 32
+MAT_SLABS, MAT_FIXED_ROWS, MAT_LDS_LIMIT = 6, 3 + 4 + 4 + LN_PART, 160 * 1024
 RNG_ACTOR = 0x70000000          # csrc/mqe_common.hpp MQE_RNG_ACTOR: `count` of the actor's draws = RNG_ACTOR + post-physics steps so far
 
 
@@ -190,7 +194,27 @@ def bptt_row_tile(actor_dims, critic_dims, layer_norm=False, feature_norm=False)
     return next((rt for rt in (64, 32) if bptt_lds_bytes(rows, rt) <= BPTT_LDS_LIMIT), None)
 
 
-def actor_param_layout(actor_dims, critic_dims=None, value_norm=False, layer_norm=False, feature_norm=False, recurrent=False):
+def actor_mat_lds_bytes(obs_dim, n_embd):
+    """LDS of k_actor_mat (csrc/kernels_mat.hpp actor_mat_lds_bytes): the observation's D rows, MAT_SLABS slabs of E rows, the rows of s, the
+    outputs, the kept results and the norm's partials, in rows of 65 floats.  mqe_actor_create refuses above MAT_LDS_LIMIT."""
+    return (int(obs_dim) + MAT_SLABS * int(n_embd) + MAT_FIXED_ROWS) * ACT_LD * 4
+
+
+def mat_param_blocks(obs_dim, n_embd):
+    """[(name, shape)] of the transformer's tensors in the engine's order -- mqe.utils.actor_net.MATNet's parameters() without log_std: the
+    encoder and the decoder in the order their operators run, then the two narrow output layers (csrc/kernels_mat.hpp, PARAMETERS)"""
+    D, E = int(obs_dim), int(n_embd)
+    ln = lambda name, n: [(f"mat.{name}.weight", (n,)), (f"mat.{name}.bias", (n,))]
+    lin = lambda name, k, n: [(f"mat.{name}.weight", (n, k)), (f"mat.{name}.bias", (n,))]
+    attn = lambda name: [b for part in ("key", "query", "value", "proj") for b in lin(f"{name}.{part}", E, E)]
+    return (ln("enc.obs_norm", D) + lin("enc.obs_fc", D, E) + ln("enc.ln", E) + attn("enc.attn") + ln("enc.ln1", E) + lin("enc.mlp0", E, E) +
+            lin("enc.mlp1", E, E) + ln("enc.ln2", E) + lin("enc.head0", E, E) + ln("enc.head_ln", E) +
+            lin("dec.act_fc", 3, E) + ln("dec.ln", E) + attn("dec.attn1") + ln("dec.ln1", E) + attn("dec.attn2") + ln("dec.ln2", E) +
+            lin("dec.mlp0", E, E) + lin("dec.mlp1", E, E) + ln("dec.ln3", E) + lin("dec.head0", E, E) + ln("dec.head_ln", E) +
+            lin("value_out", E, 1) + lin("mean_out", E, 3))
+
+
+def actor_param_layout(actor_dims, critic_dims=None, value_norm=False, layer_norm=False, feature_norm=False, recurrent=False, transformer=False):
     """The flat parameter buffer of mqe_actor_params as an ordered {name: (offset, shape)}: per layer W (out, in) row-major as
     torch.nn.Linear.weight, then b; the actor's layers, then the critic's, then log_std[3].  Names: actor.<layer>.weight / .bias,
     critic.<layer>.weight / .bias, log_std.  value_norm (an actor created with ACTOR_VALUE_NORM): + "value_norm", the VALUE_NORM_STATE
@@ -198,8 +222,21 @@ def actor_param_layout(actor_dims, critic_dims=None, value_norm=False, layer_nor
     <who>.norm_in.weight / .bias (D each) in front of a network's layer 0; layer_norm (ACTOR_LAYER_NORM): <who>.<layer>.norm.weight / .bias
     (n each) behind the bias of every hidden layer.  With both off the layout is the plain one.  recurrent (ACTOR_RECURRENT; every network needs
     a hidden layer, H = the last one's width): <who>.gru.weight_ih / .weight_hh (3H, H), .bias_ih / .bias_hh (3H) and, with layer_norm,
-    <who>.gru.norm.weight / .bias (H) in front of the output layer's weight -- torch.nn.GRU's own tensors and order."""
+    <who>.gru.norm.weight / .bias (H) in front of the output layer's weight -- torch.nn.GRU's own tensors and order.
+    transformer (ACTOR_TRANSFORMER; actor_dims = (D, E, 3), critic_dims = (D, E, 1) or None for the same): mat_param_blocks' names, mat.enc.*, mat.dec.*,
+    mat.value_out.*, mat.mean_out.*, in MATNet's parameters() order; log_std and value_norm behind them as always.  The trainable count is
+    2 D + D E + 18 E^2 + 45 E + 7:  the encoder 2 D + D E + 7 E^2 + 16 E, the decoder 11 E^2 + 25 E, value_out E + 1, mean_out 3 E + 3, log_std 3."""
     out, off = {}, 0
+    if transformer:
+        dims = [int(d) for d in actor_dims]
+        if len(dims) != 3 or dims[2] != 3 or (critic_dims and [int(d) for d in critic_dims] != [dims[0], dims[1], 1]):
+            raise ValueError("transformer: actor_dims = (D, E, 3) and critic_dims = (D, E, 1) with the same E (the encoder carries the value head)")
+        if layer_norm or feature_norm or recurrent:
+            raise ValueError("transformer: the transformer has its own norms and no state (no layer_norm, feature_norm or recurrent)")
+        for name, shape in mat_param_blocks(dims[0], dims[1]):
+            out[name] = (off, shape)
+            off += shape[0] * (shape[1] if len(shape) > 1 else 1)
+        actor_dims, critic_dims = (), ()
     for who, dims in (("actor", actor_dims), ("critic", critic_dims or ())):
         if feature_norm and len(dims) > 1:
             d = int(dims[0])
@@ -228,9 +265,9 @@ def actor_param_layout(actor_dims, critic_dims=None, value_norm=False, layer_nor
     return out
 
 
-def actor_param_count(actor_dims, critic_dims=None, value_norm=False, layer_norm=False, feature_norm=False, recurrent=False):
+def actor_param_count(actor_dims, critic_dims=None, value_norm=False, layer_norm=False, feature_norm=False, recurrent=False, transformer=False):
     """floats of the buffer: the trainable parameters, + VALUE_NORM_STATE with value_norm"""
-    off, shape = list(actor_param_layout(actor_dims, critic_dims, value_norm, layer_norm, feature_norm, recurrent).values())[-1]
+    off, shape = list(actor_param_layout(actor_dims, critic_dims, value_norm, layer_norm, feature_norm, recurrent, transformer).values())[-1]
     return off + shape[0]
 
 

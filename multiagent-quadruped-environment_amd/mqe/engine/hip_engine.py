@@ -180,7 +180,7 @@ class HipEngine(EngineBase):
 
     # ---- on-device rollouts (mqe_actor_create / mqe_actor_params / mqe_rollout) -------------------------------------------------------
     def create_actor(self, actor_dims, critic_dims=None, activation="tanh", action_gain=1.0, value_norm=False, layer_norm=False, feature_norm=False,
-                     recurrent=False):
+                     recurrent=False, transformer=False):
         """The engine's actor (and critic): MLPs on the task observation.  actor_dims = (D, hidden ..., 3), critic_dims = (D, hidden ..., 1)
         or None; activation "tanh" / "relu" on every hidden layer; the step receives action_gain * a.  Parameters start at zero: fill the
         views of actor_params().  A second call replaces the first.  value_norm (needs a critic): the engine keeps OpenRL's ValueNorm beside
@@ -192,8 +192,13 @@ class HipEngine(EngineBase):
         torch.nn.GRU cell H -> H (H = the last hidden width; every network needs a hidden layer) in front of the output layer of both networks,
         followed by a LayerNorm(H) under layer_norm; the engine carries the state across rollout calls, zeroed here and reset wherever a step ended
         an episode.  rollout, gae and adam_step work on such an actor; ppo_grad and ppo_update take it with chunk_length= (back-propagation through time over
-        chunks of a trajectory recorded with rollout(record_hidden=True)) and refuse it without."""
+        chunks of a trajectory recorded with rollout(record_hidden=True)) and refuse it without.  transformer (abi.ACTOR_TRANSFORMER;
+        csrc/kernels_mat.hpp states the network): MAT, the Multi-Agent Transformer -- actor_dims = (D, E, 3), critic_dims = (D, E, 1) or None for
+        the same; the parameters are mqe.utils.actor_net.MATNet's (abi.mat_param_blocks).  rollout, gae and adam_step work on such an actor;
+        ppo_grad and ppo_update refuse it: the gradient through the attention is not in the engine yet."""
         actor_dims = [int(x) for x in actor_dims]
+        if transformer and critic_dims is None and len(actor_dims) == 3:
+            critic_dims = [actor_dims[0], actor_dims[1], 1]          # the encoder always carries the value head
         critic_dims = [int(x) for x in critic_dims] if critic_dims is not None else []
         for who, dims in (("actor", actor_dims), ("critic", critic_dims)):
             if len(dims) - 1 > abi.ACTOR_MAX_LAYERS:         # mqe_actor_shape has no room for them: never reaches the library
@@ -209,11 +214,12 @@ class HipEngine(EngineBase):
             sh.critic_dims[i] = v
         sh.activation = ((abi.ACTOR_RELU if activation == "relu" else abi.ACTOR_TANH) | (abi.ACTOR_VALUE_NORM if value_norm else 0)
                          | (abi.ACTOR_LAYER_NORM if layer_norm else 0) | (abi.ACTOR_FEATURE_NORM if feature_norm else 0)
-                         | (abi.ACTOR_RECURRENT if recurrent else 0))
+                         | (abi.ACTOR_RECURRENT if recurrent else 0) | (abi.ACTOR_TRANSFORMER if transformer else 0))
         sh.action_gain = float(action_gain)
         self._invoke("actor_create", C.byref(sh))
         self._actor = dict(actor_dims=actor_dims, critic_dims=critic_dims or None, activation=activation, action_gain=float(action_gain),
-                           value_norm=bool(value_norm), layer_norm=bool(layer_norm), feature_norm=bool(feature_norm), recurrent=bool(recurrent))
+                           value_norm=bool(value_norm), layer_norm=bool(layer_norm), feature_norm=bool(feature_norm), recurrent=bool(recurrent),
+                           transformer=bool(transformer))
         self._actor_views = None
         self.ppo_step = 0            # the library dropped Adam's moments with the old actor
 
@@ -229,7 +235,7 @@ class HipEngine(EngineBase):
             flat = self._wrap(v.ptr, [int(v.shape[0])], v.dtype)
             vn = self._actor["value_norm"]
             layout = abi.actor_param_layout(self._actor["actor_dims"], self._actor["critic_dims"], vn, self._actor["layer_norm"], self._actor["feature_norm"],
-                                            self._actor["recurrent"])
+                                            self._actor["recurrent"], self._actor.get("transformer", False))
             views = {n: flat[o:o + int(np.prod(shp))].view(shp) for n, (o, shp) in layout.items()}
             if vn:
                 views["all"] = flat
@@ -252,6 +258,10 @@ class HipEngine(EngineBase):
     def _chunks(self, who, traj, chunk_length):
         """chunk_length of ppo_grad / ppo_update against the actor and the trajectory: -> L (0: a plain actor, samples), or the refusal"""
         rec = self._actor is not None and self._actor["recurrent"]
+        if self._actor is not None and self._actor.get("transformer", False):
+            raise NotImplementedError(f"{who}: the actor is the transformer (create_actor(transformer=True)): the gradient through the attention is not in the "
+                                      f"engine yet; differentiate the torch twin -- MATNet.evaluate(traj.obs, traj.actions) -- and sync_actor() the result, or "
+                                      f"step the engine's buffer with adam_step")
         if chunk_length is None:
             if rec:
                 raise NotImplementedError(f"{who}: the actor is recurrent: its gradient is back-propagation through time over chunks of the trajectory, which "

@@ -171,9 +171,25 @@ class FusedTaskWrapper(EmptyWrapper):
         across rollout() calls and zeroes it wherever a step ended an episode; sync_actor() / pull_actor() copy the cells too.  ppo_update()
         trains such an actor with chunk_length=L: back-propagation through time over chunks of a trajectory of rollout(record_hidden=True),
         inside the engine; without the keyword it refuses it (a learner may still differentiate the torch twins -- RecurrentMLP.evaluate
-        from traj.hidden -- and sync_actor() the result)."""
-        from mqe.utils.actor_net import RecurrentMLP, actor_tensors, mlp_spec, recurrent_spec
+        from traj.hidden -- and sync_actor() the result).  actor_module may instead be ONE mqe.utils.actor_net.MATNet, the Multi-Agent
+        Transformer (OpenRL's --algo mat): the whole policy, with no critic_module (its encoder carries the value head) and no log_std (the
+        module's own Parameter); value_norm= applies, layer_norm= / recurrent= do not.  rollout() evaluates it inside the engine; ppo_update()
+        refuses it -- a learner differentiates MATNet.evaluate(traj.obs, traj.actions) and sync_actor() copies every tensor back."""
+        from mqe.utils.actor_net import MATNet, RecurrentMLP, actor_tensors, mat_spec, mlp_spec, recurrent_spec
         D = self.observation_space.shape[0]
+        if isinstance(actor_module, MATNet):
+            # the Multi-Agent Transformer (OpenRL's --algo mat): one module is the whole policy -- its encoder carries the value head, log_std is its
+            # own Parameter.  rollout() / gae work as for any actor; ppo_update() refuses it: a learner differentiates MATNet.evaluate(traj.obs,
+            # traj.actions) in torch and sync_actor() copies the result back (HipEngine.create_actor(transformer=True))
+            if critic_module is not None or log_std is not None or layer_norm or recurrent:
+                raise ValueError("set_actor(MATNet): the transformer is the whole policy: no separate critic (its encoder carries the value head), no log_std "
+                                 "(it is the module's own Parameter), no layer_norm= / recurrent= (it has its own norms and no state)")
+            _, E = mat_spec(actor_module, D)
+            self._rollout_engine("set_actor").create_actor([D, E, 3], [D, E, 1], activation="tanh", action_gain=action_gain, value_norm=value_norm, transformer=True)
+            self._actor = (actor_tensors("mat", mat=actor_module), actor_module.log_std, True)
+            self._recurrent, self._hidden_next, self._hidden_saved = False, "live", "zeros"
+            self.sync_actor()
+            return
         no_norms = {"feature": None, "hidden": []}
 
         def spec(module, what, out):           # (dims, activation, linears, norms) of a network, whichever of the three forms it comes in

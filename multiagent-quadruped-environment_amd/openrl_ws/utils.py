@@ -49,7 +49,8 @@ class mqe_openrl_wrapper(Wrapper):
         """the policy rollout_torch evaluates inside the engine (FusedTaskWrapper.set_actor) with this adapter's transform: the step
         receives 0.5 * a, clipped to +-1 inside the engine.  value_norm: OpenRL's use_valuenorm, kept by the engine.  layer_norm: the stacks
         may hold the LayerNorm layers of OpenRL's MLP base (use_feature_normalization, and one behind every hidden activation).  recurrent:
-        OpenRL's use_recurrent_policy -- the networks are mqe.utils.actor_net.RecurrentMLP, the engine carries their GRU state"""
+        OpenRL's use_recurrent_policy -- the networks are mqe.utils.actor_net.RecurrentMLP, the engine carries their GRU state.  actor_module may be
+        one mqe.utils.actor_net.MATNet (--algo mat) with no critic_module and no log_std: it is passed through as it is"""
         kw = {"layer_norm": True} if layer_norm else {}
         if recurrent:
             kw["recurrent"] = True

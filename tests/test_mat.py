@@ -1,0 +1,206 @@
+"""The Multi-Agent Transformer policy on a CPU-only host (MQE_ACTOR_TRANSFORMER; csrc/kernels_mat.hpp; abi.actor_param_layout(transformer=True),
+mqe.utils.actor_net.MATNet / mat_spec): act against evaluate, causality, the layout against torch's flattening of the twin, what mat_spec
+refuses, the constant stated alike in header, engine and abi.py, the LDS rule, the kernel's resources, and the wrong variants against the bound
+the GPU test applies."""
+import os
+import re
+import subprocess
+
+import pytest
+import torch
+
+import mat_ref as ref
+from mqe.engine import abi
+from mqe.engine.hip_engine import LIB_PATH
+from mqe.utils.actor_net import MATNet, actor_tensors, mat_spec
+from test_rollout import HEADER, LLVM, TOOLS, ROOT
+
+KERNELS = os.path.join(ROOT, "multiagent-quadruped-environment_amd", "csrc", "kernels_mat.hpp")
+D = 16
+
+
+# ---- 1. act and evaluate ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("A", [1, 2, 4])
+@pytest.mark.parametrize("name", list(ref.SHAPES))
+def test_act_and_evaluate_agree_in_float64(name, A):
+    net = ref.doubles(ref.make_net(D, ref.SHAPES[name], seed=A))
+    obs, z = (t.double() for t in ref.inputs(9, A, D, seed=A))
+    with torch.no_grad():
+        actions, logp, value = net.act(obs, z=z)
+        mean, logp_e, value_e = net.evaluate(obs, actions)
+        det, logp_d, _ = net.act(obs, deterministic=True)
+        mean_d, _, _ = net.evaluate(obs, det)
+    assert actions.shape == (9, A, 3) and logp.shape == value.shape == (9, A)
+    # the autoregressive loop and the parallel pass are the same function: the implied draws are the given ones
+    assert float((actions - (mean + net.sigma().detach() * z)).abs().max()) <= 1e-12
+    assert float((logp - logp_e).abs().max()) <= 1e-12 and float((value - value_e).abs().max()) <= 1e-12
+    assert float((det - mean_d).abs().max()) <= 1e-12, "deterministic: a = mean"
+    want = -torch.log(net.sigma().detach()).sum() - 1.5 * torch.log(torch.tensor(2.0 * torch.pi, dtype=torch.float64))
+    assert float((logp_d - want).abs().max()) <= 1e-12, "deterministic: logp at z = 0"
+    # the written-out network of mat_ref is the module
+    m2, lp2, v2 = ref.wrong_evaluate(net, obs, actions, None)
+    assert float((m2 - mean).abs().max()) <= 1e-12 and float((lp2 - logp_e).abs().max()) <= 1e-12 and float((v2 - value).abs().max()) <= 1e-12
+    # sigma is MAT's 0.5 sigmoid(log_std)
+    assert torch.allclose(net.sigma().detach(), 0.5 / (1.0 + torch.exp(-net.log_std.detach())))
+
+
+# ---- 2. causality ---------------------------------------------------------------------------------------------------------------------------------------
+def test_causality_of_the_decoder_and_the_unmasked_encoder():
+    A = 4
+    net = ref.doubles(ref.make_net(D, 12, seed=2))
+    obs, z = (t.double() for t in ref.inputs(5, A, D, seed=2))
+    with torch.no_grad():
+        actions, _, _ = net.act(obs, z=z)
+        mean, _, value = net.evaluate(obs, actions)
+        for j in range(A - 1):
+            moved = actions.clone()
+            moved[:, j] += 0.7
+            m2, _, v2 = net.evaluate(obs, moved)
+            assert torch.equal(m2[:, :j + 1], mean[:, :j + 1]), f"agent {j}'s action reaches no mean of agents <= {j}"
+            assert float((m2[:, j + 1] - mean[:, j + 1]).abs().min()) > 1e-6, f"agent {j}'s action reaches agent {j + 1}'s mean"
+            assert torch.equal(v2, value)
+        # the last agent's action conditions nothing
+        moved = actions.clone()
+        moved[:, A - 1] += 0.7
+        assert torch.equal(net.evaluate(obs, moved)[0], mean)
+        # the encoder is unmasked: agent 1's observation reaches agent 0's value and mean
+        obs2 = obs.clone()
+        obs2[:, 1, 0] += 0.5              # one feature: a shift of all D would be taken out again by LN_D
+        m3, _, v3 = net.evaluate(obs2, actions)
+        assert float((v3[:, 0] - value[:, 0]).abs().min()) > 1e-6 and float((m3[:, 0] - mean[:, 0]).abs().min()) > 1e-6
+
+
+# ---- 3. layout ------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(ref.SHAPES))
+@pytest.mark.parametrize("vn", [False, True])
+def test_transformer_layout_is_torch_flattening_of_the_twin(name, vn):
+    E, Dd = ref.SHAPES[name], 17
+    net = ref.make_net(Dd, E, seed=3)
+    lay = abi.actor_param_layout([Dd, E, 3], [Dd, E, 1], vn, transformer=True)
+    want = ref.flat_params(net)
+    assert want.numel() == ref.param_count(Dd, E) == 2 * Dd + Dd * E + 18 * E * E + 45 * E + 7
+    assert abi.actor_param_count([Dd, E, 3], [Dd, E, 1], vn, transformer=True) == want.numel() + (abi.VALUE_NORM_STATE if vn else 0)
+    assert abi.actor_param_layout([Dd, E, 3], None, vn, transformer=True) == lay, "the critic's dims are implied"
+    named = [("log_std" if n == "log_std" else "mat." + n, p) for n, p in net.named_parameters()]
+    assert [n for n, _ in named] == [n for n in lay if n != "value_norm"], "the names and the order of MATNet.parameters()"
+    assert [n for n, _ in named][-1] == "log_std" and list(lay)[-1] == ("value_norm" if vn else "log_std")
+    off = 0
+    for n, p in named:
+        o, shape = lay[n]
+        assert o == off and tuple(p.shape) == shape and torch.equal(want[o:o + p.numel()].view(shape), p.detach()), n
+        off += p.numel()
+    if vn:
+        assert lay["value_norm"] == (off, (abi.VALUE_NORM_STATE,))
+    # actor_tensors names every tensor but log_std, which set_actor takes from the module
+    assert [n for n, _ in actor_tensors("mat", mat=net)] == [n for n, _ in named[:-1]]
+    # with an even D every E x E matrix starts on the 16-byte grid the kernel's wide scalar loads need; the two narrow output layers come last
+    lay16 = abi.actor_param_layout([16, E, 3], None, transformer=True)
+    assert all(o % 4 == 0 for n, (o, shape) in lay16.items() if n.endswith(".weight") and len(shape) == 2 and n != "mat.mean_out.weight")
+    assert list(lay16)[-5:] == ["mat.value_out.weight", "mat.value_out.bias", "mat.mean_out.weight", "mat.mean_out.bias", "log_std"]
+    # without the keyword nothing changed
+    assert abi.actor_param_layout([Dd, 8, 3], [Dd, 8, 1]) == abi.actor_param_layout([Dd, 8, 3], [Dd, 8, 1], transformer=False)
+    for bad in (dict(layer_norm=True), dict(feature_norm=True), dict(recurrent=True)):
+        with pytest.raises(ValueError, match="its own norms and no state"):
+            abi.actor_param_layout([Dd, E, 3], None, transformer=True, **bad)
+    with pytest.raises(ValueError, match="the same E"):
+        abi.actor_param_layout([Dd, E, 3], [Dd, E + 4, 1], transformer=True)
+
+
+# ---- 4. mat_spec ----------------------------------------------------------------------------------------------------------------------------------------
+def test_mat_spec_accepts_the_twin_and_refuses_by_layer_name():
+    nn = torch.nn
+    assert mat_spec(ref.make_net(D, 64), D) == (D, 64) and mat_spec(MATNet(7, 4), 7) == (7, 4)
+
+    def refused(change, match, in_dim=D):
+        m = ref.make_net(D, 12)
+        change(m)
+        with pytest.raises(ValueError, match=match):
+            mat_spec(m, in_dim)
+    refused(lambda m: setattr(m.dec, "ln2", nn.LayerNorm(12, eps=1e-6)), r"mat\.dec\.ln2 \(LayerNorm\): eps 1e-06")
+    refused(lambda m: setattr(m.enc, "head_ln", nn.LayerNorm(12, eps=1e-5, elementwise_affine=False)), r"mat\.enc\.head_ln \(LayerNorm\): elementwise_affine=False")
+    refused(lambda m: setattr(m.enc, "ln", nn.LayerNorm(12, eps=1e-5, bias=False)), r"mat\.enc\.ln \(LayerNorm\): elementwise_affine=False \(or no bias\)")
+    refused(lambda m: setattr(m.enc, "ln1", nn.Identity()), r"mat\.enc\.ln1 \(Identity\): expected LayerNorm\(12, eps=1e-5\)")
+    refused(lambda m: setattr(m.dec.attn2, "query", nn.Linear(12, 12, bias=False)), r"mat\.dec\.attn2\.query \(Linear\): Linear without a bias")
+    refused(lambda m: setattr(m.dec, "act_fc", nn.Linear(4, 12)), r"mat\.dec\.act_fc \(Linear\): Linear\(4, 12\) where the network has Linear\(3, 12\)")
+    refused(lambda m: setattr(m.enc, "mlp0", nn.Linear(12, 24)), r"mat\.enc\.mlp0 \(Linear\): Linear\(12, 24\) where the network has Linear\(12, 12\)")
+    refused(lambda m: setattr(m, "mean_out", nn.Linear(12, 2)), r"mat\.mean_out \(Linear\): Linear\(12, 2\)")
+    refused(lambda m: setattr(m.enc, "obs_norm", nn.LayerNorm(8)), r"mat\.enc\.obs_norm \(LayerNorm\): normalized_shape \(8,\) is not \(16,\)")
+    refused(lambda m: None, r"mat\.enc\.obs_norm \(LayerNorm\): normalized_shape \(16,\) is not \(20,\)", in_dim=20)
+    refused(lambda m: setattr(m, "n_head", 2), r"mat\.n_head = 2: the engine's attention has one head")
+    refused(lambda m: setattr(m, "n_block", 2), r"mat\.n_block = 2: the engine evaluates one encoder block")
+    with pytest.raises(ValueError, match="expected a mqe.utils.actor_net.MATNet, got Sequential"):
+        mat_spec(nn.Sequential(nn.Linear(D, 3)), D)
+
+
+# ---- 5. the constant, the LDS rule ----------------------------------------------------------------------------------------------------------------------
+def test_constant_is_stated_alike_in_header_engine_and_abi():
+    header, src = open(HEADER).read(), open(KERNELS).read()
+    stated = [int(v) for v in re.findall(r"\bMQE_ACTOR_TRANSFORMER = (\d+)\b", header)]
+    defined = [int(v) for v in re.findall(r"^#define MQE_ACTOR_TRANSFORMER (\d+)\b", src, re.M)]
+    assert stated == defined == [abi.ACTOR_TRANSFORMER] == [32]
+    assert not re.search(r"^\s*#\s*define\s+MQE_ACTOR_TRANSFORMER", header, re.M), "the header's define set is pinned: it states the value in words"
+    others = abi.ACTOR_TANH | abi.ACTOR_RELU | abi.ACTOR_LAYER_NORM | abi.ACTOR_FEATURE_NORM | abi.ACTOR_RECURRENT | abi.ACTOR_VALUE_NORM | 8 | 512
+    assert abi.ACTOR_TRANSFORMER & others == 0 and abi.ACTOR_TRANSFORMER < 256
+    assert "Multi-agent transformer policy" in header and "not in the engine" in header
+    for stated_once in ("0.5f * x * (1.0f + erff(x * 0.70710678f))", "0.5f * gru_sigmoid(", "logf(sg[j])"):
+        assert stated_once in src, stated_once
+
+
+def test_lds_rule_in_python_is_the_c_function():
+    src = open(KERNELS).read()
+    m = re.search(r"static inline size_t actor_mat_lds_bytes\(int D, int E\) \{ return (.*?); \}", src)
+    assert m, "the LDS rule is one host function"
+    expr = m.group(1).replace("(size_t)", "").replace("sizeof(float)", "4")
+    assert "#define MAT_SLABS 6" in src and "#define MAT_FIXED_ROWS (3 + 4 + 4 + LN_PART)" in src and re.search(r"#define MAT_LDS_LIMIT \(160 \* 1024\)", src)
+    consts = dict(ACT_LD=abi.ACT_LD, MAT_SLABS=abi.MAT_SLABS, MAT_FIXED_ROWS=abi.MAT_FIXED_ROWS)
+    assert abi.MAT_FIXED_ROWS == 43 and abi.MAT_LDS_LIMIT == 160 * 1024
+    for Dd in (1, 16, 127, abi.ACTOR_MAX_OBS):
+        for E in (4, 12, 64, 96, 128, 256):
+            assert abi.actor_mat_lds_bytes(Dd, E) == eval(expr, {}, dict(consts, D=Dd, E=E)) == (Dd + 6 * E + 43) * 260
+        assert abi.actor_mat_lds_bytes(Dd, 64) <= abi.MAT_LDS_LIMIT, "E = 64 is accepted for every D <= 128"
+    assert abi.actor_mat_lds_bytes(16, 92) <= abi.MAT_LDS_LIMIT < abi.actor_mat_lds_bytes(16, 96)
+
+
+# ---- 6. kernel resources --------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.skipif(not (os.path.isfile(LIB_PATH) and all(os.path.isfile(os.path.join(LLVM, t)) for t in TOOLS)),
+                    reason="needs the built HIP engine and the ROCm LLVM tools")
+def test_mat_kernel_uses_no_scratch(tmp_path):
+    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "dev.co")
+    subprocess.check_call([f"{LLVM}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", LIB_PATH, str(tmp_path / "stripped.so")])
+    subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
+    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
+    mine = []
+    for blk in notes.split("- .agpr_count:")[1:]:
+        f = dict(re.findall(r"\.(\w+):\s*(\S+)", ".agpr_count:" + blk))
+        if f.get("name", "").startswith("k_actor_mat"):          # extern "C": the name a kernel trace shows
+            mine.append(f)
+    assert [f["name"] for f in mine] == ["k_actor_mat"]
+    for f in mine:
+        print(f["name"], "vgpr", f["vgpr_count"], "sgpr", f["sgpr_count"], "spills", f["vgpr_spill_count"], f["sgpr_spill_count"], "scratch",
+              f["private_segment_fixed_size"], "static lds", f.get("group_segment_fixed_size", 0))
+        assert int(f["private_segment_fixed_size"]) == 0 and int(f["vgpr_spill_count"]) == 0, f
+        assert int(f["vgpr_count"]) <= 128, "1024 threads per workgroup: 128 registers each"
+        assert int(f.get("group_segment_fixed_size", 0)) == 0, "all LDS is dynamic: the rule above is the whole footprint"
+
+
+# ---- 7. the wrong variants against the GPU test's bound ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(ref.SHAPES))
+def test_wrong_variants_are_far_outside_the_bound(name):
+    """On the inputs, seeds and shapes of tests/test_mat_gpu.py's one-step test (37 envs x 2 agents, D = 16): the float64 wrong variant's deviation
+    from the float64 twin, over 4 x the yardstick (the bound the kernel is held to), is at least 100 for every variant at every shape.  The two
+    variants of the decoder's conditioning cannot be told from the network at A' = 1 (one agent: nothing to mask, nothing to condition on);
+    the shapes here have A' = 2."""
+    E, A = ref.SHAPES[name], 2
+    n32 = ref.make_net(D, E, seed=len(name))
+    n64 = ref.doubles(n32)
+    obs, z = ref.inputs(37, A, D, seed=E)
+    with torch.no_grad():
+        actions, _, _ = n64.act(obs.double(), z=z.double())
+        y = ref.yardstick(n32, n64, obs, actions.float())
+        for variant in ref.VARIANTS:
+            m, lp, v = ref.wrong_evaluate(n64, obs.double(), actions.float().double(), variant)
+            what, dev, yard = ("logp", float((lp - y["logp64"]).abs().max()), y["yard_logp"]) if variant == "exp_sigma" else \
+                              ("mean", float((m - y["mean64"]).abs().max()), y["yard_mean"])
+            ratio = dev / (4 * yard)
+            print(f"mat_wrong {name} {variant}: {what} deviation {dev:.3e} over 4 x yardstick {yard:.3e} = {ratio:.1f}")
+            assert ratio >= 100, (name, variant, ratio)

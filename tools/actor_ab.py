@@ -2,6 +2,10 @@
 T = 200, two 64 x 64 tanh networks.  --kinds: a comma list out of
     plain      k_actor, k_ppo_grad                          norms      both layer norms: k_actor_ln, k_ln_grad
     gru        a GRU cell in both networks: k_actor_gru      gru_norms  the cells and both norms: k_actor_gru_ln
+    mat        the Multi-Agent Transformer at n_embd = --hidden: k_actor_mat (not in the default list: a parent library may not know it).  Its paths:
+               rollout(T) per step, and the same steps with the torch twin around step_torch -- MATNet.act on the device, then
+               mqe_openrl_wrapper.step_torch, no host synchronisation in the loop; it has no gradient inside the engine, so no ppo_update path,
+               and its digest covers the first rollout's actions, logp, value and the advantages of gae
   default     one process, one handle of the same scene per kind, the windows of all of them alternated --rounds times:
               rollout(T) per step, every kind: the physics launches are the same on every handle, so a difference of medians is a difference of the
                   rollout kernels (+ the recorded tails, for "recorded");
@@ -32,7 +36,8 @@ import types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "multiagent-quadruped-environment_amd")]
 
-KINDS = {"plain": (False, False), "norms": (True, False), "gru": (False, True), "gru_norms": (True, True)}      # (both norms, a GRU cell)
+KINDS = {"plain": (False, False), "norms": (True, False), "gru": (False, True), "gru_norms": (True, True), "mat": (False, False)}      # (both norms, a GRU cell)
+MAT_KIND = "mat"     # the transformer: one MATNet instead of the two stacks
 VN_KIND = "gru"      # the handle whose actor also keeps value normalisation (only the flagged calls below read or change it)
 
 
@@ -69,6 +74,24 @@ def measure(a, say):
     for kind in ([a.trace_only] if a.trace_only else a.kinds):
         norms, recurrent = KINDS[kind]
         env = make_mqe_env("go1gate", margs, custom_cfg(margs))[0]
+        if kind == MAT_KIND:
+            from mqe.utils.actor_net import MATNet
+            torch.manual_seed(0)
+            net = MATNet(env.observation_space.shape[0], a.hidden).to(dev)
+            with torch.no_grad():
+                net.log_std.fill_(-0.5)
+            env.set_actor(net)
+            obs = env.reset()
+            eng = env.env.engine
+            traj = eng.gae(eng.rollout(T, time_outs=True), 0.99, 0.95, normalize=True)
+            torch.cuda.synchronize()
+            h = hashlib.sha256()
+            for t in (traj.actions, traj.logp, traj.value, traj.advantages):
+                h.update(t.detach().cpu().contiguous().numpy().tobytes())
+            digest[kind] = h.hexdigest()
+            handles[kind] = (eng, traj, False, env)
+            twin = (net, obs)
+            continue
         actor, critic = networks(env.observation_space.shape[0], a.hidden, norms, recurrent, dev)
         env.set_actor(actor, critic, log_std=torch.full((3,), -0.5, device=dev), **({"layer_norm": True} if norms else {}), **({"recurrent": True} if recurrent else {}),
                       **({"value_norm": True} if kind == VN_KIND else {}))
@@ -107,19 +130,30 @@ def measure(a, say):
         eng, traj, recurrent, _ = handles[a.trace_only]
         for _ in range(2):
             eng.rollout(T, out=traj, **({"record_hidden": True} if recurrent else {}))
-        if not recurrent:
+        if not recurrent and a.trace_only != MAT_KIND:
             grad, stats = torch.empty(eng.actor_params()["flat"].numel(), device=dev), torch.empty(6, device=dev)
             perm = torch.randperm(total, device=dev).to(torch.int32)
             for _ in range(9):
                 eng.ppo_grad(traj, index=perm, first=0, count=total // mb, out=(grad, stats), **kw)
         torch.cuda.synchronize()
-        print(f"trace-only {a.trace_only}: {3 * T} rollout steps" + ("" if recurrent else f" and 10 gradient calls (minibatch of {total // mb} samples)") + " done")
+        print(f"trace-only {a.trace_only}: {3 * T} rollout steps" + ("" if recurrent or a.trace_only == MAT_KIND else f" and 10 gradient calls (minibatch of {total // mb} samples)") + " done")
     else:
         say(f"go1gate {a.envs} envs x 2 agents, T = {T}: {total} samples, {mb} minibatches of {total // mb}, hidden {a.hidden} x {a.hidden} tanh, "
             f"{torch.cuda.get_device_name(0)}, library {os.environ.get('MQE_HIP_LIB', 'in-tree')}, kinds {','.join(a.kinds)}")
         paths = {}
-        for kind, (eng, traj, recurrent, _) in handles.items():
-            if recurrent:
+        for kind, (eng, traj, recurrent, env) in handles.items():
+            if kind == MAT_KIND:
+                from openrl_ws.utils import mqe_openrl_wrapper
+                net, state = twin[0], {"obs": twin[1], "w": mqe_openrl_wrapper(env)}
+
+                def torch_steps(net=net, state=state):
+                    with torch.no_grad():
+                        for _ in range(T):
+                            act, _, _ = net.act(state["obs"])
+                            state["obs"] = state["w"].step_torch(act)[0]
+                paths[f"rollout per step, {kind}"] = (lambda eng=eng, traj=traj: eng.rollout(T, out=traj), 1e3 / T, "us")
+                paths[f"torch twin + step_torch, {kind}"] = (torch_steps, 1e3 / T, "us")
+            elif recurrent:
                 plain = eng.rollout(T)
                 paths[f"rollout per step, {kind}"] = (lambda eng=eng, plain=plain: eng.rollout(T, out=plain), 1e3 / T, "us")
                 paths[f"rollout per step, {kind}, recorded"] = (lambda eng=eng, traj=traj: eng.rollout(T, out=traj, record_hidden=True), 1e3 / T, "us")
@@ -190,7 +224,7 @@ def against_parent(a, say):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kinds", default=",".join(KINDS), type=lambda s: s.split(","))
+    ap.add_argument("--kinds", default=[k for k in KINDS if k != MAT_KIND], type=lambda s: s.split(","))
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--T", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
