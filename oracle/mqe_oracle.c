@@ -783,7 +783,11 @@ static void fill_jac(const mqo_sim* s, const envwork_t* w, int act, int body, co
       real e[3] = {0, 0, 0}; e[k] = 1;
       real r[3] = {p[0] - bk[0].p[0], p[1] - bk[0].p[1], p[2] - bk[0].p[2]};
       real wv[3]; cross3(e, r, wv);
+#if MQO_DEFECT == 8      /* defect build: a two-actor contact's rows without the second actor's angular part */
+      for (int q = 0; q < 3; q++) { J[q][o + k] += sign * dirs[q][k]; if (sign > 0) J[q][o + 3 + k] += sign * dot3(dirs[q], wv); }
+#else
       for (int q = 0; q < 3; q++) { J[q][o + k] += sign * dirs[q][k]; J[q][o + 3 + k] += sign * dot3(dirs[q], wv); }
+#endif
     }
     for (int j = 1; j < NB; j++) {
       if (!is_ancestor_or_self(g_parent, j, body)) continue;
@@ -1420,7 +1424,9 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
       real bias;
       if (TGS) {
         real sep = ct->sd;
+#if MQO_DEFECT != 5      /* defect build (Makefile: defects; tests/test_contact_substep_ref.py): the separation without the motion accumulated so far */
         { real acc = 0; for (int i = 0; i < ndof; i++) acc += ct->J[0][i] * Dacc[i]; sep += acc; }
+#endif
         if (vel_it && sep < 0) sep = 0;
         bias = -sep / sdt;
         if (sep < 0 && bias > d->max_depenetration_velocity) bias = d->max_depenetration_velocity;
@@ -1442,6 +1448,9 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
       if (l1 > lim) l1 = lim; if (l1 < -lim) l1 = -lim;
       dl[1] = l1 - ct->lam[1]; ct->lam[1] = l1;
       u[2] += ct->K[2][1] * dl[1];
+#if MQO_DEFECT == 7      /* defect build: the second tangent row bounded by the first row's impulse instead of mu lambda_n */
+      lim = ct->lam[1] < 0 ? -ct->lam[1] : ct->lam[1];
+#endif
       real l2 = ct->lam[2] - u[2] / ct->K[2][2];
       if (l2 > lim) l2 = lim; if (l2 < -lim) l2 = -lim;
       dl[2] = l2 - ct->lam[2]; ct->lam[2] = l2;
@@ -1532,7 +1541,11 @@ static void simulate_env(mqo_sim* s, int env, envwork_t* w) {
     const real* vo = act < A ? voff + act * RD : voff + A * RD + (act - A) * 6;      /* positions move with v + voff (TGS: the accumulated motion) */
     for (int k = 0; k < 3; k++) { rs[k] = (float)(rs[k] + dt * (v[k] + vo[k])); rs[7 + k] = (float)v[k]; rs[10 + k] = (float)v[3 + k]; }
     if (act >= A && lin_only) { for (int k = 0; k < 3; k++) rs[10 + k] = (float)w->v[A * RD + (act - A) * 6 + 3 + k]; continue; }
+#if MQO_DEFECT == 6      /* defect build: the quaternion integrated with the final velocity alone, voff left out */
+    real q[4] = {rs[3], rs[4], rs[5], rs[6]}, wq[3] = {v[3], v[4], v[5]};
+#else
     real q[4] = {rs[3], rs[4], rs[5], rs[6]}, wq[3] = {v[3] + vo[3], v[4] + vo[4], v[5] + vo[5]};
+#endif
     /* qdot = 0.5 * (w,0) * q */
     real dq[4];
     dq[0] = (real)0.5 * (wq[0] * q[3] + wq[1] * q[2] - wq[2] * q[1]);

@@ -281,13 +281,16 @@ def kept_envs(d, st, dof64):
     return ~(bound_distance(d, st, dof64)[0] <= NEAR).any(axis=1)
 
 
-def good_seeds(e64, grid, count, fused, first=0):
-    """the first `count` seeds from `first` up whose float64 result stays within the exclusion cap -> [(state, float64 result, kept envs)]"""
+def good_seeds(e64, grid, count, fused, first=0, make=None, run=None, kept=None):
+    """the first `count` seeds from `first` up whose float64 result stays within the exclusion cap -> [(state, float64 result, kept envs)].
+    make(e64, grid, seed), run(e64, st, fused) and kept(d, st, float64 dof state) default to this module's free-flight ones
+    (tests/contact_substep_ref.py passes its own: states in contact, a result with the contact forces, the contact list's stability added to the rule)"""
     d, out = e64.desc, []
+    make, run, kept = make or make_state, run or run_substep, kept or kept_envs
     for seed in range(first, first + SEEDS_TRIED):
-        st = make_state(e64, grid, seed)
-        r64 = run_substep(e64, st, fused)
-        keep = kept_envs(d, st, r64[1])
+        st = make(e64, grid, seed)
+        r64 = run(e64, st, fused)
+        keep = kept(d, st, r64[1])
         if (~keep).sum() <= EXCLUDE_CAP * d.num_envs:
             out.append((st, r64, keep))
             if len(out) == count:

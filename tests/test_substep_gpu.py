@@ -23,14 +23,15 @@ def _f64(d, keep):
     return oracle_engine(d, keep, f64=True)
 
 
-def _engines(monkeypatch, capfd, task, N, env, domain):
-    """(HIP engine, float32 oracle, float64 oracle, variant fields) of one descriptor, built under the case's switches"""
+def _engines(monkeypatch, capfd, task, N, env, domain, make=sr.make_engine):
+    """(HIP engine, float32 oracle, float64 oracle, variant fields) of one descriptor, built under the case's switches by make(factory, task, N, domain)
+    (tests/test_contact_substep_gpu.py passes contact_substep_ref.make_engine, whose flag is the randomised friction)"""
     for k, v in dict(env, MQE_VERBOSE="1").items():
         monkeypatch.setenv(k, v)
     capfd.readouterr()
     try:
-        eh = sr.make_engine(hip_engine, task, N, domain)
-        e32, e64 = sr.make_engine(_f32, task, N, domain), sr.make_engine(_f64, task, N, domain)
+        eh = make(hip_engine, task, N, domain)
+        e32, e64 = make(_f32, task, N, domain), make(_f64, task, N, domain)
     finally:
         for k in dict(env, MQE_VERBOSE="1"):
             monkeypatch.delenv(k)
