@@ -702,13 +702,29 @@ int mqe_ppo_adam(mqe_sim* s, const float* grad_dev, long long step, float lr, fl
  *   attn2.*, ln2, mlp0, mlp1, ln3, head0, head_ln), then value_out (E -> 1), mean_out (E -> 3), log_std[3] and the value-normalisation state:
  *   2 D + D E + 18 E^2 + 45 E + 7 trainable floats.  mqe_ppo_optimizer and mqe_ppo_adam cover them like any weight.
  * mqe_rollout, mqe_gae, mqe_rollout_time_outs, mqe_ppo_optimizer and mqe_ppo_adam work unchanged on such a handle; there is no carried state.
- *   mqe_ppo_grad refuses it (-6, nothing enqueued or written): the gradient through the attention is not in the engine; a learner differentiates the
- *   torch twin and steps the buffer with mqe_ppo_adam or copies its parameters back.
+ *   mqe_ppo_grad WITHOUT the bit below refuses such a handle (-6, nothing enqueued or written: "the gradient through the attention is not in the engine
+ *   yet"), as it did before that gradient existed: it is asked for explicitly, like MQE_PPO_BPTT on a recurrent handle.
+ * THE GRADIENT (csrc/kernels_mat_grad.hpp: k_mat_grad, k_mat_reduce; the loss is stated there once).  The constant is not #defined by this header either
+ *   (tests/test_ppo.py pins the MQE_PPO_* define set); it is defined in csrc/kernels_mat_grad.hpp and mirrored in mqe/engine/abi.py (tests/test_mat_grad.py):
+ *   MQE_PPO_TRANSFORMER = 65536
+ *   Bit 16 of mqe_ppo_grad's flags, the first above the chunk-length byte.  With it the minibatch's unit is the env-step GROUP g = t N + n, standing for the
+ *   samples g A' + a -- MQE_PPO_JOINT's unit and numbering, because the attention needs all A' agents of an env-step: index_dev / first / count are group
+ *   numbers in [0, T N) (index values are clamped), M = count A'.  The loss is mqe_ppo_grad's with the Head above: mean and value from one parallel pass over
+ *   the group (s_a = the recorded action of agent a - 1: data), dlogp/dmean_j = z_j / sigma_j, dlogp/dlog_std_j = (z_j^2 - 1)(1 - sigmoid(log_std_j)), H = sum_j
+ *   ln sigma_j + 1.5 (1 + ln(2 pi)), log_std_j receiving -entropy_coef (1 - sigmoid(log_std_j)).  With MQE_PPO_JOINT the ratio is the group's and the policy term
+ *   is divided by G = count; without it the ratio is per sample and every mean is over M.  MQE_PPO_DUAL_CLIP, MQE_PPO_CLIP_VALUE and MQE_PPO_VALUE_NORM[_UPDATE]
+ *   combine as elsewhere.  Every element of grad_dev is written; no floating-point atomics: the same bits on every run.
+ *   -6, nothing enqueued or written: the bit on a handle without MQE_ACTOR_TRANSFORMER (flags); the bit with MQE_PPO_BPTT or a chunk length (flags);
+ *   first + count beyond the T N groups without an index (first / count).
+ *   The first flagged call of an actor allocates (and synchronises once; released with the actor) 256 tapes of the activations the backward needs,
+ *   256 x (2 obs_dim + 40 E + 20) rows x 64 floats (E = 64, obs_dim = 128: 186 MB), and refuses with -5, naming E, a shape whose working set,
+ *   (max(obs_dim, E) + 2 + max(6 E, E + obs_dim) + E + 41) rows of 260 bytes + 528 bytes, exceeds the 160 KiB of a workgroup: E = 64 fits for every
+ *   obs_dim <= 128; at obs_dim = 16 every E <= 72 fits, so E = 76 .. 92, which mqe_actor_create accepts, can act and be updated through the torch twin only.
  * -6 naming the field: the bit with MQE_ACTOR_LAYER_NORM, MQE_ACTOR_FEATURE_NORM or MQE_ACTOR_RECURRENT (activation); the relu kind (activation);
  *   actor_layers / critic_layers other than 2; critic_dims[1] != actor_dims[1] (critic_dims); E < 4 or E % 4 != 0 (actor_dims); an E whose LDS need,
  *   obs_dim + 6 E + 43 rows of 260 bytes, exceeds the 160 KiB of a workgroup (actor_dims; E = 64 fits for every obs_dim <= 128); an A' that does not
  *   divide the 64 rows of a tile (A').  A handle created without the bit launches exactly the kernels it launched before.
- * Not built: the on-device gradient, n_block > 1, n_head > 1, dec_actor, discrete actions. */
+ * Not built: n_block > 1, n_head > 1, dec_actor, discrete actions. */
 
 /* ---- Joint-ratio and dual-clip policy losses in mqe_ppo_grad (csrc/kernels_ppo.hpp: the loss head of the four gradient kernels, k_joint_expand) ----
  * v17, additive: no export, no prototype and no #define of this header changes; mqe_ppo_loss_ex above is the one new typedef.  OpenRL's

@@ -1,7 +1,7 @@
 // kernels_mat.hpp -- the Multi-Agent Transformer policy of an on-device rollout (MQE_ACTOR_TRANSFORMER; include/mqe_hip.h): the network as a
 // program of three operators, its constants, its parameter order and its LDS rule, and the rollout kernel k_actor_mat.  A handle created
-// without the bit never launches it.  The gradient through the attention is not in the engine: mqe_ppo_grad refuses such a handle, and a
-// learner differentiates the torch twin (mqe.utils.actor_net.MATNet.evaluate) and copies the result back.
+// without the bit never launches it.  The gradient through the attention is kernels_mat_grad.hpp's (k_mat_grad), asked for with MQE_PPO_TRANSFORMER;
+// without that flag mqe_ppo_grad refuses such a handle, and a learner differentiates the torch twin (mqe.utils.actor_net.MATNet.evaluate).
 //
 // THE NETWORK is MAT as published (ma_transformer.py, continuous actions) at n_block = 1, n_head = 1, dec_actor = False; E = n_embd, D = the
 // observation width, A' = the agents of an env.  LN = LayerNorm(eps = 1e-5) with weight and bias (kernels_ln.hpp: ln_rows, unchanged);

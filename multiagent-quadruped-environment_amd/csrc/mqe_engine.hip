@@ -27,6 +27,7 @@
 #include "kernels_gru.hpp"
 #include "kernels_actor_critic.hpp"
 #include "kernels_mat.hpp"
+#include "kernels_mat_grad.hpp"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, const char* a = "", const char* b = "", const char* c = "") {      // fmt: up to three %s
@@ -168,6 +169,7 @@ struct mqe_sim {
     // expanded sample list [count L] for the value normalisation; made by the first call that needs them, grown when L (count) grows
     float* hscr = nullptr; size_t hscr_cap = 0;
     int32_t* idx = nullptr; size_t idx_cap = 0;
+    // MQE_PPO_TRANSFORMER (kernels_mat_grad.hpp): hscr holds the workgroups' tapes, mat_grad_scratch_bytes of them, made by the first flagged call; jidx as below
     // MQE_PPO_JOINT (kernels_ppo.hpp): the minibatch's groups expanded to count A' flat sample (chunk) numbers; made by the first such call, grown with count
     int32_t* jidx = nullptr; size_t jidx_cap = 0;
     float* moments = nullptr;
@@ -1877,11 +1879,15 @@ static const struct PpoGradVariant { const void* kern[2]; const char* name; cons
    {{(const void*)k_bptt_grad<64>, (const void*)k_bptt_grad<32>}, "k_bptt_grad",
     "mqe_ppo_grad: flags: MQE_PPO_BPTT: the layer outputs of one network and 7 rows per unit of the wider GRU cell (width %s) do not fit the LDS even at 32 rows"}},
 };
+// the transformer's gradient kernel (kernels_mat_grad.hpp; MQE_PPO_TRANSFORMER): one tile height, its own two rules; behind the four above, which stay in the order they are named
+static const struct { const void* kern; const char* name; } MAT_GRAD_VARIANT = {(const void*)k_mat_grad, "k_mat_grad"};
 // ---- mqe_ppo_grad, stage by stage as mqe_actor_create: the checks in the order of their refusals, the once-per-actor plan, this call's scratch, the
 // launches.  PpoCall: what the flags, the handle and the arguments make of one call; each check fills what it has decided, nothing behind the checks reads
 // `flags`.  The minibatch is a PpoTraj (kernels_ppo.hpp): the caller's selection at first, the joint expansion's list once that is enqueued
 struct PpoCall {
   bool bptt, joint, dual, clip_value, vn, vn_update;
+  bool mat;                       // MQE_PPO_TRANSFORMER: k_mat_grad; the units are groups whether or not the ratio is joint
+  bool grouped() const { return joint || mat; }
   int L, Aw;                      // the chunk length (1 without MQE_PPO_BPTT); the agents of a group
   size_t n_chunks;                // (T / L) R'; without MQE_PPO_BPTT: the samples
   size_t n_units; const char* units;      // what index_dev / first / count number -- the chunks, under MQE_PPO_JOINT the (T / L) N groups -- and their name in a refusal
@@ -1890,7 +1896,12 @@ struct PpoCall {
 };
 // MQE_PPO_BPTT (kernels_bptt.hpp): bits 8 .. 15 hold the chunk length L; index_dev / first / count are chunks
 static int ppo_check_actor(const mqe_sim* s, int flags, PpoCall* c) {
-  if (s->act.mat)
+  c->mat = (flags & MQE_PPO_TRANSFORMER) != 0;
+  if (c->mat && !s->act.mat)
+    return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_TRANSFORMER (65536) needs an actor created with MQE_ACTOR_TRANSFORMER");
+  if (c->mat && (flags & (MQE_PPO_BPTT | (0xff << MQE_PPO_CHUNK_SHIFT))))
+    return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_TRANSFORMER does not combine with MQE_PPO_BPTT or a chunk length in bits 8 .. 15 (the transformer has no state)");
+  if (s->act.mat && !c->mat)
     return fail(-6, "mqe_ppo_grad: the actor was created with MQE_ACTOR_TRANSFORMER: the gradient through the attention is not in the engine yet; differentiate the "
                     "torch twin (mqe.utils.actor_net.MATNet.evaluate on the trajectory) and step with mqe_ppo_adam or copy the parameters back");
   c->bptt = (flags & MQE_PPO_BPTT) != 0; c->L = c->bptt ? (flags >> MQE_PPO_CHUNK_SHIFT) & 0xff : 1;
@@ -1916,8 +1927,8 @@ static int ppo_check_traj(const mqe_sim* s, int T, int flags, PpoTraj* tr, const
   if (c->joint && 32 % c->Aw != 0)
     return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_JOINT: the agents of an env-step share the lanes of one wavefront, so A' must divide 32 (this handle's A' is %s)",
                 std::to_string(c->Aw).c_str());
-  c->n_chunks = c->ts.n / (size_t)c->L; c->n_units = c->joint ? c->n_chunks / (size_t)c->Aw : c->n_chunks;
-  c->units = c->joint ? (c->bptt ? "(T / L) x N chunk groups" : "T x N groups") : (c->bptt ? "(T / L) x R' chunks" : "T x R' samples");
+  c->n_chunks = c->ts.n / (size_t)c->L; c->n_units = c->grouped() ? c->n_chunks / (size_t)c->Aw : c->n_chunks;
+  c->units = c->grouped() ? (c->bptt ? "(T / L) x N chunk groups" : "T x N groups") : (c->bptt ? "(T / L) x R' chunks" : "T x R' samples");
   tr->rows = (int)c->ts.rows; tr->n_total = (long long)c->ts.n;
   return 0;
 }
@@ -1926,8 +1937,8 @@ static int ppo_check_selection(const PpoTraj& tr, PpoCall* c) {
   if (tr.first < 0) return fail(-6, "mqe_ppo_grad: first must not be negative");
   if (tr.first > (1LL << 40) || tr.count > (1LL << 40)) return fail(-6, "mqe_ppo_grad: first / count beyond any trajectory");
   if (!tr.index && tr.first + tr.count > (long long)c->n_units)
-    return fail(-6, "mqe_ppo_grad: first + count exceeds the %s of the trajectory%s", c->units, c->joint ? " (MQE_PPO_JOINT)" : "");
-  c->groups = tr.count * c->L; c->M = c->groups * (c->joint ? c->Aw : 1);
+    return fail(-6, "mqe_ppo_grad: first + count exceeds the %s of the trajectory%s", c->units, c->joint ? " (MQE_PPO_JOINT)" : c->mat ? " (MQE_PPO_TRANSFORMER)" : "");
+  c->groups = tr.count * c->L; c->M = c->groups * (c->grouped() ? c->Aw : 1);
   return 0;
 }
 // the loss's floats (MQE_PPO_DUAL_CLIP, kernels_ppo.hpp: `loss` is an mqe_ppo_loss_ex, read past its first 16 bytes under the bit only), then the rest of the flags
@@ -1945,9 +1956,10 @@ static int ppo_check_loss(const mqe_sim* s, const mqe_ppo_loss* loss, int flags,
     memcpy(rw, lx->reserved, sizeof rw);
     if (rw[0] | rw[1] | rw[2]) return fail(-6, "mqe_ppo_grad: the reserved words of mqe_ppo_loss_ex (MQE_PPO_DUAL_CLIP) must be zero");
   }
-  if (flags & ~(MQE_PPO_BPTT | (0xff << MQE_PPO_CHUNK_SHIFT) | MQE_PPO_JOINT | MQE_PPO_DUAL_CLIP | MQE_PPO_CLIP_VALUE | MQE_PPO_VALUE_NORM | MQE_PPO_VALUE_NORM_UPDATE))
-    return fail(-6, "mqe_ppo_grad: unknown bits in flags (MQE_PPO_CLIP_VALUE, MQE_PPO_VALUE_NORM, MQE_PPO_VALUE_NORM_UPDATE, MQE_PPO_JOINT and MQE_PPO_DUAL_CLIP are "
-                    "the only ones)");
+  if (flags & ~(MQE_PPO_BPTT | (0xff << MQE_PPO_CHUNK_SHIFT) | MQE_PPO_JOINT | MQE_PPO_DUAL_CLIP | MQE_PPO_CLIP_VALUE | MQE_PPO_VALUE_NORM | MQE_PPO_VALUE_NORM_UPDATE |
+                MQE_PPO_TRANSFORMER))
+    return fail(-6, "mqe_ppo_grad: unknown bits in flags (MQE_PPO_CLIP_VALUE, MQE_PPO_VALUE_NORM, MQE_PPO_VALUE_NORM_UPDATE, MQE_PPO_JOINT, MQE_PPO_DUAL_CLIP and "
+                    "MQE_PPO_TRANSFORMER are the only ones)");
   c->clip_value = (flags & MQE_PPO_CLIP_VALUE) != 0; c->vn = (flags & MQE_PPO_VALUE_NORM) != 0; c->vn_update = (flags & MQE_PPO_VALUE_NORM_UPDATE) != 0;
   if (c->vn_update && !c->vn) return fail(-6, "mqe_ppo_grad: flags: MQE_PPO_VALUE_NORM_UPDATE requires MQE_PPO_VALUE_NORM (the update precedes the normalisation it serves)");
   return c->vn ? need_value_norm(s, "mqe_ppo_grad", "MQE_PPO_VALUE_NORM") : 0;
@@ -1964,8 +1976,31 @@ static int ppo_check_ranges(const mqe_sim* s, int T, const PpoTraj& tr, const fl
                                          {c.vn ? a.params + a.n_params : nullptr, MQE_VALUE_NORM_STATE * 4, "the value-normalisation state"}}, 2);
 }
 // once per actor: the row tile its shapes allow, the kernel of that tile and its LDS, the workgroups' partials (hipMalloc synchronises)
+// the transformer's plan (kernels_mat_grad.hpp): the LDS rule against the limit -- every shape mqe_actor_create accepts and the gradient cannot serve is refused
+// here --, the tapes, the partials
+static int mat_grad_plan(mqe_sim* s) {
+  const mqe_sim::Actor& a = s->act; mqe_sim::Ppo& p = s->ppo;
+  const int D = s->D, E = a.sh.actor.dims[1];
+  const size_t lds = mat_grad_lds_bytes(D, E);
+  if (lds > MATG_LDS_LIMIT)
+    return fail(-5, "mqe_ppo_grad: flags: MQE_PPO_TRANSFORMER: the working set of k_mat_grad at E = %s (obs_dim %s) takes %s bytes of LDS, above the 163840 of a workgroup; "
+                    "differentiate the torch twin for this shape", std::to_string(E).c_str(), std::to_string(D).c_str(), std::to_string(lds).c_str());
+  const int tape_rows = matg_tape_rows(MAT_ENC_HOST, MAT_ENC_N, D, E) + matg_tape_rows(MAT_DEC_HOST, MAT_DEC_N, D, E);
+  if ((size_t)PPO_MAX_WG * tape_rows * ACT_ROWS * sizeof(float) != mat_grad_scratch_bytes(D, E))
+    return fail(-100, "mqe_ppo_grad: the transformer's program and the closed count of its tape disagree");
+  p.rt = ACT_ROWS; p.lds = (int)lds; p.lds_rows = tape_rows; p.uw = 0; p.kern = MAT_GRAD_VARIANT.kern;
+  const hipError_t e = hipFuncSetAttribute(p.kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
+  if (p.lds > 48 * 1024 && e != hipSuccess) return fail(-5, "mqe_ppo_grad: cannot reserve LDS for %s", MAT_GRAD_VARIANT.name);
+  if ((!p.hscr && dalloc(s, &p.hscr, mat_grad_scratch_bytes(D, E) / sizeof(float), 0)) || dalloc(s, &p.pst, (size_t)PPO_MAX_WG * PPO_PST) ||
+      dalloc(s, &p.part, (size_t)PPO_MAX_WG * a.n_params, 0)) {
+    p.part = nullptr;
+    return fail(-5, "device alloc failed (mqe_ppo_grad transformer scratch)");
+  }
+  return 0;
+}
 static int ppo_plan(mqe_sim* s) {
   if (s->ppo.part) return 0;
+  if (s->act.mat) return mat_grad_plan(s);
   const mqe_sim::Actor& a = s->act; mqe_sim::Ppo& p = s->ppo;
   const bool ln = a.ln(); const PpoGradVariant& var = PPO_GRAD_VARIANTS[a.gru][!ln];
   const int plain_rows = ppo_lds_rows(a.sh.actor, a.sh.critic, s->D);
@@ -1989,7 +2024,7 @@ static int ppo_scratch(mqe_sim* s, const PpoCall& c) {
   mqe_sim::Ppo& p = s->ppo;
   if (c.vn && (grow_scratch(s, &s->vn.tgt, &s->vn.tgt_cap, c.ts.n) || (!s->vn.part && dalloc(s, &s->vn.part, (size_t)VN_PART))))
     return fail(-5, "device alloc failed (mqe_ppo_grad value-normalisation scratch)");
-  if (c.joint && grow_scratch(s, &p.jidx, &p.jidx_cap, (size_t)(c.M / c.L))) return fail(-5, "device alloc failed (mqe_ppo_grad joint-ratio scratch)");
+  if (c.grouped() && grow_scratch(s, &p.jidx, &p.jidx_cap, (size_t)(c.M / c.L))) return fail(-5, "device alloc failed (mqe_ppo_grad joint-ratio scratch)");
   if (c.bptt && (grow_scratch(s, &p.hscr, &p.hscr_cap, (size_t)PPO_MAX_WG * c.L * s->act.Hm() * p.rt) || (c.vn && grow_scratch(s, &p.idx, &p.idx_cap, (size_t)c.M))))
     return fail(-5, "device alloc failed (mqe_ppo_grad back-propagation-through-time scratch)");
   return 0;
@@ -2030,6 +2065,14 @@ static void launch_grad(mqe_sim* s, const PpoCall& c, PpoTraj tr, const mqe_ppo_
   const int G = capped_grid(tr.count, p.rt, PPO_MAX_WG);
   const float* params = a.params; const ActorShapes* nets = a.nets;
   int log_std_off = a.log_std_off, n_params = a.n_params, D = s->D, relu = a.relu;
+  if (c.mat) {                         // k_mat_grad over the expanded list, then its reduction (MAT's log_std gradient and H)
+    int Aw = c.Aw;
+    void* margs[] = {&params, &nets, &tr, &log_std_off, &n_params, &D, &Aw, &p.lds_rows, &p.part, &p.pst, &ls, &p.hscr};
+    (void)hipLaunchKernel(p.kern, dim3(G), dim3(ACT_THREADS), margs, p.lds, q);
+    hipLaunchKernelGGL(k_mat_reduce, dim3((a.n_params + PPO_REDUCE_THREADS - 1) / PPO_REDUCE_THREADS), dim3(PPO_REDUCE_THREADS), 0, q, (const float*)p.part,
+                       (const double*)p.pst, G, a.n_params, a.log_std_off, c.M, ls.value_coef, ls.entropy_coef, (const float*)a.params, grad_dev, stats_dev);
+    return;
+  }
   void* args[] = {&params, &nets, &tr, &log_std_off, &n_params, &D, &p.lds_rows, &p.uw, &relu, &p.part, &p.pst, &ls, &bt, &p.hscr};
   (void)hipLaunchKernel(p.kern, dim3(G), dim3(ACT_THREADS), args, p.lds, q);      // launched() reports a failure
   hipLaunchKernelGGL(k_ppo_reduce, dim3((a.n_params + PPO_REDUCE_THREADS - 1) / PPO_REDUCE_THREADS), dim3(PPO_REDUCE_THREADS), 0, q, (const float*)p.part,
@@ -2052,7 +2095,7 @@ extern "C" int mqe_ppo_grad(mqe_sim* s, int T, const float* packed_dev, long lon
   if (int rc = ppo_plan(s)) return rc;
   if (int rc = ppo_scratch(s, c)) return rc;
   hipStream_t q = (hipStream_t)stream;
-  if (c.joint) tr = launch_joint_expand(s, c, tr, q);
+  if (c.grouped()) tr = launch_joint_expand(s, c, tr, q);
   if (c.vn) tr.ret = launch_value_norm(s, c, tr, q);
   launch_grad(s, c, tr, loss, grad_dev, stats_dev, q);
   return launched();

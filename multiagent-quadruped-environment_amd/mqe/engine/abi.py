@@ -142,6 +142,10 @@ LN_STAT, BPTT_CELL_ROWS, BPTT_LDS_LIMIT = 8, 7, 160 * 1024      # csrc/kernels_l
 # mqe_actor_shape.activation -- actor_dims = (D, E, 3) and critic_dims = (D, E, 1) then describe MAT's encoder and decoder --, and what its LDS rule is made of
 ACTOR_TRANSFORMER = 32
 MAT_SLABS, MAT_FIXED_ROWS, MAT_LDS_LIMIT = 6, 3 + 4 + 4 + LN_PART, 160 * 1024
+# the transformer's on-device gradient (include/mqe_hip.h states the value, csrc/kernels_mat_grad.hpp defines it): mqe_ppo_grad flags bit 16, the first above
+# the chunk-length byte -- index / first / count number the env-step groups --, and what the two rules below are made of
+PPO_TRANSFORMER = 65536
+PPO_MAX_WG, MATG_FIXED_ROWS, MATG_HEAD_BYTES, MATG_LDS_LIMIT = 256, 2 + 3 + 4 + LN_PART, 64 * 8 + 16, 160 * 1024
 RNG_ACTOR = 0x70000000          # csrc/mqe_common.hpp MQE_RNG_ACTOR: `count` of the actor's draws = RNG_ACTOR + post-physics steps so far
 
 
@@ -198,6 +202,20 @@ def actor_mat_lds_bytes(obs_dim, n_embd):
     """LDS of k_actor_mat (csrc/kernels_mat.hpp actor_mat_lds_bytes): the observation's D rows, MAT_SLABS slabs of E rows, the rows of s, the
     outputs, the kept results and the norm's partials, in rows of 65 floats.  mqe_actor_create refuses above MAT_LDS_LIMIT."""
     return (int(obs_dim) + MAT_SLABS * int(n_embd) + MAT_FIXED_ROWS) * ACT_LD * 4
+
+
+def mat_grad_lds_bytes(obs_dim, n_embd):
+    """LDS of k_mat_grad (csrc/kernels_mat_grad.hpp mat_grad_lds_bytes, LDS RULE): max(D, E) + 2 rows of popped inputs, max(6 E, E + D) rows of slabs and
+    their gradients, E rows of a dx to be added, the fixed rows, in rows of 65 floats, behind the tile's sample numbers.  The first
+    ppo_grad(transformer=True) refuses above MATG_LDS_LIMIT (-5, naming E)."""
+    D, E = int(obs_dim), int(n_embd)
+    return (max(D, E) + 2 + max(MAT_SLABS * E, E + D) + E + MATG_FIXED_ROWS) * ACT_LD * 4 + MATG_HEAD_BYTES
+
+
+def mat_grad_scratch_bytes(obs_dim, n_embd):
+    """the workgroups' tapes (csrc/kernels_mat_grad.hpp mat_grad_scratch_bytes, THE TAPE): PPO_MAX_WG x (2 D + 40 E + 20) rows of 64 floats, allocated by
+    the first ppo_grad(transformer=True) of an actor and released with it"""
+    return PPO_MAX_WG * (2 * int(obs_dim) + 40 * int(n_embd) + 20) * 64 * 4
 
 
 def mat_param_blocks(obs_dim, n_embd):

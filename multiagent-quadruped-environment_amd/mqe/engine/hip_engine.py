@@ -255,10 +255,18 @@ class HipEngine(EngineBase):
             return 0
         return a["actor_dims"][-2] + (a["critic_dims"][-2] if a["critic_dims"] else 0)
 
-    def _chunks(self, who, traj, chunk_length):
-        """chunk_length of ppo_grad / ppo_update against the actor and the trajectory: -> L (0: a plain actor, samples), or the refusal"""
+    def _chunks(self, who, traj, chunk_length, transformer=False):
+        """chunk_length of ppo_grad / ppo_update against the actor and the trajectory: -> L (0: a plain actor, samples), or the refusal.
+        transformer: the caller asked for the transformer's on-device gradient (abi.PPO_TRANSFORMER)"""
         rec = self._actor is not None and self._actor["recurrent"]
-        if self._actor is not None and self._actor.get("transformer", False):
+        mat = self._actor is not None and self._actor.get("transformer", False)
+        if transformer:
+            if not mat:
+                raise ValueError(f"{who}: transformer=True needs the transformer actor (create_actor(transformer=True)); this actor's gradient needs no such switch")
+            if chunk_length is not None:
+                raise ValueError(f"{who}: transformer=True does not combine with chunk_length= (the transformer carries no state)")
+            return 0
+        if mat:
             raise NotImplementedError(f"{who}: the actor is the transformer (create_actor(transformer=True)): the gradient through the attention is not in the "
                                       f"engine yet; differentiate the torch twin -- MATNet.evaluate(traj.obs, traj.actions) -- and sync_actor() the result, or "
                                       f"step the engine's buffer with adam_step")
@@ -387,12 +395,13 @@ class HipEngine(EngineBase):
 
     # ---- the PPO update on the engine's own parameters (mqe_ppo_grad / mqe_ppo_optimizer / mqe_ppo_adam; csrc/kernels_ppo.hpp) ---------------
     def _ppo_units(self, T, L, joint):
-        """(how many, their noun): the units a minibatch of this trajectory is made of -- what index / first / count number (csrc/kernels_ppo.hpp)"""
+        """(how many, their noun): the units a minibatch of this trajectory is made of -- what index / first / count number (csrc/kernels_ppo.hpp).
+        joint: the units are groups (the joint ratio, or the transformer's gradient)"""
         N, Aw, _ = (int(x) for x in self.tensor(abi.T_WRAPPER_OBS).shape)
         return T * N * (1 if joint else Aw) // max(L, 1), ("chunk groups" if L else "groups") if joint else ("chunks" if L else "samples")
 
     def ppo_grad(self, traj, index=None, first=0, count=None, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=None, out=None, value_norm=None,
-                 update_value_norm=False, chunk_length=None, joint=False, dual_clip=None):
+                 update_value_norm=False, chunk_length=None, joint=False, dual_clip=None, transformer=False):
         """Gradient of rsl_rl's clipped-surrogate PPO loss over one minibatch of a Rollout that HipEngine.gae has filled, with respect to the
         engine's actor-critic parameters (mqe_ppo_grad; csrc/kernels_ppo.hpp states the loss): two launches, no synchronisation (the first
         call after create_actor allocates its scratch and synchronises once), the same bits on every run.  The minibatch is
@@ -413,9 +422,14 @@ class HipEngine(EngineBase):
         mean -- per env-step; index / first / count are then GROUP numbers t * N + env (with chunk_length: chunk groups (t0 / L) * N + env), each
         standing for the A' samples (chunks) of that env-step, and the policy term averages over the groups; one more small launch.
         dual_clip=c_d (abi.PPO_DUAL_CLIP; OpenRL's dual_clip_ppo / dual_clip_coeff; None: off): where the advantage is negative the surrogate is
-        additionally bounded by c_d * adv; c_d > 1 + clip.  csrc/kernels_ppo.hpp states both."""
+        additionally bounded by c_d * adv; c_d > 1 + clip.  csrc/kernels_ppo.hpp states both.
+        transformer=True (the transformer actor, which is refused without it; abi.PPO_TRANSFORMER, csrc/kernels_mat_grad.hpp: k_mat_grad): the gradient
+        through MAT's encoder, decoder and attention on the device.  index / first / count are GROUP numbers t * N + env whether or not joint is set (the
+        attention needs all A' agents of an env-step); the loss is the one above with sigma = 0.5 sigmoid(log_std); joint, dual_clip, value_clip and the
+        value normalisation combine with it.  The first such call allocates the activation tapes (abi.mat_grad_scratch_bytes) and synchronises once; a
+        width whose working set does not fit the LDS (abi.mat_grad_lds_bytes) is refused there."""
         self._need_actor()
-        L = self._chunks("ppo_grad", traj, chunk_length)
+        L = self._chunks("ppo_grad", traj, chunk_length, transformer)
         vn = self._value_norm("ppo_grad", value_norm)
         if update_value_norm and not vn:
             raise ValueError("ppo_grad: update_value_norm=True needs value normalisation (an actor created with value_norm=True)")
@@ -431,7 +445,7 @@ class HipEngine(EngineBase):
             _need_f32(f"traj.{name}", getattr(traj, name), shp)
         _need_packed(traj)
         n_params = self.actor_params()["flat"].numel()
-        total, what = self._ppo_units(T, L, joint)
+        total, what = self._ppo_units(T, L, joint or transformer)
         if index is not None:
             if not (index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.dim() == 1):
                 raise ValueError("index must be a contiguous one-dimensional int32 device tensor")
@@ -452,7 +466,7 @@ class HipEngine(EngineBase):
                      _ptr(traj.advantages), _ptr(traj.returns), _ptr(index), first, count, C.cast(C.pointer(loss), C.POINTER(abi.PpoLoss)),
                      (abi.PPO_CLIP_VALUE if value_clip is not None else 0) | (abi.PPO_VALUE_NORM if vn else 0) |
                      (abi.PPO_VALUE_NORM_UPDATE if update_value_norm else 0) | ((abi.PPO_BPTT | L << abi.PPO_CHUNK_SHIFT) if L else 0) |
-                     (abi.PPO_JOINT if joint else 0) | (abi.PPO_DUAL_CLIP if dual_clip is not None else 0),
+                     (abi.PPO_JOINT if joint else 0) | (abi.PPO_DUAL_CLIP if dual_clip is not None else 0) | (abi.PPO_TRANSFORMER if transformer else 0),
                      _ptr(grad), _ptr(stats), self._stream())
         return grad, stats
 
@@ -478,7 +492,7 @@ class HipEngine(EngineBase):
                      float(max_grad_norm) if max_grad_norm is not None else 0.0, _ptr(norm_out), self._stream())
 
     def ppo_update(self, traj, epochs, minibatches, lr, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=None, betas=(0.9, 0.999), eps=1e-8,
-                   max_grad_norm=None, generator=None, value_norm=None, chunk_length=None, joint=False, dual_clip=None):
+                   max_grad_norm=None, generator=None, value_norm=None, chunk_length=None, joint=False, dual_clip=None, transformer=False):
         """The PPO update of one trajectory inside the engine: per epoch one device permutation of the T x N x A' samples
         (torch.randperm(..., device=..., generator=generator)), cut into `minibatches` equal slices (the last takes the remainder), and per
         slice ppo_grad + adam_step -- 2 to 4 launches, no synchronisation, no copy.  The step count lives on this object (ppo_step) and carries
@@ -488,12 +502,14 @@ class HipEngine(EngineBase):
         chunk_length=L (a recurrent actor, refused without it; ppo_grad's): what is permuted and cut into minibatches are the (T / L) * N * A'
         chunks, and `minibatches` is bounded by their number; one launch more a slice under value normalisation.
         joint, dual_clip: ppo_grad's (OpenRL's use_joint_action_loss; dual_clip_ppo with dual_clip_coeff).  With joint what is permuted and cut are
-        the T * N groups (the (T / L) * N chunk groups), `minibatches` is bounded by their number, and a slice costs one launch more."""
+        the T * N groups (the (T / L) * N chunk groups), `minibatches` is bounded by their number, and a slice costs one launch more.
+        transformer=True (the transformer actor, refused without it; ppo_grad's): the update through k_mat_grad -- rollout, gae and this call, and the
+        parameters never leave the buffer the actor reads.  What is permuted and cut are the T * N groups, and `minibatches` is bounded by their number."""
         self._need_actor()
-        L = self._chunks("ppo_update", traj, chunk_length)
+        L = self._chunks("ppo_update", traj, chunk_length, transformer)
         vn = self._value_norm("ppo_update", value_norm)
         epochs, minibatches = int(epochs), int(minibatches)
-        total, what = self._ppo_units(int(traj.T), L, joint)
+        total, what = self._ppo_units(int(traj.T), L, joint or transformer)
         if epochs < 1 or minibatches < 1 or minibatches > total:
             raise ValueError(f"ppo_update: epochs >= 1 and 1 <= minibatches <= {total} {what}")
         dev = self.torch_device
@@ -507,7 +523,7 @@ class HipEngine(EngineBase):
                 count = per if b + 1 < minibatches else total - first
                 self.ppo_grad(traj, index=perm, first=first, count=count, clip=clip, value_coef=value_coef, entropy_coef=entropy_coef,
                               value_clip=value_clip, out=(grad, stats[e, b]), value_norm=vn, update_value_norm=vn, chunk_length=chunk_length, joint=joint,
-                              dual_clip=dual_clip)
+                              dual_clip=dual_clip, transformer=transformer)
                 self.ppo_step += 1
                 self.adam_step(grad, self.ppo_step, lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm)
         return stats

@@ -173,14 +173,16 @@ class FusedTaskWrapper(EmptyWrapper):
         inside the engine; without the keyword it refuses it (a learner may still differentiate the torch twins -- RecurrentMLP.evaluate
         from traj.hidden -- and sync_actor() the result).  actor_module may instead be ONE mqe.utils.actor_net.MATNet, the Multi-Agent
         Transformer (OpenRL's --algo mat): the whole policy, with no critic_module (its encoder carries the value head) and no log_std (the
-        module's own Parameter); value_norm= applies, layer_norm= / recurrent= do not.  rollout() evaluates it inside the engine; ppo_update()
-        refuses it -- a learner differentiates MATNet.evaluate(traj.obs, traj.actions) and sync_actor() copies every tensor back."""
+        module's own Parameter); value_norm= applies, layer_norm= / recurrent= do not.  rollout() evaluates it inside the engine; ppo_update(...,
+        transformer=True) updates it inside the engine too, and without the keyword refuses it (a learner may still differentiate
+        MATNet.evaluate(traj.obs, traj.actions) in torch and sync_actor() every tensor back)."""
         from mqe.utils.actor_net import MATNet, RecurrentMLP, actor_tensors, mat_spec, mlp_spec, recurrent_spec
         D = self.observation_space.shape[0]
         if isinstance(actor_module, MATNet):
             # the Multi-Agent Transformer (OpenRL's --algo mat): one module is the whole policy -- its encoder carries the value head, log_std is its
-            # own Parameter.  rollout() / gae work as for any actor; ppo_update() refuses it: a learner differentiates MATNet.evaluate(traj.obs,
-            # traj.actions) in torch and sync_actor() copies the result back (HipEngine.create_actor(transformer=True))
+            # own Parameter.  rollout() / gae work as for any actor; ppo_update(transformer=True) runs the engine's own backward; without the keyword it
+            # refuses, and a learner differentiates MATNet.evaluate(traj.obs, traj.actions) in torch and sync_actor() copies the result back
+            # (HipEngine.create_actor(transformer=True))
             if critic_module is not None or log_std is not None or layer_norm or recurrent:
                 raise ValueError("set_actor(MATNet): the transformer is the whole policy: no separate critic (its encoder carries the value head), no log_std "
                                  "(it is the module's own Parameter), no layer_norm= / recurrent= (it has its own norms and no state)")
@@ -271,7 +273,9 @@ class FusedTaskWrapper(EmptyWrapper):
         the trajectory (rollout(record_hidden=True), T a multiple of L) is cut into chunks of L steps per row, the minibatches are sets of chunks
         and the gradient runs through the GRU cells over each chunk's steps (OpenRL's data_chunk_length; HipEngine.ppo_grad states the rule).
         joint=True is OpenRL's use_joint_action_loss (jrpo.yaml): one ratio and one advantage per env-step, the minibatches are sets of env-steps;
-        dual_clip=c_d is dual_clip_ppo with dual_clip_coeff = c_d (dppo.yaml)."""
+        dual_clip=c_d is dual_clip_ppo with dual_clip_coeff = c_d (dppo.yaml).  After set_actor(MATNet): transformer=True is required -- the update
+        runs through the engine's own backward of the transformer (HipEngine.ppo_grad states it), the minibatches are sets of env-steps, and
+        pull_actor() brings the result back into the module; without the keyword the call is refused as before and the learner stays in torch."""
         eng = self._rollout_engine("ppo_update")
         if getattr(self, "_actor", None) is None:
             raise RuntimeError("ppo_update: no actor (set_actor first)")

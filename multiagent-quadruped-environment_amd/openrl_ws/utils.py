@@ -71,7 +71,7 @@ class mqe_openrl_wrapper(Wrapper):
         into the torch modules.  A recurrent actor needs chunk_length=L (OpenRL's data_chunk_length) and a trajectory of
         rollout_torch(record_hidden=True) whose T is a multiple of L: back-propagation through time runs inside the engine.  Beside use_valuenorm (set_actor) the loss switches of
         OpenRL's configs are keywords here: joint=True is use_joint_action_loss (jrpo.yaml), dual_clip=c_d is dual_clip_ppo with dual_clip_coeff = c_d
-        (dppo.yaml)"""
+        (dppo.yaml); transformer=True (--algo mat, after set_actor(MATNet)) runs the update through the engine's backward of the transformer"""
         return self.env.ppo_update(traj, **kw)
 
     def step_dlpack(self, actions):

@@ -1,0 +1,215 @@
+"""The transformer's on-device PPO gradient on a CPU-only host (MQE_PPO_TRANSFORMER; csrc/kernels_mat_grad.hpp; tests/mat_grad_ref.py): the manual
+backward written from the kernel file's formulas against float64 autograd, the K cases, the constant stated alike in header, kernel file and abi.py,
+the LDS and scratch rules against the C functions, the generator's condition at every shape the GPU test uses, the kernel's resources, and the wrong
+variants against the bound the GPU test applies.
+
+WRONG VARIANTS, measured (the smallest factor, over the shapes below, by which a variant's worst tensor exceeds 2 K_MAT_GPU 2^-24 S_n):
+65 groups of mat_grad_ref.k_case(seed 1), joint + dual clip + value clip; per variant the weakest case of E in {64, 12, 4} x A' in {1, 2, 4}:
+    no_r 915 (e4, A' = 4)   mask_ignored 176 (e4, A' = 4)   no_scale 222 (e4, A' = 4)   no_res_rep 173 (e4, A' = 4)   no_query_rep 45 (e4, A' = 4)
+    enc_value_only 178 (e4, A' = 4)   no_one_minus_sigmoid 35 (e4, A' = 4)   tanh_gelu 2.31 (e64, A' = 4; 6.05 at e12)
+At E = 4 the tanh_gelu variant has inputs of its own (mat_grad_ref.TANH_GELU_AT_E4: a few groups, where S_n holds little cancellation and the
+derivative's relative error -- some 3 % near x = -3 -- shows; with 65 groups it reads 0.30 .. 0.38 and would fall inside): 3.14 at A' = 1 (4 groups, seed
+0), 9.0 at A' = 2 (1 group, seed 3), 2.15 at A' = 4 (8 groups, seed 0).  The weakest of all is tanh_gelu at E = 4, A' = 4: 2.15 times the doubled bound.
+
+WHAT THE WIDTHS PROTECT.  The bound is per width (mat_grad_ref: K_MAT_CPU_OF, never above the one constant K_MAT_CPU).  At E = 4 the GPU's bound is
+20 796 x 2^-24 = 1.2e-3 of S_n, about 200 times what the kernel shows there (65 .. 112), so the E = 4 cases catch gross errors and little else; the
+per-tensor protection comes from E = 12 (bound 468, kernel 53 .. 322) and E = 64 (bound 984, kernel 36 .. 184)."""
+import os
+import re
+import subprocess
+
+import pytest
+import torch
+
+import mat_grad_ref as ref
+import mat_ref
+from mqe.engine import abi
+from mqe.engine.hip_engine import LIB_PATH
+from test_rollout import HEADER, LLVM, TOOLS, ROOT
+
+KERNELS = os.path.join(ROOT, "multiagent-quadruped-environment_amd", "csrc", "kernels_mat_grad.hpp")
+EPS32 = ref.EPS32
+CFGS = {k: dict(ref.CFG, **v) for k, v in ref.LOSSES.items()}
+
+
+# ---- 1. the manual backward is float64 autograd ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("A", [1, 2, 4])
+@pytest.mark.parametrize("name", list(mat_ref.SHAPES))
+def test_manual_backward_agrees_with_float64_autograd(name, A):
+    """the worst entry of every gradient tensor within 1e-9 of that tensor's largest magnitude: this holds the formulas the kernel file states"""
+    import warnings
+    warnings.filterwarnings("ignore", message="Full backward hook is firing")
+    for loss, cfg in CFGS.items():
+        net, b = ref.k_case(name, A, 65, 0)
+        n64 = mat_ref.doubles(net)
+        g64, st64, S, _ = ref.reference(net, b, cfg)
+        gm, stm = ref.manual(n64, b, cfg)
+        # an attention's key bias has NO gradient: it shifts every score of a row alike and the softmax cancels it.  What both backward passes leave there is
+        # the rounding of contributions of size S_n that cancel, so that tensor's magnitude is S_n
+        top_of = lambda n: S[n] if n.endswith(".key.bias") else float(g64[n].abs().max())
+        for n in g64:
+            assert float((gm[n] - g64[n]).abs().max()) <= 1e-9 * top_of(n), (name, A, loss, n)
+        assert float((stm - st64).abs().max()) <= 1e-12 * float(st64.abs().max())
+        # and the tiled accumulation is the same float64 gradient
+        gt, stt = ref.autograd(net, b, cfg, torch.float64, tile=64)
+        for n in g64:
+            assert float((gt[n] - g64[n]).abs().max()) <= 1e-9 * top_of(n), (name, A, loss, n)
+        assert float((stt - st64).abs().max()) <= 1e-12 * float(st64.abs().max())
+
+
+# ---- 2. K ---------------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("A", [1, 2, 4])
+@pytest.mark.parametrize("name", list(mat_ref.SHAPES))
+def test_float32_evaluations_stay_inside_k_cpu(name, A):
+    worst, k = 0.0, ref.K_MAT_CPU_OF[mat_ref.SHAPES[name]]
+    assert k <= ref.K_MAT_CPU == 5199.0
+    for (nm, Aw, count, loss, seed) in ref.K_CASES:
+        if (nm, Aw) != (name, A):
+            continue
+        cfg = CFGS[loss]
+        net, b = ref.k_case(name, A, count, seed)
+        g64, st64, S, ss = ref.reference(net, b, cfg)
+        for how, tile in (("whole", None), ("tiled", 64)):
+            g32, st32 = ref.autograd(net, b, cfg, torch.float32, tile=tile)
+            r, at = ref.ratio_to_bound(g32, g64, S)
+            rs = ppo_stats_ratio(st32, st64, ss)
+            print(f"mat_grad_k {name} A'={A} count={count} {loss} seed={seed} {how}: gradient {r:.2f} ({at}) statistics {rs:.2f}")
+            worst = max(worst, r, rs)
+            assert r <= k and rs <= k, (name, A, count, loss, seed, how, r, at, rs)
+    print(f"mat_grad_k {name} A'={A}: worst {worst:.2f} of K_MAT_CPU_OF = {k:.0f}")
+
+
+def ppo_stats_ratio(st, st64, scales):
+    return float(((st.double() - st64).abs() / (EPS32 * scales)).max())
+
+
+# ---- 3. the constant, the two rules ---------------------------------------------------------------------------------------------------------------------------
+def test_constant_is_stated_alike_in_header_kernel_file_and_abi():
+    header, src = open(HEADER).read(), open(KERNELS).read()
+    stated = [int(v) for v in re.findall(r"\bMQE_PPO_TRANSFORMER = (\d+)\b", header)]
+    defined = [int(v) for v in re.findall(r"^#define MQE_PPO_TRANSFORMER (\d+)\b", src, re.M)]
+    assert stated == defined == [abi.PPO_TRANSFORMER] == [65536] == [1 << 16]
+    assert not re.search(r"^\s*#\s*define\s+MQE_PPO_TRANSFORMER", header, re.M), "the header's define set is pinned: it states the value in words"
+    others = (abi.PPO_CLIP_VALUE | abi.PPO_VALUE_NORM | abi.PPO_VALUE_NORM_UPDATE | abi.PPO_BPTT | abi.PPO_JOINT | abi.PPO_DUAL_CLIP | 2 | 4 |
+              0xff << abi.PPO_CHUNK_SHIFT)
+    assert abi.PPO_TRANSFORMER & others == 0, "the first bit above the chunk-length byte; 2 and 4 stay unknown"
+    assert "not in the engine" in header and "Not built: n_block" in header
+    for stated_once in ("0.5f * (1.0f + erff(x * 0.70710678f)) + x * expf(-0.5f * x * x) * 0.3989422804f", "logf(0.5f * gru_sigmoid("):
+        assert stated_once in src, stated_once
+    assert 'extern "C" __global__ void __launch_bounds__(ACT_THREADS) k_mat_grad(' in src
+
+
+def test_lds_and_scratch_rules_in_python_are_the_c_functions():
+    src = open(KERNELS).read()
+    lds = re.search(r"static inline size_t mat_grad_lds_bytes\(int D, int E\) \{ return (.*?); \}", src)
+    scr = re.search(r"static inline size_t mat_grad_scratch_bytes\(int D, int E\) \{ return (.*?); \}", src)
+    assert lds and scr, "each rule is one host function"
+    clean = lambda e: e.replace("(size_t)", "").replace("sizeof(float)", "4")
+    assert "#define MATG_FIXED_ROWS (2 + 3 + 4 + LN_PART)" in src and "#define MATG_HEAD_BYTES (64 * 8 + 16)" in src
+    assert re.search(r"#define MATG_LDS_LIMIT \(160 \* 1024\)", src) and "#define MATG_MAX(a, b) ((a) > (b) ? (a) : (b))" in src
+    assert "#define PPO_MAX_WG 256" in open(os.path.join(os.path.dirname(KERNELS), "kernels_ppo.hpp")).read()
+    consts = dict(ACT_LD=abi.ACT_LD, ACT_ROWS=64, MAT_SLABS=abi.MAT_SLABS, MATG_FIXED_ROWS=abi.MATG_FIXED_ROWS, MATG_HEAD_BYTES=abi.MATG_HEAD_BYTES,
+                  PPO_MAX_WG=abi.PPO_MAX_WG, MATG_MAX=max)
+    assert abi.MATG_FIXED_ROWS == 41 and abi.MATG_LDS_LIMIT == 160 * 1024
+    for Dd in (1, 13, 16, 127, abi.ACTOR_MAX_OBS):
+        for E in (4, 12, 64, 72, 76, 92):
+            env = dict(consts, D=Dd, E=E)
+            assert abi.mat_grad_lds_bytes(Dd, E) == eval(clean(lds.group(1)), {}, env) == (max(Dd, E) + 2 + max(6 * E, E + Dd) + E + 41) * 260 + 528
+            assert abi.mat_grad_scratch_bytes(Dd, E) == eval(clean(scr.group(1)), {}, env) == 256 * (2 * Dd + 40 * E + 20) * 256
+        for A in (1, 2, 4):
+            assert abi.mat_grad_lds_bytes(Dd, 64) <= abi.MATG_LDS_LIMIT, "E = 64 fits for every D <= 128 (the rule does not depend on A')"
+    assert abi.mat_grad_lds_bytes(16, 72) <= abi.MATG_LDS_LIMIT < abi.mat_grad_lds_bytes(16, 76)
+    assert abi.actor_mat_lds_bytes(16, 92) <= abi.MAT_LDS_LIMIT, "accepted by mqe_actor_create, refused by the first flagged mqe_ppo_grad"
+
+
+def test_the_closed_tape_count_is_the_walk_of_the_program():
+    """2 D + 40 E + 20 rows: the pushes of csrc/kernels_mat_grad.hpp's THE TAPE, counted over the operator lists of csrc/kernels_mat.hpp"""
+    src = open(os.path.join(os.path.dirname(KERNELS), "kernels_mat.hpp")).read()
+    progs = {}
+    for which in ("ENC", "DEC"):
+        body = src.split(f"#define MAT_{which}_OPS {{")[1].split("}}")[0]
+        progs[which] = [[f.strip() for f in op.split(",")] for op in re.findall(r"\{(MAT_\w+,[^{}]*)", body)]
+    assert len(progs["ENC"]) == 15 and len(progs["DEC"]) == 20
+    for Dd, E in ((16, 12), (128, 64), (13, 4)):
+        width = lambda c: {"MAT_WD": Dd, "MAT_WE": E, "MAT_W3": 3, "MAT_W1": 1}[c]
+        rows = 0
+        for prog in progs.values():
+            for i, op in enumerate(prog):
+                kind, src_slot, _, kin, nout, post = op[:6]
+                if kind == "MAT_LN":
+                    rows += width(kin) + 2
+                elif kind == "MAT_ATT":
+                    rows += 3 * E
+                else:
+                    nxt = prog[i + 1] if i + 1 < len(prog) else None
+                    keeps = src_slot != "MAT_S" and not (nxt and nxt[0] == "MAT_LIN" and nxt[1] == src_slot)
+                    rows += (width(kin) if keeps else 0) + (width(nout) if post == "MAT_GELU" else 0)
+        assert rows == 2 * Dd + 40 * E + 20
+        assert abi.mat_grad_scratch_bytes(Dd, E) == abi.PPO_MAX_WG * rows * 64 * 4
+
+
+# ---- 4. the generator's condition at the GPU test's shapes ----------------------------------------------------------------------------------------------------
+def test_redrawn_groups_stay_below_fifteen_percent_at_every_gpu_shape():
+    for what, (shape, widths) in ref.GPU_SHAPES.items():
+        for E in widths:
+            s = ref.gpu_synth(what, E)
+            print(f"mat_grad_synth {what} E={E} shape={shape}: {100 * s['redrawn']:.1f} % of the groups drawn again")
+            assert s["redrawn"] < 0.15
+            n64 = mat_ref.doubles(s["net"])
+            assert not bool(ref.group_kinks(n64, s["groups"]).any())
+            # ratios on both sides of the clip range, both signs of the advantage, the value clip active and not
+            with torch.no_grad():
+                _, logp, v = n64.evaluate(s["groups"]["obs"].double(), s["groups"]["actions"].double())
+            ratio = torch.exp(logp - s["groups"]["logp_old"].double())
+            assert bool((ratio > 1 + ref.CLIP).any()) and bool((ratio < 1 - ref.CLIP).any()) and bool(((ratio - 1).abs() < ref.CLIP).any())
+            dvo = (v - s["groups"]["v_old"].double()).abs()
+            assert bool((dvo > ref.VALUE_CLIP).any()) and bool((dvo < ref.VALUE_CLIP).any())
+
+
+# ---- 5. kernel resources ------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.skipif(not (os.path.isfile(LIB_PATH) and all(os.path.isfile(os.path.join(LLVM, t)) for t in TOOLS)),
+                    reason="needs the built HIP engine and the ROCm LLVM tools")
+def test_mat_grad_kernel_uses_no_scratch(tmp_path):
+    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "dev.co")
+    subprocess.check_call([f"{LLVM}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", LIB_PATH, str(tmp_path / "stripped.so")])
+    subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
+    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
+    mine = []
+    for blk in notes.split("- .agpr_count:")[1:]:
+        f = dict(re.findall(r"\.(\w+):\s*(\S+)", ".agpr_count:" + blk))
+        if f.get("name", "") == "k_mat_grad":                     # extern "C": the name a kernel trace shows
+            mine.append(f)
+    assert len(mine) == 1
+    f = mine[0]
+    print(f["name"], "vgpr", f["vgpr_count"], "sgpr", f["sgpr_count"], "spills", f["vgpr_spill_count"], f["sgpr_spill_count"], "scratch",
+          f["private_segment_fixed_size"], "static lds", f.get("group_segment_fixed_size", 0))
+    assert int(f["private_segment_fixed_size"]) == 0 and int(f["vgpr_spill_count"]) == 0, f
+    assert int(f["vgpr_count"]) <= 128, "1024 threads per workgroup: 128 registers each"
+    assert int(f.get("group_segment_fixed_size", 0)) == 0, "all LDS is dynamic: the rule is the whole footprint"
+
+
+# ---- 6. the wrong variants against the GPU test's bound ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("A", [1, 2, 4])
+@pytest.mark.parametrize("name", list(mat_ref.SHAPES))
+def test_wrong_variants_lie_outside_twice_the_gpu_bound(name, A):
+    """each variant misses 2 K_MAT_GPU_OF 2^-24 S_n on at least one tensor at every shape where it can differ.  Cannot differ: the mask, the scale and
+    attn2's query path at A' = 1 (mat_grad_ref.NEEDS_AGENTS).  The tanh approximation's derivative at E = 4 is asserted on inputs of its own
+    (mat_grad_ref.TANH_GELU_AT_E4: the inputs were changed, not the bound)"""
+    E = mat_ref.SHAPES[name]
+    kg = ref.K_MAT_GPU_OF[E]
+    cfg = CFGS["joint+dual+vclip"]
+    net, b = ref.k_case(name, A, 65, 1)
+    n64 = mat_ref.doubles(net)
+    g64, _, S, _ = ref.reference(net, b, cfg)
+    for variant in ref.WRONG:
+        if A == 1 and variant in ref.NEEDS_AGENTS:
+            continue
+        if variant == "tanh_gelu" and E == 4:
+            count, seed = ref.TANH_GELU_AT_E4[A]
+            net4, b4 = ref.k_case(name, A, count, seed)
+            g4, _, S4, _ = ref.reference(net4, b4, cfg)
+            r, at = ref.ratio_to_bound(ref.manual(mat_ref.doubles(net4), b4, cfg, variant)[0], g4, S4)
+        else:
+            r, at = ref.ratio_to_bound(ref.manual(n64, b, cfg, variant)[0], g64, S)
+        print(f"mat_grad_wrong {name} A'={A} {variant}: {r / (2 * kg):.2f} x (2 K_MAT_GPU_OF 2^-24 S_n) at {at}")
+        assert r > 2 * kg, (name, A, variant, r, at)

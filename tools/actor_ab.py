@@ -4,8 +4,11 @@ T = 200, two 64 x 64 tanh networks.  --kinds: a comma list out of
     gru        a GRU cell in both networks: k_actor_gru      gru_norms  the cells and both norms: k_actor_gru_ln
     mat        the Multi-Agent Transformer at n_embd = --hidden: k_actor_mat (not in the default list: a parent library may not know it).  Its paths:
                rollout(T) per step, and the same steps with the torch twin around step_torch -- MATNet.act on the device, then
-               mqe_openrl_wrapper.step_torch, no host synchronisation in the loop; it has no gradient inside the engine, so no ppo_update path,
-               and its digest covers the first rollout's actions, logp, value and the advantages of gae
+               mqe_openrl_wrapper.step_torch, no host synchronisation in the loop; one ppo_update(transformer=True) epoch (k_mat_grad: per slice
+               k_joint_expand, the gradient, k_mat_reduce, Adam) and the same epoch by a torch learner -- MATNet on the device, autograd of the same
+               loss over the same number of slices, clip_grad_norm_, torch.optim.Adam, then sync_actor() -- which is the only way a library without
+               the gradient has (such a library is noticed and measured through the torch learner alone).  Its digest covers the first rollout's
+               actions, logp, value and the advantages of gae
   default     one process, one handle of the same scene per kind, the windows of all of them alternated --rounds times:
               rollout(T) per step, every kind: the physics launches are the same on every handle, so a difference of medians is a difference of the
                   rollout kernels (+ the recorded tails, for "recorded");
@@ -91,6 +94,13 @@ def measure(a, say):
             digest[kind] = h.hexdigest()
             handles[kind] = (eng, traj, False, env)
             twin = (net, obs)
+            try:                                       # a library of the parent commit refuses the flag as unknown; any other failure is one
+                eng.ppo_grad(traj, first=0, count=T * a.envs // mb, transformer=True, **kw)
+                mat_grad = True
+            except RuntimeError as e:
+                if "unknown bits in flags" not in str(e) and "not in the engine yet" not in str(e):
+                    raise
+                mat_grad = False
             continue
         actor, critic = networks(env.observation_space.shape[0], a.hidden, norms, recurrent, dev)
         env.set_actor(actor, critic, log_std=torch.full((3,), -0.5, device=dev), **({"layer_norm": True} if norms else {}), **({"recurrent": True} if recurrent else {}),
@@ -130,13 +140,18 @@ def measure(a, say):
         eng, traj, recurrent, _ = handles[a.trace_only]
         for _ in range(2):
             eng.rollout(T, out=traj, **({"record_hidden": True} if recurrent else {}))
+        if a.trace_only == MAT_KIND and mat_grad:
+            grad, stats = torch.empty(eng.actor_params()["flat"].numel(), device=dev), torch.empty(6, device=dev)
+            perm = torch.randperm(T * a.envs, device=dev).to(torch.int32)
+            for _ in range(9):
+                eng.ppo_grad(traj, index=perm, first=0, count=T * a.envs // mb, out=(grad, stats), transformer=True, **kw)
         if not recurrent and a.trace_only != MAT_KIND:
             grad, stats = torch.empty(eng.actor_params()["flat"].numel(), device=dev), torch.empty(6, device=dev)
             perm = torch.randperm(total, device=dev).to(torch.int32)
             for _ in range(9):
                 eng.ppo_grad(traj, index=perm, first=0, count=total // mb, out=(grad, stats), **kw)
         torch.cuda.synchronize()
-        print(f"trace-only {a.trace_only}: {3 * T} rollout steps" + ("" if recurrent or a.trace_only == MAT_KIND else f" and 10 gradient calls (minibatch of {total // mb} samples)") + " done")
+        print(f"trace-only {a.trace_only}: {3 * T} rollout steps" + ("" if recurrent or (a.trace_only == MAT_KIND and not mat_grad) else f" and 10 gradient calls (minibatch of {total // mb} samples)") + " done")
     else:
         say(f"go1gate {a.envs} envs x 2 agents, T = {T}: {total} samples, {mb} minibatches of {total // mb}, hidden {a.hidden} x {a.hidden} tanh, "
             f"{torch.cuda.get_device_name(0)}, library {os.environ.get('MQE_HIP_LIB', 'in-tree')}, kinds {','.join(a.kinds)}")
@@ -153,6 +168,33 @@ def measure(a, say):
                             state["obs"] = state["w"].step_torch(act)[0]
                 paths[f"rollout per step, {kind}"] = (lambda eng=eng, traj=traj: eng.rollout(T, out=traj), 1e3 / T, "us")
                 paths[f"torch twin + step_torch, {kind}"] = (torch_steps, 1e3 / T, "us")
+                learner = torch.optim.Adam(net.parameters(), lr=1e-4)
+                G, D = T * a.envs, traj.obs.shape[-1]
+                flat = dict(obs=traj.obs[:T].reshape(G, 2, D), act=traj.actions.reshape(G, 2, 3), lpo=traj.logp.reshape(G, 2), vo=traj.value[:T].reshape(G, 2),
+                            adv=traj.advantages.reshape(G, 2), ret=traj.returns.reshape(G, 2))
+
+                def torch_epoch(net=net, env=env, flat=flat, G=G):
+                    """ppo_update(transformer=True)'s epoch in torch: the same loss (csrc/kernels_mat_grad.hpp), slices, norm clip and optimiser"""
+                    perm = torch.randperm(G, device=dev)
+                    per = G // mb
+                    for b in range(mb):
+                        g = perm[b * per:] if b + 1 == mb else perm[b * per:(b + 1) * per]
+                        _, logp, v = net.evaluate(flat["obs"][g], flat["act"][g])
+                        ratio, adv, vo, ret = torch.exp(logp - flat["lpo"][g]), flat["adv"][g], flat["vo"][g], flat["ret"][g]
+                        l_pi = -torch.minimum(ratio * adv, torch.clamp(ratio, 1 - kw["clip"], 1 + kw["clip"]) * adv).mean()
+                        v_c = vo + torch.clamp(v - vo, -kw["value_clip"], kw["value_clip"])
+                        l_v = torch.maximum((v - ret) ** 2, (v_c - ret) ** 2).mean()
+                        entropy = torch.log(net.sigma()).sum() + 1.5 * (1.0 + 1.8378770664093453)
+                        loss = l_pi + kw["value_coef"] * l_v - kw["entropy_coef"] * entropy
+                        learner.zero_grad(set_to_none=True)
+                        loss.backward()
+                        torch.nn.utils.clip_grad_norm_(net.parameters(), 1.0)
+                        learner.step()
+                    env.sync_actor()
+                if mat_grad:
+                    paths[f"ppo_update epoch, {kind}, on-device"] = (lambda eng=eng, traj=traj: eng.ppo_update(
+                        traj, epochs=1, minibatches=mb, lr=1e-4, max_grad_norm=1.0, transformer=True, **kw), 1.0, "ms")
+                paths[f"ppo_update epoch, {kind}, torch learner"] = (torch_epoch, 1.0, "ms")
             elif recurrent:
                 plain = eng.rollout(T)
                 paths[f"rollout per step, {kind}"] = (lambda eng=eng, plain=plain: eng.rollout(T, out=plain), 1e3 / T, "us")
