@@ -30,6 +30,21 @@ gradient, and over E = 4 features (and with ten norms in a row) what remains is 
 constant for all widths would let E = 64 and E = 12 pass with 20 and 40 times the error a float32 evaluation of THEM shows.  So the bound a width is held to
 is the maximum of ITS row, rounded up (K_MAT_CPU_OF; never above K_MAT_CPU, so no test asks less than the one constant would), and K_MAT_GPU_OF = 4 x that:
 the project's margin for a kernel that differs from the CPU by its expf / erff.  None of them is taken from anything the kernel computes.
+BEYOND D = 16 AND E = 64 the same measurement per (E, D) (K_CASES_AT: the A' the GPU cases run at that pair, the four counts, both losses, three seeds,
+both evaluations); largest ratio per pair and count:
+                           count = 1       31       65      520
+    (68, 16)  A' in {2, 4}     162.0    120.0    106.4     44.1
+    (72, 16)  A' in {2, 4}     190.6    243.6    200.9     28.8
+    (72, 13)  A' = 1            85.1     54.6     57.1     21.8
+    (72, 34)  A' = 2            81.4    155.5     82.1     34.1
+    (12, 34)  A' = 2            65.8    188.5    127.7    184.2
+    (4, 34)   A' = 2           353.6    249.9    243.1   6798.2
+    (12, 14)  A' = 2          2016.1    100.4     66.3     51.7
+    (12, 20)  A' = 2           959.7     77.4    135.7     23.1
+(the same with torch running 1, 16 and its default number of threads, but (72, 13) at 520 groups: 21.5 .. 21.8, and (12, 34) at one group: 65.8 .. 66.0).
+K_MAT_CPU_AT is each row's maximum rounded up, K_MAT_GPU_AT = 4 x that.  The two one-group maxima, (12, 14) seed 2 at mat.dec.attn1.query.weight and
+(12, 20) seed 1 at mat.enc.attn.query.weight, are the E = 4 effect in one group: S_n of a query weight is made of ds, which a single group's softmax
+leaves small, and the roundings behind it are not.  (4, 34): mat.enc.obs_fc.weight, 520 groups, seed 2, plain, autograd on the whole batch.
 
 THE WRONG VARIANTS (manual(variant=...)), each the float64 backward with one thing wrong: "no_r" the softmax Jacobian's - r_i term dropped; "mask_ignored"
 dv and dk summed with the UNMASKED probabilities; "no_scale" c missing from dq and dk; "no_res_rep" the decoder's residual path into rep dropped;
@@ -59,8 +74,18 @@ LOSSES = {"plain": dict(joint=False, dual_clip=None, value_clip=None), "joint+du
 CFG = dict(clip=CLIP, value_coef=0.7, entropy_coef=0.01, value_clip=VALUE_CLIP, joint=False, dual_clip=None)
 K_COUNTS = (1, 31, 65, 520)
 K_CASES = [(name, Aw, count, loss, seed) for name in mat_ref.SHAPES for Aw in (1, 2, 4) for count in K_COUNTS for loss in LOSSES for seed in (0, 1, 2)]
+# beyond D = 16 and E = 64: per (n_embd, D) the A' measured (those the GPU cases run there) and the row of the second table above, rounded up
+K_AT_AGENTS = {(68, 16): (2, 4), (72, 16): (2, 4), (72, 13): (1,), (72, 34): (2,), (12, 34): (2,), (4, 34): (2,), (12, 14): (2,), (12, 20): (2,)}
+K_MAT_CPU_AT = {(68, 16): 163.0, (72, 16): 244.0, (72, 13): 86.0, (72, 34): 156.0, (12, 34): 189.0, (4, 34): 6799.0, (12, 14): 2017.0, (12, 20): 960.0}
+K_MAT_GPU_AT = {at: 4 * k for at, k in K_MAT_CPU_AT.items()}
+K_CASES_AT = [(at, Aw, count, loss, seed) for at, agents in K_AT_AGENTS.items() for Aw in agents for count in K_COUNTS for loss in LOSSES for seed in (0, 1, 2)]
 # the trajectories of tests/test_mat_grad_gpu.py: (N, A', T, D) and the widths; tests/test_mat_grad.py checks the generator's condition at every one
-GPU_SHAPES = {"gate": ((37, 2, 3, 16), (64, 12, 4)), "football": ((17, 4, 4, 16), (12, 64)), "plane": ((70, 1, 2, 13), (12, 64)), "many": ((129, 2, 64, 16), (12,))}
+GPU_SHAPES = {"gate": ((37, 2, 3, 16), (64, 12, 4, 68, 72)), "football": ((17, 4, 4, 16), (12, 64, 72)), "plane": ((70, 1, 2, 13), (12, 64, 72)),
+              "many": ((129, 2, 64, 16), (12,)),
+              # the real tasks' own observations (go1sheep-hard, go1seesaw, go1football-defender)
+              "sheep": ((37, 2, 3, 34), (72, 12, 4)), "seesaw": ((37, 2, 3, 14), (12,)), "defender": ((37, 2, 3, 20), (12,))}
+# the widths of a set held to K_MAT_GPU_AT[(E, D)]; every other to K_MAT_GPU_OF[E], as before
+EDGE_WIDTHS = {"gate": (68, 72), "football": (72,), "plane": (72,), "sheep": (72, 12, 4), "seesaw": (12,), "defender": (12,)}
 _SYNTH, _POOL = {}, {}
 
 
@@ -84,6 +109,16 @@ def k_case(name, Aw, count, seed, D=16):
     return net, {k: v[:count] for k, v in b.items()}
 
 
+def k_case_at(E, D, Aw, count, seed):
+    """k_case at a pair of K_MAT_CPU_AT: the same seeds, the width and the observation size given"""
+    key = (E, D, Aw, seed)
+    if key not in _POOL:
+        net = mat_ref.make_net(D, E, 500 + seed)
+        _POOL[key] = (net, kink_free(net, max(K_COUNTS), Aw, D, 100 * seed + Aw)[0])
+    net, b = _POOL[key]
+    return net, {k: v[:count] for k, v in b.items()}
+
+
 WRONG = ("no_r", "mask_ignored", "no_scale", "no_res_rep", "no_query_rep", "enc_value_only", "tanh_gelu", "no_one_minus_sigmoid")
 # cannot differ at A' = 1: one row, nothing masked; and p = 1 there, so ds = 0 and dq = dk = 0 -- with or without the scale, and nothing reaches rep through
 # attn2's query
@@ -91,6 +126,9 @@ NEEDS_AGENTS = ("mask_ignored", "no_scale", "no_query_rep")
 # the inputs on which the tanh_gelu variant is held to the bound at E = 4, per A': (groups, seed) of k_case.  With many groups S_n (a sum of absolute
 # contributions) outgrows the variant's error, whose sign varies; with a few it does not
 TANH_GELU_AT_E4 = {1: (4, 0), 2: (1, 3), 4: (8, 0)}
+# the same at the pairs of K_MAT_CPU_AT whose bound is as loose, (E, D) -> A' -> (groups, seed) of k_case_at: E = 4 keeps its rule; at (12, 14) the row's
+# maximum is a one-group case (2016; with 31 groups and more the pair stays below 101), and with 65 groups the variant reads 0.28 of the doubled bound
+TANH_GELU_AT = {(4, 34): {2: TANH_GELU_AT_E4[2]}, (12, 14): {2: (1, 0)}}
 KEYS = ("obs", "actions", "logp_old", "v_old", "adv", "ret")
 
 

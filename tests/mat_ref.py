@@ -12,6 +12,25 @@ from mqe.utils.actor_net import MATNet
 # n_embd of the shapes: the reference's width; a width that is neither a power of two nor a multiple of 8; the smallest the engine accepts
 SHAPES = {"e64": 64, "e12": 12, "e4": 4}
 VARIANTS = ("no_mask", "s_zero", "no_scale", "exp_sigma", "tanh_gelu")
+# the edges of what the engine accepts, for the rollout: (scene, A', D, E).  NOT part of SHAPES: every test parametrised over SHAPES keeps its cases.
+#   E = 68: a second, partial pass of actor_layer's 16 x 4 outputs (4 left), norm chunks of 5 with the last three wavefronts empty
+#   E = 92: the largest width mqe_actor_create accepts; 28 outputs in the second pass; norm chunks of 6, the last wavefront with 2
+#   go1plane with the seesaw task kind: A' = 1, D = 13 -- nothing on the 16-byte grid
+#   go1sheep-hard: D = 34 (629 rows of LDS at E = 92, 300 bytes under the limit; D > E at E = 12; D > 5 E at E = 4), a scene with NPCs
+#   go1seesaw D = 14, go1football-defender D = 20: the real tasks' own observations; at D = 14 and 34 obs_fc loads dwords, every E x E matrix 16 bytes
+EDGE_SHAPES = {"gate-e68": ("go1gate", 2, 16, 68), "gate-e92": ("go1gate", 2, 16, 92), "plane-e92": ("go1plane", 1, 13, 92),
+               "sheep-e92": ("go1sheep-hard", 2, 34, 92), "sheep-e12": ("go1sheep-hard", 2, 34, 12), "sheep-e4": ("go1sheep-hard", 2, 34, 4),
+               "seesaw-e64": ("go1seesaw", 2, 14, 64), "defender-e12": ("go1football-defender", 2, 20, 12)}
+# envs of a scene in the GPU tests: 74 rows = one full tile and one partial; 70 rows at A' = 1
+EDGE_ENVS = {"go1gate": 37, "go1plane": 70, "go1sheep-hard": 37, "go1seesaw": 37, "go1football-defender": 37}
+# (make_net's seed, inputs' seed) of an edge shape's one-step test: SHAPES' rule (the name's length, E) unless a wrong variant missed the factor there
+EDGE_SEEDS = {}
+# with one agent nothing is masked, nothing conditions and the one probability is 1 with or without the scale: these cannot differ at A' = 1
+NEED_AGENTS = ("no_mask", "s_zero", "no_scale")
+
+
+def edge_seeds(name):
+    return EDGE_SEEDS.get(name, (len(name), EDGE_SHAPES[name][3]))
 
 
 def make_net(D, E, seed=0):

@@ -204,3 +204,34 @@ def test_wrong_variants_are_far_outside_the_bound(name):
             ratio = dev / (4 * yard)
             print(f"mat_wrong {name} {variant}: {what} deviation {dev:.3e} over 4 x yardstick {yard:.3e} = {ratio:.1f}")
             assert ratio >= 100, (name, variant, ratio)
+
+
+@pytest.mark.parametrize("name", list(ref.EDGE_SHAPES))
+def test_wrong_variants_are_far_outside_the_bound_at_the_edge_shapes(name):
+    """The same on the inputs, seeds and shapes of tests/test_mat_gpu.py's one-step test at mat_ref.EDGE_SHAPES (the scene's envs x A' agents, its D):
+    at least 100 x the bound for every variant that can differ.  At A' = 1 three cannot (mat_ref.NEED_AGENTS).  A shape whose seeds are not SHAPES'
+    rule is listed in mat_ref.EDGE_SEEDS: the seed was changed there, not the factor."""
+    task, A, Dd, E = ref.EDGE_SHAPES[name]
+    pseed, iseed = ref.edge_seeds(name)
+    n32 = ref.make_net(Dd, E, seed=pseed)
+    n64 = ref.doubles(n32)
+    obs, z = ref.inputs(ref.EDGE_ENVS[task], A, Dd, seed=iseed)
+    with torch.no_grad():
+        actions, _, _ = n64.act(obs.double(), z=z.double())
+        y = ref.yardstick(n32, n64, obs, actions.float())
+        for variant in ref.VARIANTS:
+            if A == 1 and variant in ref.NEED_AGENTS:
+                continue
+            m, lp, v = ref.wrong_evaluate(n64, obs.double(), actions.float().double(), variant)
+            what, dev, yard = ("logp", float((lp - y["logp64"]).abs().max()), y["yard_logp"]) if variant == "exp_sigma" else \
+                              ("mean", float((m - y["mean64"]).abs().max()), y["yard_mean"])
+            ratio = dev / (4 * yard)
+            print(f"mat_wrong {name} {variant}: {what} deviation {dev:.3e} over 4 x yardstick {yard:.3e} = {ratio:.1f}")
+            assert ratio >= 100, (name, variant, ratio)
+
+
+def test_lds_rule_at_the_largest_observation_of_a_real_task():
+    """go1sheep-hard's D = 34: E = 92 is 629 rows, 300 bytes under the limit; E = 96 is the first width refused there"""
+    assert abi.actor_mat_lds_bytes(34, 92) == 629 * 260 == abi.MAT_LDS_LIMIT - 300
+    assert abi.actor_mat_lds_bytes(34, 92) <= abi.MAT_LDS_LIMIT < abi.actor_mat_lds_bytes(34, 96)
+    assert abi.actor_mat_lds_bytes(16, 92) == 611 * 260

@@ -3,7 +3,8 @@ HipEngine.create_actor(transformer=True)): (1) one deterministic step against fl
 MATNet; (2) twelve recorded stochastic steps: the conditioning on the SAMPLED actions, the draws, logp, value; (3) the acting pass against the parallel
 pass; (4) continuation, checkpoint, determinism, shards; (5) A' = 4 and A' = 1; (6) gae under value normalisation and Adam on a torch gradient;
 (7) refusals; (8) the task wrapper's surface.  go1gate with 37 envs = 74 rows: one full workgroup and one partial; max_episode_length=5: every env
-resets inside a 12-step window.
+resets inside a 12-step window.  (1) and (2) run again at mat_ref.EDGE_SHAPES -- E = 68 and 92, D = 13, 14, 20 and 34, the real tasks' own scenes -- and (7)
+has the refusal boundary at D = 34.
 
 THE HANDLES WITH A' = 4 AND A' = 1 are tests/test_joint_loss_gpu.py's: go1football-2vs2 and go1plane with the descriptor's task kind set to the
 seesaw wrapper's.  Those tests never step such a handle; a rollout does.  What a step of it runs that the stock scenes do not: the seesaw branch of
@@ -78,12 +79,41 @@ def test_one_step_against_float64(name):
     eng.close()
 
 
+def edge_engine(task):
+    """the cached handle of a scene of mat_ref.EDGE_SHAPES: its own task kind, but go1plane, which takes the seesaw wrapper's (the module docstring)"""
+    if ("edge", task) not in _CACHE:
+        n = ref.EDGE_ENVS[task]
+        if task == "go1plane":
+            d, k, _ = make_desc(task, n)
+            d.task = abi.TASK["seesaw"]
+            _CACHE["edge", task] = hip_engine(d, k)
+        else:
+            _CACHE["edge", task] = engine(task, n, max_episode_length=5)
+        _CACHE["edge", task].reset_all()
+    return _CACHE["edge", task]
+
+
+@pytest.mark.parametrize("name", list(ref.EDGE_SHAPES))
+def test_one_step_at_the_edge_shapes(name):
+    """mat_ref.EDGE_SHAPES: a second, partial output pass (E = 68, 92), the largest LDS image (E = 92 at D = 34), D off the 16-byte grid beside aligned
+    E x E matrices (D = 14, 34; nothing aligned at D = 13), D > E and D > 5 E, a scene with NPCs.  tests/test_mat.py holds the wrong variants to at least
+    100x this bound on these inputs, seeds and shapes"""
+    task, A, Dd, E = ref.EDGE_SHAPES[name]
+    eng, n = edge_engine(task), ref.EDGE_ENVS[task]
+    assert tuple(int(x) for x in eng.tensor(abi.T_WRAPPER_OBS).shape) == (n, A, Dd)
+    assert abi.actor_mat_lds_bytes(Dd, E) <= abi.MAT_LDS_LIMIT
+    pseed, iseed = ref.edge_seeds(name)
+    net = install(eng, E, seed=pseed)
+    one_step(eng, net, n, A, Dd, iseed, name)
+
+
 # ---- 2. twelve steps, recorded, stochastic --------------------------------------------------------------------------------------------------------------
-def recorded(name, seed=11, T=12):
-    key = (name, seed, T)
+def recorded(name, seed=11, T=12, task="go1gate"):
+    """name: a key of mat_ref.SHAPES on go1gate, or the width itself"""
+    key = (name, seed, T, task)
     if key not in _CACHE:
-        eng = engine("go1gate", N, seed=seed, max_episode_length=5)
-        net = install(eng, ref.SHAPES[name], seed=3)
+        eng = engine(task, N, seed=seed, max_episode_length=5)
+        net = install(eng, ref.SHAPES[name] if name in ref.SHAPES else name, seed=3)
         eng.reset_all()
         traj = eng.rollout(T)
         torch.cuda.synchronize()
@@ -94,7 +124,18 @@ def recorded(name, seed=11, T=12):
 
 @pytest.mark.parametrize("name", ["e64", "e12"])
 def test_twelve_recorded_steps(name):
-    r = recorded(name)
+    check_recorded(recorded(name), name)
+
+
+@pytest.mark.parametrize("task,E", [("go1sheep-hard", 12), ("go1gate", 92)])
+def test_six_recorded_steps_at_the_edges(task, E):
+    """the same window, six steps with every env reset inside it: D = 34 > E in a scene with NPCs; the largest width"""
+    r = recorded(E, T=6, task=task)
+    assert r["obs"].shape == (7, N, AW, ref.EDGE_SHAPES["sheep-e12" if task == "go1sheep-hard" else "gate-e92"][2])
+    check_recorded(r, f"{task} E={E}")
+
+
+def check_recorded(r, name):
     T, net = r["T"], r["net"]
     n64 = ref.doubles(net)
     assert bool(r["done"].any(dim=0).all()), "every env resets at least once inside the window"
@@ -323,6 +364,24 @@ def test_refusals():
     eng2.create_actor([D, 7, 3], [D, 5, 1])
     assert same_bits(eng2.rollout(2).actions, plain.actions)
     eng.close(); eng2.close()
+
+
+def test_refusal_boundary_at_the_widest_observation():
+    """go1sheep-hard, D = 34: E = 92 (629 LDS rows, 300 bytes under the limit) is created and steps; E = 96 is refused by name, and the actor that was there
+    keeps its parameters and produces the bits it produced"""
+    eng, Dd = edge_engine("go1sheep-hard"), 34
+    n = ref.EDGE_ENVS["go1sheep-hard"]
+    assert abi.actor_mat_lds_bytes(Dd, 92) <= abi.MAT_LDS_LIMIT < abi.actor_mat_lds_bytes(Dd, 96)
+    net = install(eng, 92, seed=4)
+    before, _, obs0 = one_step(eng, net, n, AW, Dd, 92, "D = 34, E = 92 in front of the refusal")
+    with pytest.raises(RuntimeError, match=r"mqe_actor_create failed \(-6\)") as ei:
+        eng.create_actor([Dd, 96, 3], None, transformer=True)
+    assert "E = 96" in str(ei.value) and "actor_dims" in str(ei.value)
+    views = eng.actor_params()
+    assert views["flat"].numel() == ref.param_count(Dd, 92) and torch.equal(views["flat"].cpu(), ref.flat_params(net))
+    after = eng.rollout(1, obs0=obs0.to(eng.torch_device), deterministic=True)
+    torch.cuda.synchronize()
+    assert same_bits(after.actions, before.actions) and same_bits(after.value[0], before.value[0]) and same_bits(after.logp, before.logp)
 
 
 # ---- 8. the public surface: FusedTaskWrapper ------------------------------------------------------------------------------------------------------------------

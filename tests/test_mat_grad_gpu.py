@@ -34,9 +34,10 @@ def handle(what):
     """the engine of mat_grad_ref.GPU_SHAPES[what]: go1gate, or a stock scene with the seesaw wrapper's task observation (tests/test_mat_gpu.py)"""
     if what not in _HANDLES:
         (N, Aw, _, D), _ = ref.GPU_SHAPES[what]
-        task = {"gate": "go1gate", "many": "go1gate", "football": "go1football-2vs2", "plane": "go1plane"}[what]
+        task = {"gate": "go1gate", "many": "go1gate", "football": "go1football-2vs2", "plane": "go1plane", "sheep": "go1sheep-hard", "seesaw": "go1seesaw",
+                "defender": "go1football-defender"}[what]
         d, k, _ = make_desc(task, N)
-        if task != "go1gate":
+        if what in ("football", "plane"):                         # every other scene keeps its own task kind
             d.task = abi.TASK["seesaw"]
         eng = hip_engine(d, k)
         assert tuple(int(x) for x in eng.tensor(abi.T_WRAPPER_OBS).shape) == (N, Aw, D)
@@ -80,10 +81,11 @@ def groups_of(s, first, count, use_index):
     return s["gindex"][first:first + count].long() if use_index else torch.arange(first, first + count)
 
 
-def check(s, t, b, cfg, what):
-    """gradient and statistics against float64 autograd within K_MAT_GPU_OF[E]; guards; every gradient element written"""
+def check(s, t, b, cfg, what, kg=None):
+    """gradient and statistics against float64 autograd within K_MAT_GPU_OF[E] (kg: the bound of an edge shape, K_MAT_GPU_AT[(E, D)]); guards; every
+    gradient element written"""
     n, E = s["n_params"], s["E"]
-    kg = ref.K_MAT_GPU_OF[E]
+    kg = ref.K_MAT_GPU_OF[E] if kg is None else kg
     gi, si = t["grad"].cpu(), t["stats"].cpu()
     assert bool((gi[n:] == SENT).all()) and bool((si[6:] == SENT).all()), f"{what}: a guard word was written"
     assert not bool((gi[:n] == SENT).any()) and not bool((si[:6] == SENT).any()), f"{what}: an output element was not written"
@@ -174,6 +176,94 @@ def test_other_agent_counts(what, E):
         t = upload(s, eng.torch_device)
         assert call(eng, s, t, first, count, use_index, cfg) == 0, eng.lib.mqe_last_error().decode()
         check(s, t, ref.batch(s, groups_of(s, first, count, use_index)), cfg, f"{what} A'={s['Aw']} E={E} joint={cfg['joint']} count={count} first={first}")
+
+
+# ---- 3b. the edges: E > 64, the widest width the gradient serves, the real tasks' observation sizes ----------------------------------------------------------
+EDGES = [(what, E) for what, widths in ref.EDGE_WIDTHS.items() for E in widths]
+
+
+@pytest.mark.parametrize("what,E", EDGES, ids=[f"{what}-e{E}" for what, E in EDGES])
+def test_gradient_and_statistics_at_the_edges(what, E):
+    """E = 68 and 72: a second, partial pass of the GELU loops and of actor_layer (4 and 8 outputs), norm chunks of 5 with empty wavefronts; E = 72: the largest
+    LDS image (619 rows) and tape (2 D + 2900 rows); D = 14, 20, 34: the observation off the 16-byte grid beside aligned E x E matrices, T = max(D, E) = D at
+    E = 12, G = E + D at E = 4 (the observation's gradient slot over slabs B1 .. REP).  The three selections of test 1 with the value clip on, held to
+    K_MAT_GPU_AT[(E, D)]"""
+    s = ref.gpu_synth(what, E)
+    eng = handle(what)
+    install(eng, s)
+    kg = ref.K_MAT_GPU_AT[(E, s["D"])]
+    cfg = dict(ref.CFG)
+    assert cfg["value_clip"] == ref.VALUE_CLIP
+    for count, first, use_index in ((s["n_groups"], 0, False), (45, 5, True), (1, 7, True)):
+        t = upload(s, eng.torch_device)
+        assert call(eng, s, t, first, count, use_index, cfg) == 0, eng.lib.mqe_last_error().decode()
+        check(s, t, ref.batch(s, groups_of(s, first, count, use_index)), cfg, f"{what} E={E} D={s['D']} A'={s['Aw']} count={count} first={first} index={use_index}", kg)
+
+
+@pytest.mark.parametrize("what,E", [("football", 72), ("sheep", 4)])
+def test_joint_ratio_and_dual_clip_at_the_edges(what, E):
+    s = ref.gpu_synth(what, E)
+    eng = handle(what)
+    install(eng, s)
+    cfg = dict(ref.CFG, joint=True, dual_clip=ref.DUAL)
+    first, count = 3, s["n_groups"] // 2 + 1
+    t = upload(s, eng.torch_device)
+    assert call(eng, s, t, first, count, True, cfg) == 0, eng.lib.mqe_last_error().decode()
+    check(s, t, ref.batch(s, groups_of(s, first, count, True)), cfg, f"{what} E={E} D={s['D']} A'={s['Aw']} joint+dual count={count} first={first}",
+          ref.K_MAT_GPU_AT[(E, s["D"])])
+
+
+@pytest.mark.parametrize("what", ["gate", "sheep"])
+def test_the_widest_width_and_the_first_refused(what):
+    """D = 16 and D = 34: E = 72 is served; E = 76, which mqe_actor_create accepts, is refused with -5 naming the width and the bytes of the rule, and writes
+    nothing; a plain actor created afterwards produces the gradient bits it produced before"""
+    import test_ppo_gpu as P
+    sp = P.synth("tanh7", "go1gate", 5, 24)
+    plain_eng = P.handle("go1gate", 5)
+    P.install(plain_eng, sp)
+    tp = P.upload(sp, plain_eng.torch_device)
+    assert P.call(plain_eng, sp, tp, 3, 100, True) == 0
+    torch.cuda.synchronize()
+    plain_bits = tp["grad"].clone()
+    s = ref.gpu_synth(what, 72)
+    D = s["D"]
+    assert abi.mat_grad_lds_bytes(D, 72) <= abi.MATG_LDS_LIMIT < abi.mat_grad_lds_bytes(D, 76) and abi.actor_mat_lds_bytes(D, 76) <= abi.MAT_LDS_LIMIT
+    eng = handle(what)
+    install(eng, s)
+    cfg = dict(ref.CFG)
+    t = upload(s, eng.torch_device)
+    assert call(eng, s, t, 0, 10, False, cfg) == 0, eng.lib.mqe_last_error().decode()
+    check(s, t, ref.batch(s, torch.arange(10)), cfg, f"{what} E=72 D={D} in front of the refusal", ref.K_MAT_GPU_AT[(72, D)])
+    eng.create_actor([D, 76, 3], None, transformer=True)
+    n76 = mat_ref.param_count(D, 76)
+    wide = dict(s, E=76, n_params=n76, grad=np.full(n76 + 64, SENT, np.int32))
+    tw = upload(wide, eng.torch_device)
+    rc = call(eng, wide, tw, 0, 10, False, cfg)
+    msg = eng.lib.mqe_last_error().decode()
+    assert rc == -5 and "E = 76" in msg and str(abi.mat_grad_lds_bytes(D, 76)) in msg, (rc, msg)
+    assert bool((tw["grad"] == SENT).all()) and bool((tw["stats"] == SENT).all()), "a refused call wrote something"
+    P.install(plain_eng, sp)
+    tp3 = P.upload(sp, plain_eng.torch_device)
+    assert P.call(plain_eng, sp, tp3, 3, 100, True) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(tp3["grad"], plain_bits)
+
+
+def test_widths_in_ascending_order_on_one_handle():
+    """E = 12, then E = 72, then E = 12 again on one handle: tape and partials are the actor's and are released with it, so the wide actor gets its own
+    (11.2 times the rows) and the second narrow gradient has the bits of the first.  Every other test installs a set's widths in descending order"""
+    eng = handle("gate")
+    cfg = dict(ref.CFG, joint=True, dual_clip=ref.DUAL)
+    grads = []
+    for E in (12, 72, 12):
+        s = ref.gpu_synth("gate", E)
+        install(eng, s)
+        t = upload(s, eng.torch_device)
+        assert call(eng, s, t, 2, 100, True, cfg) == 0, eng.lib.mqe_last_error().decode()
+        kg = ref.K_MAT_GPU_AT[(72, 16)] if E == 72 else None
+        check(s, t, ref.batch(s, groups_of(s, 2, 100, True)), cfg, f"gate E={E} in the order 12, 72, 12", kg)
+        grads.append((t["grad"].clone(), t["stats"].clone()))
+    assert torch.equal(grads[0][0], grads[2][0]) and torch.equal(grads[0][1], grads[2][1]), "the same bits behind a wider actor on the same handle"
 
 
 # ---- 4. more tiles than workgroups ------------------------------------------------------------------------------------------------------------------------------
@@ -280,8 +370,18 @@ def test_update_on_a_real_rollout():
     float64 gradient of that minibatch.  The bound: ppo_ref.adam_tolerances for the step's own roundings, plus what the first Adam step makes of a gradient
     deviation dg = K_MAT_GPU_OF 2^-24 S_n (tests/test_ppo_gpu.py's propagation:  step_size ((1 - b1) dg / denom + |m'| sqrt((1 - b2)(2 |g| dg + dg^2)) /
     (bc2s denom^2))).  Then a deterministic step follows the moved twin, and the first statistics' KL and clip share are the float64 values"""
+    update_on_a_real_rollout("go1gate", 16, ref.K_MAT_GPU_OF[12])
+
+
+def test_update_on_a_real_rollout_of_a_scene_with_npcs():
+    """the same on go1sheep-hard: D = 34 > E = 12, the observations the scene itself produces, held to K_MAT_GPU_AT[(12, 34)]"""
+    update_on_a_real_rollout("go1sheep-hard", 34, ref.K_MAT_GPU_AT[(12, 34)])
+
+
+def update_on_a_real_rollout(task, D, kg):
     N, T, E, lr = 37, 6, 12, 1e-3
-    eng = engine("go1gate", N, seed=3, max_episode_length=5)
+    eng = engine(task, N, seed=3, max_episode_length=5)
+    assert tuple(int(x) for x in eng.tensor(abi.T_WRAPPER_OBS).shape) == (N, 2, D)
     net = install_net(eng, E, seed=9, value_norm=True)
     eng.reset_all()
     views = eng.actor_params()
@@ -301,7 +401,6 @@ def test_update_on_a_real_rollout():
     ret = torch.from_numpy(vref.normalise(traj.returns.cpu().numpy(), st[3], st[4]))      # the targets the update saw: its own new (mu, sigma)
     b = _traj_batch(traj, perm, ret)
     g64, st64, S, ss = ref.reference(net, b, cfg)
-    kg = ref.K_MAT_GPU_OF[E]
     for q in (4, 5):                                             # approximate KL, clip share
         assert abs(float(stats[0, 0, q]) - float(st64[q])) <= kg * EPS32 * float(ss[q]), (q, float(stats[0, 0, q]), float(st64[q]))
     g, dg = ref.flat(g64, net), ref.flat_bound(S, net) * (kg * EPS32) * 1.01
@@ -316,13 +415,13 @@ def test_update_on_a_real_rollout():
     moved = views["flat"].cpu().double()
     worst = float(((moved - p64).abs() / bound).max())
     sure = g.abs() > 100 * dg                                    # where the gradient's sign is beyond doubt the first step is lr against it
-    print(f"mat_update: parameters at {worst:.3f} of the propagated bound; {int(sure.sum())} of {g.numel()} elements with a sure sign")
+    print(f"mat_update {task}: parameters at {worst:.3f} of the propagated bound; {int(sure.sum())} of {g.numel()} elements with a sure sign")
     assert worst <= 1.0
     assert int(sure.sum()) > g.numel() // 4 and float(((moved - p0.double())[sure] + lr * torch.sign(g[sure])).abs().max()) <= 0.01 * lr
     # a deterministic step afterwards follows the moved twin
     with torch.no_grad():
         torch.nn.utils.vector_to_parameters(views["flat"].cpu().clone(), list(net.parameters()))
-    one_step(eng, net, N, 2, 16, 5, "after ppo_update(transformer=True)")
+    one_step(eng, net, N, 2, D, 5, f"{task} after ppo_update(transformer=True)")
     eng.close()
 
 
